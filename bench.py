@@ -7,12 +7,15 @@ of the 20 candidates, 3-D / pre-grasp points -- i.e. GraspPointSelector.select_g
 One "step" = one pass of that path over one batch of --batch frames already resident in HBM.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                 # + per-kernel figures and secondary legs
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR     # + the last step's results as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
 Frames are independent: with N ranks every rank scores its own batch (weak scaling, no data-path
 collective; torch.distributed is used only for the timing barrier and the max-over-ranks reduction).
-Rank 0 prints ONE JSON line (see README / DESIGN.md "Measurement").
+Rank 0 prints ONE JSON line (see README / DESIGN.md "Measurement").  A plain run sets up, warms up, times the steps and
+reports the headline; `--full` adds the per-kernel event times, rooflines, CPU baseline and the secondary legs.
 """
 import argparse
 import ctypes as C
@@ -296,6 +299,16 @@ def secondary_configs(args, dev, L, lib, SI, params, P, extra_frames, masks_np, 
     return out
 
 
+def dump_outputs(dirname, res):
+    """The timed path's results of its last step, as select_grasp_points_batch hands them to a caller: one row per frame of
+    grasp pixel (x, y), grasp point (X, Y, Z) and pre-grasp point, float64 (exact for the library's float32 / int32 values),
+    NaN where the frame has no such point."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, col, n in (("grasp_xy", 0, 2), ("grasp_xyz", 1, 3), ("pregrasp_xyz", 2, 3)):
+        rows = [r[col] if r[col] is not None else (np.nan,) * n for r in res]
+        np.save(os.path.join(dirname, name + ".npy"), np.array(rows, dtype=np.float64).reshape(len(res), n))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -305,31 +318,41 @@ def main():
                     help="frames per step per GPU (256 puts two sweep workgroups on every CU; 24 GB of the 288 GB)")
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--cpu-frames", type=int, default=5, help="frames timed for the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel event times, rooflines and kernel fractions, and the secondary legs "
+                         "sized by the options below (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the results of the last timed step as DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--cpu-frames", type=int, default=5, help="--full: frames timed for the cpu_baseline leg (0 = skip)")
     ap.add_argument("--no-cnn", action="store_true", help="CV-only (diagnostic; NOT the headline config)")
     ap.add_argument("--inflight", type=int, default=1,
                     help="batches in flight per GPU (each on its own handle, stream and host thread); >1 lets the "
                          "latency-bound sweeps of one batch run beside the CNN of another")
     ap.add_argument("--node-steps", type=int, default=3,
-                    help="extra, untimed-for-the-headline leg: steps of the WHOLE node sequence (batched leaf selection + "
+                    help="--full: extra, untimed-for-the-headline leg: steps of the WHOLE node sequence (batched leaf selection + "
                          "grasp selection) reported as `node_sequence` (0 = skip)")
     ap.add_argument("--train-steps", type=int, default=30,
-                    help="N=1 only: optimisation steps of the GraspPointCNN training step (lg_train_step: forward + backward + "
+                    help="--full, N=1 only: optimisation steps of the GraspPointCNN training step (lg_train_step: forward + backward + "
                          "clip + Adam) timed at the reference's batch size 16 and at 1024, reported as `train_step` (0 = skip)")
     ap.add_argument("--dense-steps", type=int, default=4,
-                    help="N=1 only: untimed passes of lg_final_kernel with EVERY tile on the stencil path (all-leaves masks, "
+                    help="--full, N=1 only: untimed passes of lg_final_kernel with EVERY tile on the stencil path (all-leaves masks, "
                          "constant-tile fast path off), reported as `roofline_dense` (0 = skip)")
     ap.add_argument("--h2d-steps", type=int, default=3,
-                    help="N=1 only: steps of pinned-host -> device copy of depth + mask followed by the scoring pass, reported "
+                    help="--full, N=1 only: steps of pinned-host -> device copy of depth + mask followed by the scoring pass, reported "
                          "as `h2d_inclusive` (never `value`; 0 = skip)")
     ap.add_argument("--pipelined", type=int, default=2,
-                    help="N=1 only: batches in flight for the secondary `pipelined` figure (the headline keeps --inflight; <= 1 = skip)")
+                    help="--full, N=1 only: batches in flight for the secondary `pipelined` figure (the headline keeps --inflight; <= 1 = skip)")
     ap.add_argument("--config-steps", type=int, default=5,
-                    help="N=1 only: timed steps per entry of the secondary `configs` leg (720p x 256, 4K x 64, 1080p x 32 = config 3's "
+                    help="--full, N=1 only: timed steps per entry of the secondary `configs` leg (720p x 256, 4K x 64, 1080p x 32 = config 3's "
                          "per-GPU share, and single-frame latency of select_grasp_point / the node sequence; 0 = skip)")
     ap.add_argument("--per-step", action="store_true", help="diagnostic: print every step's wall time to stderr "
                                                             "(adds a device sync per step; not the headline mode)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # the secondary legs (each also skipped by its own 0) run with --full only
+        args.cpu_frames = args.node_steps = args.train_steps = args.dense_steps = args.h2d_steps = args.config_steps = 0
+        args.pipelined = 0
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -412,28 +435,30 @@ def main():
             for t in th:
                 t.join()
 
-    # untimed passes: warm-up, then one pass with an event pair around EVERY kernel (kernels_ms, mfma);
-    # the timed region only keeps the dominant kernel's self-stamped events (mode 2: no extra stream packets)
+    # untimed passes: warm-up; with --full then one pass with an event pair around EVERY kernel (kernels_ms, mfma), and
+    # the timed region keeps the dominant kernel's self-stamped events (mode 2: no extra stream packets)
     run_steps(max(args.warmup, len(sels)) if args.warmup else 0)
-    for sel in sels:
-        lib.lg_profile_enable(sel._h, 1)
-    run_steps(2 * len(sels))
-    torch.cuda.synchronize(dev)
-    kern_all = {}
-    for name in ("prep", "bbox", "orient", "stem", "dt_hrun", "dt_search", "dt_band", "dt_fwd", "dt_bwd", "dt_border", "final", "topk", "gather", "cnn"):
-        tot_n, tot_ms = 0, 0.0
+    kern = {}
+    if args.full:
         for sel in sels:
-            n, ms = C.c_int(0), C.c_double(0.0)
-            lib.lg_profile_read(sel._h, name.encode(), C.byref(n), C.byref(ms))
-            tot_n += n.value
-            tot_ms += ms.value
-        if tot_n:
-            kern_all[name] = {"launches": tot_n, "avg_ms": tot_ms / tot_n}
-    for sel in sels:
-        lib.lg_profile_enable(sel._h, 2)
-    run_steps(len(sels))  # untimed rehearsal in exactly the timed configuration (the first such call costs a one-off ~40 ms)
-    for sel in sels:
-        lib.lg_profile_enable(sel._h, 2)  # reset the counters
+            lib.lg_profile_enable(sel._h, 1)
+        run_steps(2 * len(sels))
+        torch.cuda.synchronize(dev)
+        for name in ("prep", "bbox", "orient", "stem", "dt_hrun", "dt_search", "dt_band", "dt_fwd", "dt_bwd", "dt_border", "final", "topk",
+                     "gather", "cnn"):
+            tot_n, tot_ms = 0, 0.0
+            for sel in sels:
+                n, ms = C.c_int(0), C.c_double(0.0)
+                lib.lg_profile_read(sel._h, name.encode(), C.byref(n), C.byref(ms))
+                tot_n += n.value
+                tot_ms += ms.value
+            if tot_n:
+                kern[name] = {"launches": tot_n, "avg_ms": tot_ms / tot_n}
+        for sel in sels:
+            lib.lg_profile_enable(sel._h, 2)
+        run_steps(len(sels))  # untimed rehearsal in exactly the timed configuration (the first such call costs a one-off ~40 ms)
+        for sel in sels:
+            lib.lg_profile_enable(sel._h, 2)  # reset the counters
     barrier()
     t0 = time.perf_counter()
     run_steps(args.steps)
@@ -443,21 +468,21 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    res = [r for r in last if r is not None][0]
+    res = last[(args.steps - 1) % len(sels)]   # the worker that ran the last timed step
     assert all(r[0] is not None for r in res), "synthetic frames must yield a grasp point"
 
-    # per-kernel device time (HIP events recorded on the launch stream inside the library)
-    kern = dict(kern_all)
-    tot_n, tot_ms = 0, 0.0
-    for sel in sels:  # dominant kernel: HIP events over the TIMED region
-        n, ms = C.c_int(0), C.c_double(0.0)
-        lib.lg_profile_read(sel._h, b"final", C.byref(n), C.byref(ms))
-        tot_n += n.value
-        tot_ms += ms.value
-    if tot_n:
-        kern["final"] = {"launches": tot_n, "avg_ms": tot_ms / tot_n}
-    for sel in sels:
-        lib.lg_profile_enable(sel._h, 0)
+    if args.full:
+        # per-kernel device time (HIP events recorded on the launch stream inside the library)
+        tot_n, tot_ms = 0, 0.0
+        for sel in sels:  # dominant kernel: HIP events over the TIMED region
+            n, ms = C.c_int(0), C.c_double(0.0)
+            lib.lg_profile_read(sel._h, b"final", C.byref(n), C.byref(ms))
+            tot_n += n.value
+            tot_ms += ms.value
+        if tot_n:
+            kern["final"] = {"launches": tot_n, "avg_ms": tot_ms / tot_n}
+        for sel in sels:
+            lib.lg_profile_enable(sel._h, 0)
 
     if rank == 0:
         frames = world * B * args.steps
@@ -481,8 +506,11 @@ def main():
                        "frames_per_step_per_gpu": B, "height": H, "width": W, "batches_in_flight": len(sels),
                        "parallelism": f"frames sharded over {world} GPU(s), no collective"},
             "path_hbm_frac": round(fps / world * PATH_BYTES_PER_PX * H * W / (HBM_PEAK_GBS * 1e9), 5),
-            "kernels_ms": {k: round(v["avg_ms"], 4) for k, v in kern.items()},
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res)
+        if args.full:
+            out["kernels_ms"] = {k: round(v["avg_ms"], 4) for k, v in kern.items()}
         if "final" in kern:
             # algorithmic bytes of THIS launch: tiles without a leaf pixel in stencil reach take the constant-store path
             # (no depth read); dense figure (every tile on the full path) = 37.25 B/px
@@ -511,17 +539,19 @@ def main():
                                "bytes_per_launch": round(launch_bytes),
                                "bytes_per_px": round(launch_bytes / px, 3), "dense_bytes_per_px": FINAL_BYTES_PER_PX,
                                "distinct_scenes": n_distinct}
-        try:   # every other kernel of the path: compulsory bytes, average duration, fraction of the HBM peak
-            n_distinct = min(B, N_DISTINCT)
-            wins_k = [sels[0].dt_maxima(i)[2] for i in range(n_distinct)]
-            forms_k = [sels[0].dt_form(i) for i in range(n_distinct)]
-            out["kernel_fracs"] = kernel_fracs({k: v["avg_ms"] for k, v in kern.items()}, masks_np[:n_distinct], wins_k, B, H, W,
-                                               forms=forms_k)
-            out["kernel_fracs"]["dt_form"] = {"searched_frames": sum(f[0] for f in forms_k), "d_out_sweeps_skipped": sum(f[1] for f in forms_k),
-                                              "of": n_distinct, "what": "which form of the distance transform the batch took (decided on "
-                                                                        "the device, lg_bbox_kernel): row search or the two sweeps"}
-        except Exception as e:  # noqa: BLE001
-            out["kernel_fracs"] = {"error": str(e)}
+        if args.full:
+            try:   # every other kernel of the path: compulsory bytes, average duration, fraction of the HBM peak
+                n_distinct = min(B, N_DISTINCT)
+                wins_k = [sels[0].dt_maxima(i)[2] for i in range(n_distinct)]
+                forms_k = [sels[0].dt_form(i) for i in range(n_distinct)]
+                out["kernel_fracs"] = kernel_fracs({k: v["avg_ms"] for k, v in kern.items()}, masks_np[:n_distinct], wins_k, B, H, W,
+                                                   forms=forms_k)
+                out["kernel_fracs"]["dt_form"] = {"searched_frames": sum(f[0] for f in forms_k),
+                                                  "d_out_sweeps_skipped": sum(f[1] for f in forms_k), "of": n_distinct,
+                                                  "what": "which form of the distance transform the batch took (decided on "
+                                                          "the device, lg_bbox_kernel): row search or the two sweeps"}
+            except Exception as e:  # noqa: BLE001
+                out["kernel_fracs"] = {"error": str(e)}
         if "cnn" in kern and not args.no_cnn:
             # MFMA flops actually executed per 9x32x32 patch (2 x MACs): Winograd F(4x4,3x3) = 36 positions x Cout x Cin x
             # tiles (4x fewer than direct), layer 0 on 12 padded input planes; F(2x2,3x3) = 16 positions (2.25x fewer) with

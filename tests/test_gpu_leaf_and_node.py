@@ -596,7 +596,7 @@ def test_bench_two_ranks_one_device(tmp_path):
     steps, batch = 3, 8
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", str(port), os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", str(steps),
-                          "--warmup", "1", "--batch", str(batch), "--height", "270", "--width", "360"],
+                          "--warmup", "1", "--batch", str(batch), "--height", "270", "--width", "360", "--full"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=repo)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -607,6 +607,43 @@ def test_bench_two_ranks_one_device(tmp_path):
     # whole-job value: 2 ranks x batch x steps frames over the (max over ranks) time
     assert res["value"] == pytest.approx(2 * batch * steps / (res["ms_per_step"] * steps * 1e-3), rel=2e-3)
     assert "cpu_baseline" not in res and "roofline" in res      # the CPU leg is rank 0 at N = 1 only
+
+
+def test_bench_plain_run_dumps_its_results(L, tmp_path):
+    """A plain bench.py run reports the headline only (no per-kernel figures or secondary legs), times exactly --steps steps,
+    and --dump-outputs writes the last step's results: the triples select_grasp_points_batch returns for the same seeded
+    frames on a fresh handle."""
+    import json
+    import subprocess
+    import sys
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, H, W, steps = 8, 270, 360, 3
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                          "--batch", str(B), "--height", str(H), "--width", str(W), "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=repo)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == steps and res["unit"] == "frames/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+    assert res["value"] == pytest.approx(B * steps / (res["ms_per_step"] * steps * 1e-3), rel=2e-3)
+    for key in ("kernels_ms", "roofline", "kernel_fracs", "mfma", "cpu_baseline", "configs", "node_sequence", "train_step"):
+        assert key not in res, key
+
+    import bench
+    import synthetic_inputs as SI
+
+    masks, depths, P, _ = bench.make_frames(B, H, W)
+    sel = L.GraspPointSelector("cuda:0", load_model=False)
+    sel.set_camera_params(P)
+    sel.set_cnn_state_dict(SI.cnn_closed_form_params(seed=0))
+    want = sel.select_grasp_points_batch(torch.from_numpy(masks).cuda(), torch.from_numpy(depths).cuda())
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("grasp_xy", "grasp_xyz", "pregrasp_xyz")}
+    assert all(a.dtype == np.float64 and a.shape[0] == B for a in got.values())
+    for b, (xy, xyz, pre) in enumerate(want):
+        assert tuple(got["grasp_xy"][b]) == xy and tuple(got["grasp_xyz"][b]) == xyz
+        assert np.isnan(got["pregrasp_xyz"][b]).all() if pre is None else tuple(got["pregrasp_xyz"][b]) == pre
 
 
 @pytest.mark.parametrize("shape", [(360, 480), (270, 363)])

@@ -5,7 +5,7 @@
 out=${1:-gpurun_out/dt_ab}
 for ma in ${2:-0:2 1:1 1:2 2:2}; do
   mode=${ma%%:*}; algo=${ma##*:}
-  LG_DT_SEARCH=$mode LG_DT_SEARCH_ALGO=$algo python bench.py --steps 10 --warmup 3 --node-steps 0 --train-steps 0 --dense-steps 0 --h2d-steps 0 \
+  LG_DT_SEARCH=$mode LG_DT_SEARCH_ALGO=$algo python bench.py --steps 10 --warmup 3 --full --node-steps 0 --train-steps 0 --dense-steps 0 --h2d-steps 0 \
       --pipelined 0 --cpu-frames 0 --config-steps 5 > ${out}_mode${mode}_algo$algo.json 2> ${out}_mode${mode}_algo$algo.err || exit 1
   python - <<PY
 import json

@@ -3,7 +3,7 @@ set -e
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r04final
 mkdir -p $OUT && cd $GRAFT_REPO_ROOT
 if [ "$1" = "a" ]; then
-  timeout -k 10 500 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+  timeout -k 10 500 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
   bash tools/prof_bench.sh > $OUT/prof_bench.log 2>&1
   cp gpurun_out/prof_bench/kernel_stats.csv $OUT/bench_b256_kernel_stats.csv
   cp gpurun_out/prof_bench/bench_under_rocprof.json $OUT/bench_b256_under_rocprof.json
