@@ -28,6 +28,9 @@
  *                      negative-region helpers (scripts/utils/ml_grasp_optimizer/data_collector.py:91-173,426-490)
  *   lg_leaf_stats      the per-leaf passes of OptimalLeafSelector.select_optimal_leaf
  *                      (scripts/utils/leaf_scorer.py:32-47,66-71,74-138)
+ *   lg_clahe / lg_detect_midrib / lg_midrib_walk   GraspPointSelector.detect_midrib
+ *                      (scripts/utils/grasp_point_selector.py:829-922), which LeafVisualizer calls
+ *                      (scripts/utils/visualizer.py:141)
  */
 #ifndef LEAFGRASP_H
 #define LEAFGRASP_H
@@ -246,6 +249,31 @@ int lg_leaf_select_from_stats(const lg_leaf_stat* stats, int n, const int32_t* e
    outer contour, in (0, pi]), major axis, minor axis, centre x, centre y.  Returns LG_OK and *found = 0
    when the mask is empty.  Synchronises `stream`. */
 int lg_leaf_orientation(lg_handle h, const uint8_t* mask, int H, int W, float* out, int* found, void* stream);
+
+/* ---- GraspPointSelector.detect_midrib (:829-922)
+   lg_clahe          cv2.createCLAHE(clipLimit=clip_limit, tileGridSize=(tiles_x, tiles_y)).apply on B gray frames (:842-843 on its
+                     own; OpenCV clahe.cpp): src, dst u8 [B][H][W] DEVICE.  tiles 1..64 each, H, W >= 2, else LG_ERR_INVALID.
+                     Sizes that do not divide by the tile counts pad BOTH dimensions at the end by tiles - size % tiles
+                     (BORDER_REFLECT_101) for the histograms; clip_limit <= 0: no clipping.  Enqueued on `stream`.
+   lg_detect_midrib  the whole method for B frames: leaf_region = image & mask (:834), COLOR_BGR2GRAY on channel indices 0, 1, 2
+                     (:837; the visualiser hands in RGB, visualizer.py:133), CLAHE(3.0, (8, 8)) of the whole frame (:842-843),
+                     estimate_leaf_orientation (:858, the values lg_leaf_orientation reports, as float32) and the ridge walk
+                     (:864-907).  image u8 [B][H][W][C] DEVICE, C = 3 or 4 (the fourth byte is ignored, as BGR2GRAY ignores
+                     alpha); mask u8 [B][H][W] DEVICE (nonzero = leaf).  out [B][4] HOST: x0, y0, x1, y1 (the first and the last
+                     ridge point); status [B] HOST: 0 found, 1 no contour, 2 int(minor / 6) == 0 (cv2.line asserts thickness > 0:
+                     the reference logs an error and returns None), 3 fewer than two ridge points (None); out is -1 unless 0.
+                     The Otsu threshold, Sobel, Canny and ridge_mask of the reference feed nothing and are not computed.
+                     Synchronises `stream`.
+   lg_midrib_walk    the ridge walk alone on the host (no device, no handle), over a given enhanced image [H][W] and mask [H][W]
+                     (HOST): found = 0 is the reference's None orientation, else orient = angle, major, minor, centre x, centre y
+                     (float32, widened to double as Python does).  out[4] / *status as lg_detect_midrib.  The float64 set-up,
+                     centre-line and sample arithmetic is the code the device walk runs. */
+int lg_clahe(lg_handle h, const uint8_t* src, int B, int H, int W, double clip_limit, int tiles_x, int tiles_y, uint8_t* dst,
+             void* stream);
+int lg_detect_midrib(lg_handle h, const uint8_t* image, int C, const uint8_t* mask, int B, int H, int W, int32_t* out,
+                     int32_t* status, void* stream);
+int lg_midrib_walk(const uint8_t* enhanced, const uint8_t* mask, int H, int W, int found, const float* orient, int32_t* out,
+                   int32_t* status);
 
 /* ---- training-sample harvesting: EnhancedGraspDataCollector (scripts/utils/ml_grasp_optimizer/data_collector.py)
    lg_harvest_patches   _extract_patches :91-173 (+ the rot90 of _generate_augmented_samples :250-266): raw 32x32 windows

@@ -106,6 +106,10 @@ SYMBOLS = {
     "lg_train_sync": (C.c_int, [_VP]),
     "lg_train_grad_buffer": (C.c_int, [_VP, C.POINTER(_FP), C.POINTER(C.c_int64)]),
     "lg_train_apply": (C.c_int, [_VP, C.POINTER(LgTrainHparams), _FP]),
+    "lg_clahe": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _VP, _VP]),
+    "lg_detect_midrib": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), _VP]),
+    "lg_midrib_walk": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 

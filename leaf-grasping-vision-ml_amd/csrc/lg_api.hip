@@ -20,6 +20,7 @@
 #include "lg_cnn.h"
 #include "lg_leaf.h"
 #include "lg_internal.h"
+#include "lg_midrib.h"
 #include "lg_orient.h"
 #include "lg_pool.h"
 
@@ -94,6 +95,7 @@ struct lg_ctx {
     hipStream_t s_cnn = nullptr;   // LG_CNN_CUS=n: the CNN runs on a stream of its own restricted to n CUs (experiment: room for a second
     hipEvent_t ev_cnn0 = nullptr, ev_cnn1 = nullptr;   // batch's memory-bound kernels beside it, bench.py --inflight)
     bool opt_host_orient = false;  // LG_HOST_ORIENT: contour analysis of every frame on the host threads (the round-1 path)
+    LgMidribWs* midrib = nullptr;  // lg_clahe / lg_detect_midrib scratch (lg_midrib.hip)
 };
 
 namespace {
@@ -398,6 +400,7 @@ int lg_destroy(lg_handle h) {
     lg_leaf_free(h->leaf);
     lg_leaf_prof_free(h->leaf_prof);
     lg_orient_free(h->orient);
+    lg_midrib_free(h->midrib);
     if (h->ev_orient) hipEventDestroy(h->ev_orient);
     if (h->ev_side) hipEventDestroy(h->ev_side);
     if (h->ev_search) hipEventDestroy(h->ev_search);
@@ -915,6 +918,107 @@ int lg_leaf_orientation(lg_handle h, const uint8_t* mask, int H, int W, float* o
     LG_HIP(h, hipStreamSynchronize(s));
     *found = lg_host_orientation(h->bits_host, H, W, WW, o);
     for (int i = 0; i < 5; i++) out[i] = *found ? (float)o[i] : NAN;
+    return LG_OK;
+}
+
+int lg_clahe(lg_handle h, const uint8_t* src, int B, int H, int W, double clip_limit, int tiles_x, int tiles_y, uint8_t* dst,
+             void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    LgClaheGeom g;
+    if (!src || !dst || B < 1 || lg_clahe_geom(H, W, clip_limit, tiles_x, tiles_y, &g))
+        return fail(h, LG_ERR_INVALID, "lg_clahe: bad argument (tiles 1..64 each, H, W >= 2)");
+    hipStream_t s = (hipStream_t)stream_;
+    LG_HIP(h, hipSetDevice(h->device));
+    const int ntiles = tiles_x * tiles_y;
+    std::string err;
+    if (lg_midrib_ensure(h->midrib, B, H, W, ntiles, false, false, &err)) return fail(h, LG_ERR_NOMEM, err.c_str());
+    LG_HIP(h, hipMemsetAsync(h->midrib->hist, 0, sizeof(int) * (size_t)B * ntiles * 256, s));
+    {
+        ProfScope ps(h, "clahe_hist", s);
+        lg_launch_clahe_hist(src, nullptr, 0, B, g, h->midrib->hist, s);
+    }
+    {
+        ProfScope ps(h, "clahe_lut", s);
+        lg_launch_clahe_lut(h->midrib->hist, h->midrib->lut, B, g, s);
+    }
+    {
+        ProfScope ps(h, "clahe_apply", s);
+        lg_launch_clahe_apply(src, h->midrib->lut, B, g, dst, s);
+    }
+    LG_HIP(h, hipGetLastError());
+    return LG_OK;
+}
+
+int lg_detect_midrib(lg_handle h, const uint8_t* image, int C, const uint8_t* mask, int B, int H, int W, int32_t* out,
+                     int32_t* status, void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    LgClaheGeom g;
+    if (!image || !mask || !out || !status || B < 1 || (C != 3 && C != 4) || lg_clahe_geom(H, W, 3.0, 8, 8, &g))
+        return fail(h, LG_ERR_INVALID, "lg_detect_midrib: bad argument (C 3 or 4, H, W >= 2)");
+    hipStream_t s = (hipStream_t)stream_;
+    LG_HIP(h, hipSetDevice(h->device));
+    const int ntiles = 64, WW = (W + 63) / 64;
+    std::string err;
+    const bool dev_orient = !h->opt_host_orient && H <= 16384 && W <= 8192;   // lg_leaf_orientation's condition (ensure_ws)
+    if (lg_midrib_ensure(h->midrib, B, H, W, ntiles, true, dev_orient, &err)) return fail(h, LG_ERR_NOMEM, err.c_str());
+    LgMidribWs* m = h->midrib;
+    // CLAHE(clipLimit=3.0, tileGridSize=(8,8)) of the masked gray (:834-843): histograms and LUTs; the enhanced image itself is
+    // evaluated by the walk at its samples only
+    LG_HIP(h, hipMemsetAsync(m->hist, 0, sizeof(int) * (size_t)B * ntiles * 256, s));
+    {
+        ProfScope ps(h, "midrib_hist", s);
+        lg_launch_clahe_hist(image, mask, C, B, g, m->hist, s);
+    }
+    {
+        ProfScope ps(h, "midrib_lut", s);
+        lg_launch_clahe_lut(m->hist, m->lut, B, g, s);
+    }
+    // estimate_leaf_orientation (:858) of every frame, as lg_leaf_orientation computes it
+    {
+        ProfScope ps(h, "midrib_orient", s);
+        lg_launch_pack_bits(mask, m->bits, B, H, W, WW, s);
+        if (m->orient) {
+            lg_launch_bbox(m->bits, m->win, B, H, W, WW, 0, nullptr, s);
+            lg_launch_orient(m->orient, m->bits, m->win, m->fp, 0, B, H, W, WW, s);
+            LG_HIP(h, hipMemcpyAsync(m->orient->h_out, m->orient->out, sizeof(double) * 5 * B, hipMemcpyDeviceToHost, s));
+            LG_HIP(h, hipMemcpyAsync(m->orient->h_status, m->orient->status, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+        }
+    }
+    LG_HIP(h, hipStreamSynchronize(s));
+    bool host_needed = !m->orient;
+    for (int b = 0; b < B && !host_needed; b++) host_needed = m->orient->h_status[b] != 0;
+    if (host_needed) {
+        LG_HIP(h, hipMemcpyAsync(m->bits_host, m->bits, sizeof(unsigned long long) * (size_t)B * H * WW, hipMemcpyDeviceToHost, s));
+        LG_HIP(h, hipStreamSynchronize(s));
+    }
+    for (int b = 0; b < B; b++) {
+        float o[5];
+        int found;
+        if (m->orient && !m->orient->h_status[b]) {
+            const double* d = m->orient->h_out + 5 * (size_t)b;
+            found = !std::isnan(d[0]);
+            for (int i = 0; i < 5; i++) o[i] = (float)d[i];
+        } else {
+            double d[5];
+            found = lg_host_orientation(m->bits_host + (size_t)b * H * WW, H, W, WW, d);
+            for (int i = 0; i < 5; i++) o[i] = (float)d[i];
+        }
+        lg_midrib_setup(found, o, &m->geom_host[b]);
+    }
+    LG_HIP(h, hipMemcpyAsync(m->geom, m->geom_host, sizeof(LgMidribGeom) * B, hipMemcpyHostToDevice, s));
+    {
+        ProfScope ps(h, "midrib_walk", s);
+        lg_launch_midrib_walk(image, C, mask, m->lut, B, g, m->geom, m->res, s);
+    }
+    LG_HIP(h, hipGetLastError());
+    LG_HIP(h, hipMemcpyAsync(m->res_host, m->res, sizeof(int32_t) * 5 * B, hipMemcpyDeviceToHost, s));
+    LG_HIP(h, hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) {
+        for (int i = 0; i < 4; i++) out[4 * (size_t)b + i] = m->res_host[5 * (size_t)b + i];
+        status[b] = m->res_host[5 * (size_t)b + 4];
+    }
     return LG_OK;
 }
 

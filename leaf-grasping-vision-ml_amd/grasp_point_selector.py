@@ -9,6 +9,7 @@ There is no CPU fallback: constructing a selector without a HIP device raises.
 import ctypes as C
 import math
 import os
+import threading
 
 import numpy as np
 import torch
@@ -24,6 +25,9 @@ _RESULT_DTYPE = np.dtype([(n, np.int32 if t is C.c_int else np.float32) for n, t
 assert _RESULT_DTYPE.itemsize == C.sizeof(LgGraspResult)
 
 _VP = C.c_void_p
+
+# status words of lg_detect_midrib
+MIDRIB_FOUND, MIDRIB_NO_CONTOUR, MIDRIB_THIN, MIDRIB_TOO_FEW = 0, 1, 2, 3
 
 
 def _device_index(device):
@@ -370,3 +374,83 @@ class GraspPointSelector:
         except Exception as e:  # noqa: BLE001
             logerr(f"Error in leaf orientation estimation: {str(e)}")
             return None, None, None, None
+
+    # ------------------------------------------------------------------ midrib (:829-922; LeafVisualizer calls it, visualizer.py:141)
+    def _prep_midrib(self, leaf_masks, raw_images):
+        m = leaf_masks if torch.is_tensor(leaf_masks) else torch.from_numpy(np.ascontiguousarray(leaf_masks))
+        im = raw_images if torch.is_tensor(raw_images) else torch.from_numpy(np.ascontiguousarray(raw_images))
+        if im.dtype != torch.uint8:
+            raise ValueError(f"image must be uint8 (got {im.dtype})")
+        if m.dim() != 3 or im.dim() != 4 or tuple(im.shape[:3]) != tuple(m.shape) or im.shape[3] not in (3, 4):
+            raise ValueError(f"mask {tuple(m.shape)} and image {tuple(im.shape)} must be [B,H,W] and [B,H,W,C] with C 3 or 4")
+        m = m.to(self.device).contiguous()
+        if m.dtype == torch.bool:
+            m = m.view(torch.uint8)   # one 0/1 byte per element: reinterpret, no kernel
+        elif m.dtype != torch.uint8:
+            m = (m != 0).to(torch.uint8)
+        return m.contiguous(), im.to(self.device).contiguous()
+
+    def detect_midrib_batch(self, leaf_masks, raw_images):
+        """detect_midrib of B frames in one library call: leaf_masks [B,H,W] (u8 / bool, nonzero = leaf), raw_images [B,H,W,C]
+        uint8 with C 3 or 4, numpy or tensors.  Returns a list of B results, each ((x0, y0), (x1, y1)) of Python ints or None.
+        Bad input raises; the per-frame status words stay in `last_midrib_status`."""
+        m, im = self._prep_midrib(leaf_masks, raw_images)
+        B, H, W = m.shape
+        out, st = (C.c_int32 * (4 * B))(), (C.c_int32 * B)()
+        with torch.cuda.device(self.device):
+            check(self._h, lib.lg_detect_midrib(self._h, im.data_ptr(), int(im.shape[3]), m.data_ptr(), B, H, W, out, st,
+                                                self._stream()), "lg_detect_midrib")
+        res = []
+        for b in range(B):
+            if st[b] == MIDRIB_FOUND:
+                res.append(((out[4 * b], out[4 * b + 1]), (out[4 * b + 2], out[4 * b + 3])))
+            else:
+                if st[b] == MIDRIB_THIN:   # the reference's cv2.line(..., thickness=int(minor/6)) asserts: logged, None
+                    logerr("Error in midrib detection: line thickness int(minor_axis / 6) is 0 (minor axis < 6)")
+                res.append(None)
+        self.last_midrib_status = list(st)
+        return res
+
+    def detect_midrib(self, leaf_mask_np, raw_image):
+        """Reference signature (:829): ((x0, y0), (x1, y1)) of the detected ridge's first and last point, or None.
+        leaf_mask_np: [H,W] u8 / bool (numpy or tensor); raw_image: [H,W,C] uint8 (numpy or device tensor), C 3 or 4, channels
+        weighted by index as cv2's BGR2GRAY does.  Never raises: errors are logged and give None."""
+        try:
+            m = leaf_mask_np if torch.is_tensor(leaf_mask_np) else torch.from_numpy(np.ascontiguousarray(leaf_mask_np))
+            im = raw_image if torch.is_tensor(raw_image) else torch.from_numpy(np.ascontiguousarray(raw_image))
+            if m.dim() != 2 or im.dim() != 3:
+                raise ValueError(f"mask {tuple(m.shape)} and image {tuple(im.shape)} must be [H,W] and [H,W,C]")
+            return self.detect_midrib_batch(m.unsqueeze(0), im.unsqueeze(0))[0]
+        except Exception as e:  # noqa: BLE001
+            logerr(f"Error in midrib detection: {str(e)}")
+            return None
+
+
+_clahe_handles = {}   # device index -> (lock, handle) of leafgrasp_amd.clahe
+_clahe_lock = threading.Lock()
+
+
+def clahe(gray, clip_limit=3.0, tile_grid_size=(8, 8)):
+    """cv2.createCLAHE(clipLimit=clip_limit, tileGridSize=tile_grid_size).apply(gray) on the device (lg_clahe).
+    gray: uint8 tensor [H,W] or [B,H,W] (a CPU tensor or numpy array is moved to the current device); returns a uint8 device
+    tensor of the same shape.  tile_grid_size is (tiles across, tiles down), as OpenCV takes it."""
+    g = gray if torch.is_tensor(gray) else torch.from_numpy(np.ascontiguousarray(gray))
+    if g.dtype != torch.uint8 or g.dim() not in (2, 3):
+        raise ValueError(f"clahe needs a uint8 [H,W] or [B,H,W] image (got {g.dtype} {tuple(g.shape)})")
+    dev = g.device if g.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    idx = _device_index(dev)
+    x = g.to(dev).contiguous()
+    x3 = x.unsqueeze(0) if x.dim() == 2 else x
+    B, H, W = x3.shape
+    out = torch.empty_like(x3)
+    tx, ty = (int(v) for v in tile_grid_size)
+    with _clahe_lock:
+        if idx not in _clahe_handles:
+            h = _VP()
+            check(None, lib.lg_create(idx, C.byref(h)), "lg_create")
+            _clahe_handles[idx] = (threading.Lock(), h)
+        lock, h = _clahe_handles[idx]
+    with lock, torch.cuda.device(dev):
+        check(h, lib.lg_clahe(h, x3.data_ptr(), B, H, W, float(clip_limit), tx, ty, out.data_ptr(),
+                              _VP(torch.cuda.current_stream(dev).cuda_stream)), "lg_clahe")
+    return out[0] if x.dim() == 2 else out
