@@ -48,6 +48,7 @@ struct lg_ctx {
     int capB = 0, capH = 0, capW = 0, capK = 0;
     uint32_t* tmp = nullptr;
     unsigned long long *bits = nullptr, *stem = nullptr, *tilekeys = nullptr;
+    uint8_t* tile_state = nullptr;   // [B][tiles]: which tiles' planes lg_final_kernel wrote (sparse planes, Plan::sparse)
     uint32_t* maxfix = nullptr;
     LgDtBatch* dt_batch = nullptr;   // search-or-sweeps sums of a batch (lg_bbox_kernel)
     uint8_t* mask_ws = nullptr;      // lg_select_grasp_labels: the 0 / 1 mask it derives from the labels (grown on demand)
@@ -184,13 +185,13 @@ hipError_t dev_alloc(T** p, size_t n) {
 
 void free_ws(lg_ctx* h) {
     auto F = [](void* p) { if (p) hipFree(p); };
-    F(h->tmp); F(h->bits); F(h->stem); F(h->tilekeys); F(h->maxfix); F(h->dt_batch); F(h->win); F(h->fp_dev);
+    F(h->tmp); F(h->bits); F(h->stem); F(h->tilekeys); F(h->tile_state); F(h->maxfix); F(h->dt_batch); F(h->win); F(h->fp_dev);
     for (int i = 0; i < LG_NUM_MAPS; i++) { F(h->ws_maps_base[i]); h->ws_maps_base[i] = h->ws_maps[i] = nullptr; }
     F(h->ws_valid); F(h->cand_xy); F(h->cand_n); F(h->cand_info); F(h->patches); F(h->logits);
     auto HF = [](void* p) { if (p) hipHostFree(p); };
     HF(h->fp_host); HF(h->bits_host); HF(h->win_host); HF(h->res_host);
     F(h->res_dev);
-    h->tmp = nullptr; h->bits = h->stem = h->tilekeys = nullptr; h->maxfix = nullptr; h->dt_batch = nullptr; h->win = nullptr; h->fp_dev = nullptr;
+    h->tmp = nullptr; h->bits = h->stem = h->tilekeys = nullptr; h->tile_state = nullptr; h->maxfix = nullptr; h->dt_batch = nullptr; h->win = nullptr; h->fp_dev = nullptr;
     h->ws_valid = nullptr; h->cand_xy = h->cand_n = nullptr; h->cand_info = h->patches = h->logits = nullptr;
     h->fp_host = nullptr; h->bits_host = nullptr; h->win_host = nullptr; h->bits_host_dev = nullptr; h->res_dev = h->res_host = nullptr;
     h->capB = h->capH = h->capW = h->capK = 0;
@@ -209,6 +210,7 @@ int ensure_ws(lg_ctx* h, int B, int H, int W, int K) {
     LG_HIP(h, dev_alloc(&h->bits, words));
     LG_HIP(h, dev_alloc(&h->stem, words));
     LG_HIP(h, dev_alloc(&h->tilekeys, (size_t)nB * tiles));
+    LG_HIP(h, dev_alloc(&h->tile_state, (size_t)nB * tiles));
     LG_HIP(h, dev_alloc(&h->maxfix, (size_t)nB * 2));
     LG_HIP(h, dev_alloc(&h->dt_batch, (size_t)1));
     LG_HIP(h, hipMemset(h->dt_batch, 0, sizeof(LgDtBatch)));
@@ -492,6 +494,9 @@ struct Plan {  // one call's geometry, parameters and plane pointers (absolute, 
     const int16_t* labels = nullptr;   // lg_select_grasp_labels: mask (the handle's workspace) is written from these by the bit-row pass
     float* maps[LG_NUM_MAPS];
     uint8_t* valid;
+    // sparse planes: the caller takes no plane and no validity back (lg_select_grasp*): constant tiles of the workspace planes
+    // stay unwritten, lg_final_kernel records per tile which were written (tile_state), top-k and the gather read that
+    bool sparse = false;
 };
 
 // which form of the row search a batch of n frames takes (LG_DT_SEARCH_ALGO forces one): one level up to 64 frames of 1080p (one
@@ -683,6 +688,8 @@ int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upl
     for (int i = 0; i < LG_NUM_MAPS; i++) a.maps[i] = pl.maps[i] ? pl.maps[i] + off * px : nullptr;
     a.valid = pl.valid ? pl.valid + off * px : nullptr;
     a.tilekeys = h->tilekeys + (size_t)off * pl.tiles_x * pl.tiles_y;
+    a.tile_state = pl.sparse ? h->tile_state + (size_t)off * pl.tiles_x * pl.tiles_y : nullptr;
+    a.sparse = pl.sparse ? 1 : 0;
     a.B = n; a.H = H; a.W = W; a.WW = pl.WW; a.tiles_x = pl.tiles_x; a.tiles_y = pl.tiles_y;
     a.cxi = (int)floor(P.cx); a.cyi = (int)floor(P.cy);
     a.cxf = (float)(P.cx - floor(P.cx)); a.cyf = (float)(P.cy - floor(P.cy)); a.f = (float)P.f;
@@ -818,7 +825,7 @@ int lg_topk_nms(lg_handle h, const float* trad, const uint8_t* valid, int B, int
     int rc = ensure_ws(h, B, H, W, k);
     if (rc) return rc;
     ProfScope ps(h, "topk", s);
-    lg_launch_topk(trad, valid, nullptr, h->tilekeys, false, B, H, W, k, min_dist, out_xy, out_n, nullptr, s);
+    lg_launch_topk(trad, valid, nullptr, h->tilekeys, nullptr, 0.0f, 0.0f, false, B, H, W, k, min_dist, out_xy, out_n, nullptr, s);
     LG_HIP(h, hipGetLastError());
     return LG_OK;
 }
@@ -834,7 +841,7 @@ int lg_gather_patches(lg_handle h, const float* depth, const uint8_t* mask, cons
     hipStream_t s = (hipStream_t)stream_;
     LG_HIP(h, hipSetDevice(h->device));
     ProfScope ps(h, "gather", s);
-    lg_launch_gather(depth, mask, maps, B, H, W, k, xy, n, patches, false, s);
+    lg_launch_gather(depth, mask, maps, nullptr, 0.0f, B, H, W, k, xy, n, patches, false, s);
     LG_HIP(h, hipGetLastError());
     return LG_OK;
 }
@@ -1176,6 +1183,8 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     int rc = make_plan(h, pl, depth, mask, B, H, W, pin, out_maps, out_valid, "lg_select_grasp");
     if (rc) return rc;
     pl.labels = labels;
+    pl.sparse = !out_valid;
+    for (int i = 0; i < LG_NUM_MAPS; i++) pl.sparse = pl.sparse && !pl.maps[i];
     const lg_params& P = pl.P;
     if (P.top_k < 1 || P.top_k > 64) return fail(h, LG_ERR_INVALID, "lg_select_grasp: top_k must be in [1,64]");
     hipStream_t s = (hipStream_t)stream_;
@@ -1228,7 +1237,8 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
                 ProfScope ps(h, "gather", sM);
                 const float* mp[LG_NUM_MAPS];
                 for (int i = 0; i < LG_NUM_MAPS; i++) mp[i] = pl.maps[i] ? pl.maps[i] + off * px : nullptr;
-                lg_launch_gather(depth + off * px, mask + off * px, mp, n, H, W, K, h->cand_xy + (size_t)off * K * 2,
+                lg_launch_gather(depth + off * px, mask + off * px, mp, pl.sparse ? h->tile_state + (size_t)off * tiles : nullptr,
+                                 P.flat_scale, n, H, W, K, h->cand_xy + (size_t)off * K * 2,
                                  h->cand_n + off, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, sM);
             }
             std::string err;
@@ -1288,7 +1298,8 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         {
             ProfScope ps(h, "topk", sT);
             lg_launch_topk(pl.maps[LG_MAP_TRADITIONAL] + off * px, pl.valid + off * px, depth + off * px,
-                           h->tilekeys + (size_t)off * tiles, true, n, H, W, K, P.nms_min_distance,
+                           h->tilekeys + (size_t)off * tiles, pl.sparse ? h->tile_state + (size_t)off * tiles : nullptr,
+                           P.flat_scale, P.w_flat, true, n, H, W, K, P.nms_min_distance,
                            h->cand_xy + (size_t)off * K * 2, h->cand_n + off, h->cand_info + (size_t)off * K * 2, sT);
         }
         if (trace && !piped) hipEventRecord(tev[3], s);   // after top-k

@@ -77,6 +77,8 @@ struct LgFinalArgs {
     float* maps[LG_NUM_MAPS];     // [B][H][W] each (may be null except DISTANCE/TRADITIONAL)
     uint8_t* valid;               // [B][H][W] or null
     unsigned long long* tilekeys; // [B][tiles]
+    uint8_t* tile_state;          // [B][tiles] or null: 1 = the tile's planes and validity were written, 0 = constant tile
+    int sparse;                   // 1: constant tiles write no plane and no validity byte (only their key and state byte)
     int B, H, W, WW, tiles_x, tiles_y;
     int cxi, cyi;      // floor of the optical centre; (x - cxi) is exact, the fraction is subtracted afterwards
     float cxf, cyf, f;  // fractions in [0,1) and the focal length
@@ -125,11 +127,16 @@ void lg_launch_dout_border(const unsigned long long* bits, const LgWin* win, uin
                            hipStream_t s);
 void lg_launch_final(const LgFinalArgs& a, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 void lg_launch_smooth(const float* src, float* dst, int B, int H, int W, int S, const LgGaussTaps& taps, hipStream_t s);
+// tile_state (sparse planes, LgFinalArgs::sparse): [B][tiles] from lg_final_kernel, null when every plane was written.  The
+// planes of a tile with state 0 were not written: top-k and the gather use the constant tile's values instead (flat_scale,
+// w_flat: lg_params), computed with the operations of the final kernel's constant path.
 void lg_launch_topk(const float* trad, const uint8_t* valid, const float* depth, unsigned long long* tilekeys,
+                    const uint8_t* tile_state, float flat_scale, float w_flat,
                     bool keys_ready, int B, int H, int W, int k, int min_dist, int32_t* out_xy, int32_t* out_n,
                     float* out_info, hipStream_t s);
-void lg_launch_gather(const float* depth, const uint8_t* mask, const float* const* maps_dev, int B, int H, int W, int k,
-                      const int32_t* xy, const int32_t* n, float* patches, bool haloed, hipStream_t s);
+void lg_launch_gather(const float* depth, const uint8_t* mask, const float* const* maps_dev, const uint8_t* tile_state,
+                      float flat_scale, int B, int H, int W, int k, const int32_t* xy, const int32_t* n, float* patches,
+                      bool haloed, hipStream_t s);
 
 // The host half of select_grasp_point on the device (lg_finish_kernel): CNN rescoring of the candidates, 3-D point, pre-grasp point
 struct LgFinishArgs {

@@ -97,6 +97,14 @@ __device__ __forceinline__ uint32_t lg_orderable(float s) {  // monotone float -
 // valid_scores = traditional_score * valid_regions (grasp_point_selector.py:451) -- a product, not a selection: a NaN or
 // infinite score (non-finite depth on the leaf) stays NaN where the pixel is not valid, and NaN leads the candidate order
 __device__ __forceinline__ float lg_valid_score(float trad, bool valid) { return trad * (valid ? 1.0f : 0.0f); }
+// flatness of a tile off the leaf: exp(-flat_scale * |grad 0|), evaluated at run time (lg_final_kernel's constant path; top-k and
+// the gather substitute it for tiles that path left unwritten, and must get the same float, whatever flat_scale is).  Its
+// traditional score is w_flat * this, one multiplication.
+__device__ __forceinline__ float lg_const_flat(float flat_scale) {
+    float zero = 0.0f;
+    asm volatile("" : "+v"(zero));
+    return __expf(-flat_scale * __builtin_amdgcn_sqrtf(zero));
+}
 __device__ __forceinline__ int lg_reflect(int v, int n) {  // torch 'reflect' index, clamped for safety
     if (v < 0) v = -v;
     if (v >= n) v = 2 * (n - 1) - v;
@@ -1418,8 +1426,9 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
     int frame = __builtin_amdgcn_readfirstlane((xcd_first + it) / ntile);
     int tile = xcd_first + it - frame * ntile;
     const int step_f = __builtin_amdgcn_readfirstlane(stride / ntile), step_t = stride - step_f * ntile;
-    for (int par = 0; it < it_end;
-         par ^= 1, it += stride, frame += step_f, tile += step_t, frame += (tile >= ntile ? 1 : 0), tile -= (tile >= ntile ? ntile : 0)) {
+    int par = 0;   // s_any slot: flips at every tile that takes the bit-row test (tiles far from the leaf take no barrier)
+    for (; it < it_end;
+         it += stride, frame += step_f, tile += step_t, frame += (tile >= ntile ? 1 : 0), tile -= (tile >= ntile ? ntile : 0)) {
     asm volatile("" : "+s"(ap));
     int t = threadIdx.x;
     asm volatile("" : "+v"(t));
@@ -1445,11 +1454,17 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
     // this kernel writes the plane instead of reading it
     // (win / fp / maxfix were written by earlier kernels and are only read here: constant-address-space loads, i.e. the
     //  scalar cache, instead of a vector load + readfirstlane per value)
-    bool in_win;
+    bool in_win, near_leaf;
     {
         const __attribute__((address_space(4))) LgWin* wp = (const __attribute__((address_space(4))) LgWin*)(ap->win + frame);
         const int wx0 = wp->wx0;
         in_win = tx0 >= wx0 && tx0 < min(W, wx0 + wp->nw * ap->win_wc) && ty0 >= wp->wy0 && ty0 < wp->wy1;
+        // can the bit-row test below meet the mask's bounding box at all?  Its columns are tx0-8 .. tx0+71; its rows
+        // ty0-HALO .. ty0+LG_TH-1+HALO, reflected at the frame border -- at the bottom that reaches up to LG_TH+HALO rows
+        // above ty0 (a last tile row of one pixel), at the top it stays inside the tile
+        const int bx0 = wp->bx0, bx1 = wp->bx1;
+        near_leaf = bx1 >= bx0 && bx0 <= tx0 + LG_TW + 7 && bx1 >= tx0 - 8 && wp->by0 <= ty0 + LG_TH - 1 + HALO &&
+                    wp->by1 >= ty0 - LG_TH - HALO;
     }
     // 4 floats of one plane at pixel offset `off` of this frame (uniform plane base + 32-bit byte offset)
     auto st4 = [&](int mi, unsigned off, int x0, const float* v) {
@@ -1487,46 +1502,57 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
     //      plane and both gradients are 0 and flatness = exp(-5 * 0) = 1 exactly; every other plane is "* mask" = 0,
     //      traditional = w_flat * 1, nothing is valid.  Such tiles never read depth and skip the stencil phases.
     //      Wave 0 looks at the DH x 3 (row, word) pairs and posts the verdict; s_any alternates between two slots so that a
-    //      wave that runs ahead into the next tile cannot overwrite a verdict the others have not read yet.
+    //      wave that runs ahead into the next tested tile cannot overwrite a verdict the others have not read yet.  A tile
+    //      whose test cannot meet the mask's bounding box (near_leaf) is constant without it: no bit-row load, no barrier.
+    //      Sparse mode (a.sparse: the caller takes no plane back; top-k and the gather read tile_state) stores nothing of
+    //      a constant tile but its key and its state byte.
     if (!ap->no_skip) {
-        if (t < 64) {
-            unsigned long long nz = 0;
-            for (int e = t; e < DH * 3; e += 64) {
-                const int er = e / 3, wq = e % 3;                 // extended row, word (left neighbour, own, right neighbour)
-                const int y = lg_reflect(ty0 - HALO + er, H), wi = bx - 1 + wq;
-                if (wi >= 0 && wi < WW) {
-                    unsigned long long v = bits_at(bits, y, wi);
-                    if (wq == 0) v >>= 56;                        // columns tx0-8 .. tx0-1 (halo 4 + reflection slack)
-                    if (wq == 2) v &= 0xffull;                    // columns tx0+64 .. tx0+71
-                    nz |= v;
+        bool any = false;
+        if (near_leaf) {
+            if (t < 64) {
+                unsigned long long nz = 0;
+                for (int e = t; e < DH * 3; e += 64) {
+                    const int er = e / 3, wq = e % 3;                 // extended row, word (left neighbour, own, right neighbour)
+                    const int y = lg_reflect(ty0 - HALO + er, H), wi = bx - 1 + wq;
+                    if (wi >= 0 && wi < WW) {
+                        unsigned long long v = bits_at(bits, y, wi);
+                        if (wq == 0) v >>= 56;                        // columns tx0-8 .. tx0-1 (halo 4 + reflection slack)
+                        if (wq == 2) v &= 0xffull;                    // columns tx0+64 .. tx0+71
+                        nz |= v;
+                    }
                 }
+                const bool anyw = __ballot(nz != 0) != 0ull;
+                if (t == 0) s_any[par] = anyw ? 1 : 0;
             }
-            const bool any = __ballot(nz != 0) != 0ull;
-            if (t == 0) s_any[par] = any ? 1 : 0;
+            lg_lds_barrier();
+            any = s_any[par] != 0;
+            par ^= 1;
         }
-        lg_lds_barrier();
-        if (!s_any[par]) {
-            const float flat1 = __expf(-ap->flat_scale * __builtin_amdgcn_sqrtf(zero));
-            const float tr1 = ap->w_flat * flat1;
-            const float c_flat[4] = {flat1, flat1, flat1, flat1};
-            const float c_trad[4] = {tr1, tr1, tr1, tr1};
-            const float c_zero[4] = {zero, zero, zero, zero};
+        if (!any) {
+            if (!ap->sparse) {
+                const float flat1 = lg_const_flat(ap->flat_scale);
+                const float tr1 = ap->w_flat * flat1;
+                const float c_flat[4] = {flat1, flat1, flat1, flat1};
+                const float c_trad[4] = {tr1, tr1, tr1, tr1};
+                const float c_zero[4] = {zero, zero, zero, zero};
 #pragma unroll
-            for (int rr = 0; rr < RPT; rr++) {
-                const int y = ty0 + tyi + 16 * rr, x0 = tx0 + 4 * txi;
-                if (y < H && x0 < W) {
-                    const unsigned off = (unsigned)(y * W + x0);
-                    st4(LG_MAP_SDF, off, x0, c_zero); st4(LG_MAP_APPROACH, off, x0, c_zero); st4(LG_MAP_FLATNESS, off, x0, c_flat);
-                    st4(LG_MAP_ISOLATION, off, x0, c_zero); st4(LG_MAP_ACCESS, off, x0, c_zero); st4(LG_MAP_STEM, off, x0, c_zero);
-                    st4(LG_MAP_TRADITIONAL, off, x0, c_trad);
-                    if (!in_win) st4(LG_MAP_DISTANCE, off, x0, c_zero);
-                    st_valid(off, x0, 0u);
+                for (int rr = 0; rr < RPT; rr++) {
+                    const int y = ty0 + tyi + 16 * rr, x0 = tx0 + 4 * txi;
+                    if (y < H && x0 < W) {
+                        const unsigned off = (unsigned)(y * W + x0);
+                        st4(LG_MAP_SDF, off, x0, c_zero); st4(LG_MAP_APPROACH, off, x0, c_zero); st4(LG_MAP_FLATNESS, off, x0, c_flat);
+                        st4(LG_MAP_ISOLATION, off, x0, c_zero); st4(LG_MAP_ACCESS, off, x0, c_zero); st4(LG_MAP_STEM, off, x0, c_zero);
+                        st4(LG_MAP_TRADITIONAL, off, x0, c_trad);
+                        if (!in_win) st4(LG_MAP_DISTANCE, off, x0, c_zero);
+                        st_valid(off, x0, 0u);
+                    }
                 }
             }
             if (t == 0) {   // arg-max key of a tile without valid pixels: score 0, largest flat index (top-k tie rule)
                 const int ymax = min(ty0 + LG_TH, H) - 1, xmax = min(tx0 + LG_TW, W) - 1;
                 ap->tilekeys[(size_t)frame * ntile + tile] =
                     ((unsigned long long)lg_orderable(0.0f) << 32) | (uint32_t)(ymax * W + xmax);
+                if (ap->tile_state) ap->tile_state[(size_t)frame * ntile + tile] = 0;
             }
             continue;
         }
@@ -1790,14 +1816,28 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
         k = s_key[2] > k ? s_key[2] : k;
         k = s_key[3] > k ? s_key[3] : k;
         ap->tilekeys[(size_t)frame * ntile + tile] = k;
+        if (ap->tile_state) ap->tile_state[(size_t)frame * ntile + tile] = 1;
     }
     }   // tile walk
 }
 
+// Launch form of sparse mode (LgFinalArgs::sparse), where nearly every workgroup of the one-per-tile form has only a key and a
+// state byte to store: consecutive tiles per workgroup, or resident workgroups per CU (0 = off; LG_FINAL_TPW / LG_FINAL_PERSIST
+// override).  Benchmark headline, 256 frames of 1080p, one box: one tile per workgroup 0.70 ms; 4 / 8 / 16 / 32 / 64 / 128 tiles
+// per workgroup 0.48 / 0.45 / 0.44-0.46 / 0.44-0.45 / 0.51 / 0.63 ms; resident walk with 8 / 2 workgroups per CU 0.53 / 0.96 ms.
+// One tile per workgroup launches 518 k nearly empty workgroups; past 32 tiles the leaf tiles' stencil work collects on too
+// few workgroups.
+#ifndef LG_FINAL_SPARSE_TPW
+#define LG_FINAL_SPARSE_TPW 16
+#endif
+#ifndef LG_FINAL_SPARSE_PERSIST
+#define LG_FINAL_SPARSE_PERSIST 0
+#endif
 void lg_launch_final(const LgFinalArgs& a_in, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
     long long total = (long long)a_in.tiles_x * a_in.tiles_y * a_in.B;   // < 2^31: tiles_x * tiles_y <= 8192 (make_plan), B is an int count of frames that fit in memory
-    // Launch form.  One workgroup per tile by default: on real frames most tiles take the constant path and the dispatcher's
-    // own load balancing beats a fixed stride (2.71 vs 3.12 ms per 256 frames).  LG_FINAL_PERSIST=n (or a.persist): n resident
+    // Launch form.  Dense mode: one workgroup per tile by default (sparse mode: LG_FINAL_SPARSE_TPW above): on real frames
+    // most tiles take the constant path and the dispatcher's own load balancing beats a fixed stride (2.71 vs 3.12 ms per 256
+    // frames).  LG_FINAL_PERSIST=n (or a.persist): n resident
     // workgroups per CU (a multiple of 8 workgroups, so that blockIdx % 8 stays the XCD) walk the tiles.  With every tile on
     // the stencil path the walk measured 5 % faster on three boxes (2.10 vs 2.21 ms per 128 frames; its arithmetic alone 1.14
     // vs 1.42 ms) and 25 % SLOWER on a fourth, faster one (2.28-2.33 vs 1.80-1.87 ms): a wave's loads for its next tile queue
@@ -1809,14 +1849,14 @@ void lg_launch_final(const LgFinalArgs& a_in, hipStream_t s, hipEvent_t ev_start
         hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
         return n;
     }();
-    const int per_cu = persist_env >= 0 ? persist_env : (a_in.persist ? LG_FINAL_WPE : 0);
+    const int per_cu = persist_env >= 0 ? persist_env : (a_in.persist ? LG_FINAL_WPE : a_in.sparse ? LG_FINAL_SPARSE_PERSIST : 0);
     const int resident = per_cu > 0 ? std::max(8, cus * per_cu / 8 * 8) : 0;
     // LG_FINAL_TPW=n: n consecutive tiles per workgroup (experiment: 2 / 4 / 8 change the benchmark launch by -1 / +1 / +3 %,
     // the dense launch within the noise: the workgroup launch rate is not what limits either)
-    static const int tpw_env = getenv("LG_FINAL_TPW") ? atoi(getenv("LG_FINAL_TPW")) : 0;
+    static const int tpw_env = getenv("LG_FINAL_TPW") ? atoi(getenv("LG_FINAL_TPW")) : -1;
     LgFinalArgs a = a_in;
     const bool walk = resident && total > 2ll * resident;
-    a.tpw = walk ? 0 : std::max(0, tpw_env);
+    a.tpw = walk ? 0 : std::max(0, tpw_env >= 0 ? tpw_env : a.sparse ? LG_FINAL_SPARSE_TPW : 0);
     const long long per_xcd = (total + 7) / 8;
     const unsigned grid = (unsigned)(walk ? resident : a.tpw > 1 ? 8 * ((per_xcd + a.tpw - 1) / a.tpw) : total);
     if (a.tpw == 1) a.tpw = 0;
@@ -2029,17 +2069,22 @@ __global__ __launch_bounds__(256) void lg_tilekeys_kernel(const float* __restric
 // (2d+1)^2 window meets no earlier window, i.e. iff it is > 2d away from every accepted point).
 // One 1024-thread workgroup per frame; per-tile maxima live in LDS and only the tiles touched by a new suppression
 // window (<= 8 of 64x16 pixels for the reference's 41x41 window; any number for larger min_distance) are recomputed.
+// tile_state (sparse planes): a tile with state 0 has no trad / valid written; its pixels are read as the constant tile's
+// (trad = w_flat * lg_const_flat(flat_scale), valid = 0) -- the same keys, tie rule included, as the written planes give.
 #define LG_TOPK_T 1024
 #define LG_MAX_TILES 8192
 #define LG_MAX_K 64
 __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restrict__ trad,
                                                             const uint8_t* __restrict__ valid,
                                                             const float* __restrict__ depth,
-                                                            const unsigned long long* __restrict__ tilekeys, int H,
+                                                            const unsigned long long* __restrict__ tilekeys,
+                                                            const uint8_t* __restrict__ tile_state, float flat_scale,
+                                                            float w_flat, int H,
                                                             int W, int tiles_x, int tiles_y, int k, int md,
                                                             int32_t* __restrict__ out_xy, int32_t* __restrict__ out_n,
                                                             float* __restrict__ out_info) {
     __shared__ unsigned long long s_keys[LG_MAX_TILES];
+    __shared__ uint8_t s_state[LG_MAX_TILES];   // 1: the tile's planes were written (every tile when tile_state is null)
     __shared__ unsigned long long s_best;
     __shared__ int s_cx[LG_MAX_K], s_cy[LG_MAX_K];
     const int frame = blockIdx.x;
@@ -2048,7 +2093,11 @@ __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restr
     const size_t fo = (size_t)frame * H * W;
     const int sup = 2 * md;
     const float inv_w = __frcp_rn((float)W);
-    for (int i = t; i < ntile; i += LG_TOPK_T) s_keys[i] = tilekeys[(size_t)frame * ntile + i];
+    for (int i = t; i < ntile; i += LG_TOPK_T) {
+        s_keys[i] = tilekeys[(size_t)frame * ntile + i];
+        s_state[i] = tile_state ? tile_state[(size_t)frame * ntile + i] : 1;
+    }
+    const float trad1 = w_flat * lg_const_flat(flat_scale);   // traditional score of a constant tile
     if (t == 0) s_best = 0;
     __syncthreads();
     int n = 0;
@@ -2108,10 +2157,15 @@ __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restr
                 if (y < H && x0 < W) {
                     const size_t o = fo + (size_t)y * W + x0;
                     const bool two = x0 + 4 < W;             // W % 4 == 0: groups of four pixels are inside or outside as a whole
-                    const float4 s0 = *reinterpret_cast<const float4*>(trad + o);
-                    const float4 s1 = two ? *reinterpret_cast<const float4*>(trad + o + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    const uint32_t v0 = *reinterpret_cast<const uint32_t*>(valid + o);
-                    const uint32_t v1 = two ? *reinterpret_cast<const uint32_t*>(valid + o + 4) : 0u;
+                    const bool mat = s_state[tile] != 0;     // (uniform over the tile's two waves)
+                    float4 s0 = make_float4(trad1, trad1, trad1, trad1), s1 = s0;
+                    uint32_t v0 = 0u, v1 = 0u;
+                    if (mat) {
+                        s0 = *reinterpret_cast<const float4*>(trad + o);
+                        s1 = two ? *reinterpret_cast<const float4*>(trad + o + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        v0 = *reinterpret_cast<const uint32_t*>(valid + o);
+                        v1 = two ? *reinterpret_cast<const uint32_t*>(valid + o + 4) : 0u;
+                    }
                     const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
                     // rows: which of the relevant picks reach this row at all (the column test is then per pixel)
                     unsigned long long rowrel = 0;
@@ -2166,8 +2220,9 @@ __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restr
             float tt_[GRP];
 #pragma unroll
             for (int g = 0; g < GRP; g++) {
-                vv_[g] = __builtin_nontemporal_load(valid + fo + off_[g]);
-                tt_[g] = __builtin_nontemporal_load(trad + fo + off_[g]);
+                const bool mat = s_state[tile_[g]] != 0;
+                vv_[g] = mat ? __builtin_nontemporal_load(valid + fo + off_[g]) : (uint8_t)0;
+                tt_[g] = mat ? __builtin_nontemporal_load(trad + fo + off_[g]) : trad1;
             }
 #pragma unroll
             for (int g = 0; g < GRP; g++) sc_[g] = idx_[g] >= 0 ? lg_valid_score(tt_[g], vv_[g] != 0) : 0.0f;
@@ -2197,20 +2252,23 @@ __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restr
     // every round would sit on the critical path of the next arg-max)
     if (out_info && t < n) {
         const size_t o = fo + (size_t)s_cy[t] * W + s_cx[t];
-        out_info[((size_t)frame * k + t) * 2 + 0] = trad[o];
+        const int tile = (s_cy[t] / LG_TH) * tiles_x + s_cx[t] / LG_TW;
+        out_info[((size_t)frame * k + t) * 2 + 0] = s_state[tile] ? trad[o] : trad1;
         out_info[((size_t)frame * k + t) * 2 + 1] = depth ? depth[o] : 0.0f;
     }
 }
 
 void lg_launch_topk(const float* trad, const uint8_t* valid, const float* depth, unsigned long long* tilekeys,
+                    const uint8_t* tile_state, float flat_scale, float w_flat,
                     bool keys_ready, int B, int H, int W, int k, int min_dist, int32_t* out_xy, int32_t* out_n,
                     float* out_info, hipStream_t s) {
     int tiles_x = (W + LG_TW - 1) / LG_TW, tiles_y = (H + LG_TH - 1) / LG_TH;
-    if (!keys_ready)
+    if (!keys_ready)   // (keys from the planes themselves: every plane written)
         hipLaunchKernelGGL(lg_tilekeys_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, s, trad, valid, tilekeys, H, W,
                            tiles_x, tiles_y);
-    hipLaunchKernelGGL(lg_topk_kernel, dim3(B), dim3(LG_TOPK_T), 0, s, trad, valid, depth, tilekeys, H, W, tiles_x,
-                       tiles_y, k, min_dist, out_xy, out_n, out_info);
+    hipLaunchKernelGGL(lg_topk_kernel, dim3(B), dim3(LG_TOPK_T), 0, s, trad, valid, depth, tilekeys,
+                       keys_ready ? tile_state : nullptr, flat_scale, w_flat, H, W, tiles_x, tiles_y, k, min_dist, out_xy,
+                       out_n, out_info);
 }
 
 // ============================================================================ 9-channel patch gather
@@ -2220,12 +2278,17 @@ void lg_launch_topk(const float* trad, const uint8_t* valid, const float* depth,
 struct LgGatherMaps { const float* p[7]; };
 // HALO: write the interior of the first 9 of the 12 haloed planes [12][34][36] (pixel (y,x) at [y+1][x+1]; the CNN's staging layout, lg_cnn.hip;
 // the halo itself is zeroed once when the workspace is allocated) instead of dense [9][32][32].
+// tile_state (sparse planes): on a tile with state 0 the seven planes were not written; its pixels take the constant tile's
+// values (flatness lg_const_flat(flat_scale), every other plane 0 -- distance too: the sweeps write 0 at a pixel off the leaf,
+// and the final kernel's constant path writes 0 outside their window), so the patches are those of the written planes.
 template <bool HALO>
 __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict__ depth,
-                                                        const uint8_t* __restrict__ mask, LgGatherMaps maps, int H,
+                                                        const uint8_t* __restrict__ mask, LgGatherMaps maps,
+                                                        const uint8_t* __restrict__ tile_state, float flat_scale, int H,
                                                         int W, int k, const int32_t* __restrict__ xy,
                                                         const int32_t* __restrict__ n, float* __restrict__ patches) {
     __shared__ float s_mn[4], s_mx[4];
+    __shared__ int s_mat[3][2];   // state of the <= 3 x 2 tiles under the window (rows ty_lo.., columns tx_lo..)
     constexpr int PL = HALO ? 34 * 36 : 1024, RP = HALO ? 36 : 32, O0 = HALO ? 37 : 0;
     const int ci = blockIdx.x, frame = blockIdx.y;
     const int t = threadIdx.x;
@@ -2237,17 +2300,35 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
     }
     const int px = xy[((size_t)frame * k + ci) * 2], py = xy[((size_t)frame * k + ci) * 2 + 1];
     const size_t fo = (size_t)frame * H * W;
+    // the clamped window spans rows clamp(py-16) .. clamp(py+15) (32 rows: at most 3 tile rows) and 32 columns (at most 2)
+    const int ty_lo = min(max(py - 16, 0), H - 1) / LG_TH, tx_lo = min(max(px - 16, 0), W - 1) / LG_TW;
+    if (t < 6) {
+        const int tiles_x = (W + LG_TW - 1) / LG_TW, tiles_y = (H + LG_TH - 1) / LG_TH;
+        const int ty = ty_lo + t / 2, tx = tx_lo + t % 2;
+        s_mat[t / 2][t % 2] = (!tile_state || ty >= tiles_y || tx >= tiles_x) ? 1
+                              : tile_state[(size_t)frame * tiles_x * tiles_y + ty * tiles_x + tx];
+    }
+    __syncthreads();
+    bool mat[4];
+    size_t o_[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        int i = t + 256 * q;
+        int yy = py - 16 + (i >> 5), xx = px - 16 + (i & 31);
+        yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);
+        xx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
+        o_[q] = fo + (size_t)yy * W + xx;
+        mat[q] = s_mat[yy / LG_TH - ty_lo][xx / LG_TW - tx_lo] != 0;
+    }
+    const float flat1 = lg_const_flat(flat_scale);
     for (int c = 0; c < 9; c++) {
         float v[4];
         float mn = INFINITY, mx = -INFINITY;
+        const float cst = (c == 2 + LG_MAP_FLATNESS) ? flat1 : 0.0f;   // the constant tile's value of plane c - 2
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            int i = t + 256 * q;
-            int yy = py - 16 + (i >> 5), xx = px - 16 + (i & 31);
-            yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);
-            xx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
-            size_t o = fo + (size_t)yy * W + xx;
-            float val = (c == 0) ? depth[o] : (c == 1) ? (mask[o] ? 1.0f : 0.0f) : maps.p[c - 2][o];
+            const size_t o = o_[q];
+            float val = (c == 0) ? depth[o] : (c == 1) ? (mask[o] ? 1.0f : 0.0f) : mat[q] ? maps.p[c - 2][o] : cst;
             v[q] = val;
             mn = fminf(mn, val);
             mx = fmaxf(mx, val);
@@ -2286,12 +2367,17 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
     }
 }
 
-void lg_launch_gather(const float* depth, const uint8_t* mask, const float* const* maps_host, int B, int H, int W, int k,
-                      const int32_t* xy, const int32_t* n, float* patches, bool haloed, hipStream_t s) {
+void lg_launch_gather(const float* depth, const uint8_t* mask, const float* const* maps_host, const uint8_t* tile_state,
+                      float flat_scale, int B, int H, int W, int k, const int32_t* xy, const int32_t* n, float* patches,
+                      bool haloed, hipStream_t s) {
     LgGatherMaps gm;
     for (int i = 0; i < 7; i++) gm.p[i] = maps_host[i];
-    if (haloed) hipLaunchKernelGGL(lg_gather_kernel<true>, dim3(k, B), dim3(256), 0, s, depth, mask, gm, H, W, k, xy, n, patches);
-    else hipLaunchKernelGGL(lg_gather_kernel<false>, dim3(k, B), dim3(256), 0, s, depth, mask, gm, H, W, k, xy, n, patches);
+    if (haloed)
+        hipLaunchKernelGGL(lg_gather_kernel<true>, dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W, k,
+                           xy, n, patches);
+    else
+        hipLaunchKernelGGL(lg_gather_kernel<false>, dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W,
+                           k, xy, n, patches);
 }
 
 // ============================================================================ training-sample harvesting
