@@ -24,6 +24,7 @@
  *   lg_cnn_load / lg_cnn_forward   GraspPointCNN.forward (eval)
  *                      (scripts/utils/ml_grasp_optimizer/model.py:101-128), load_ml_model :43-57
  *   lg_select_grasp    GraspPointSelector.select_grasp_point :184-253 (whole path, batched)
+ *   lg_select_grasp_candidates   the per-candidate log lines of its selection loop :210-236, every candidate ranked
  *   lg_harvest_patches / lg_negative_masks / lg_leaf_contour   EnhancedGraspDataCollector's patch extraction and
  *                      negative-region helpers (scripts/utils/ml_grasp_optimizer/data_collector.py:91-173,426-490)
  *   lg_leaf_stats      the per-leaf passes of OptimalLeafSelector.select_optimal_leaf
@@ -135,6 +136,24 @@ typedef struct lg_grasp_result {
     float   theta;            /* leaf orientation (rad), NaN if none */
 } lg_grasp_result;
 
+/* One candidate of lg_select_grasp_candidates (HOST memory), in rank order: the reference's selection
+   (:205-236) applied again to the candidates left after each pick.  17 four-byte fields, 68 bytes. */
+typedef struct lg_grasp_candidate {
+    int32_t index;            /* position in the candidate list (_get_candidate_points :447-482); -1 = unused row (all else 0) */
+    int32_t x, y;             /* the candidate pixel */
+    float   traditional;      /* traditional_score there (:205, :213) */
+    float   ml_score;         /* get_ml_score (:133-136)          NaN when not scored */
+    float   ml_confidence;    /* 1 - |ml - 0.5| * 2 (:222)        NaN when not scored */
+    float   combined;         /* (1 - w) trad + w ml (:223-226)   NaN when not scored */
+    int32_t scored;           /* the reference computes a combined score for it (CNN loaded, n > 1, not a border
+                                 candidate of a torch.bool mask: SURVEY App. B.7) */
+    float   pick_score;       /* the score that decided this rank (rank 0: lg_grasp_result.best_score) */
+    int32_t by_ml;            /* a combined score decided it (rank 0: lg_grasp_result.ml_used) */
+    float   X, Y, Z;          /* get_3d_grasp_point (:152-180) */
+    int32_t has_pre;          /* pre-grasp point present */
+    float   pX, pY, pZ;       /* calculate_pre_grasp_point (:754-819) */
+} lg_grasp_candidate;
+
 /* Per-leaf statistics of lg_leaf_stats (HOST memory), one per label id present, ascending id. */
 typedef struct lg_leaf_stat {
     int32_t id;
@@ -208,6 +227,22 @@ int lg_select_grasp(lg_handle h, const float* depth, const uint8_t* mask, int B,
 int lg_select_grasp_labels(lg_handle h, const float* depth, const int16_t* labels, const int32_t* leaf_ids, int B, int H, int W,
                            const lg_params* p, float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid,
                            lg_grasp_result* results, void* stream);
+
+/* Every candidate of every frame, ranked: the selection loop of select_grasp_point (:205-236, which logs each candidate's
+   scores) applied again to what is left after each pick, so rank 1 is the grasp the reference would choose if rank 0 were
+   taken away.  results: as lg_select_grasp / lg_select_grasp_labels fill them.  cands: HOST array of B * p->top_k rows,
+   frame after frame, in rank order; rows past n_candidates have index = -1 and zeros elsewhere.  No plane outputs.  The
+   rows are computed on the device in double precision (the ranking compares the unrounded combined scores). */
+int lg_select_grasp_candidates(lg_handle h, const float* depth, const uint8_t* mask, int B, int H, int W, const lg_params* p,
+                               lg_grasp_result* results, lg_grasp_candidate* cands, void* stream);
+int lg_select_grasp_candidates_labels(lg_handle h, const float* depth, const int16_t* labels, const int32_t* leaf_ids, int B,
+                                      int H, int W, const lg_params* p, lg_grasp_result* results, lg_grasp_candidate* cands,
+                                      void* stream);
+/* The ranking alone on the host (no device, no handle) for ONE frame of n <= 64 candidates: trad[n], comb[n], scored[n] as
+   the device computes them (comb is read only where scored), rescoring = a CNN is loaded and n > 1.  order[n]: candidate
+   indices in rank order; pick[n], by_ml[n]: the deciding score and whether a combined score decided.  The device runs this code. */
+int lg_rank_grasp_candidates(const double* trad, const double* comb, const int32_t* scored, int n, int rescoring,
+                             int32_t* order, double* pick, int32_t* by_ml);
 
 /* The node's result message of every frame (leaf_grasp_node_v3.py:170-176: "x,y,X,Y,Z[,pX,pY,pZ]", each number as Python's
    str() prints it -- the shortest decimal string of the float32 value as a double), '\n'-terminated, one line per frame in

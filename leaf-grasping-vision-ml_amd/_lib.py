@@ -42,6 +42,14 @@ class LgGraspResult(C.Structure):
                 ("best_score", C.c_float), ("theta", C.c_float)]
 
 
+class LgGraspCandidate(C.Structure):
+    """lg_grasp_candidate: one ranked candidate of lg_select_grasp_candidates (17 four-byte fields)."""
+    _fields_ = [("index", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("traditional", C.c_float), ("ml_score", C.c_float),
+                ("ml_confidence", C.c_float), ("combined", C.c_float), ("scored", C.c_int32), ("pick_score", C.c_float),
+                ("by_ml", C.c_int32), ("X", C.c_float), ("Y", C.c_float), ("Z", C.c_float), ("has_pre", C.c_int32),
+                ("pX", C.c_float), ("pY", C.c_float), ("pZ", C.c_float)]
+
+
 class LgTrainHparams(C.Structure):
     """lg_train_hparams; defaults = scripts/train_model.py:221-222,256."""
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
@@ -77,6 +85,11 @@ SYMBOLS = {
                                   C.POINTER(_VP * LG_NUM_MAPS), _VP, C.POINTER(LgGraspResult), _VP]),
     "lg_select_grasp_labels": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(LgParams),
                                          C.POINTER(_VP * LG_NUM_MAPS), _VP, C.POINTER(LgGraspResult), _VP]),
+    "lg_select_grasp_candidates": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(LgParams),
+                                             C.POINTER(LgGraspResult), C.POINTER(LgGraspCandidate), _VP]),
+    "lg_select_grasp_candidates_labels": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
+                                                    C.POINTER(LgParams), C.POINTER(LgGraspResult), C.POINTER(LgGraspCandidate), _VP]),
+    "lg_rank_grasp_candidates": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
     "lg_leaf_stats": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                 C.POINTER(LgLeafStat), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32), _VP]),
     "lg_leaf_stats_batch": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,

@@ -69,6 +69,11 @@ struct lg_ctx {
     float *cand_info = nullptr, *patches = nullptr, *logits = nullptr;
     lg_grasp_result* res_dev = nullptr;       // [B] result rows written by lg_finish_kernel
     lg_grasp_result* res_host = nullptr;      // pinned copy
+    // lg_select_grasp_candidates*: [cand_rows_cap] rows of lg_candidates_kernel and their pinned copy, allocated on the first such
+    // call (handles that never ask for candidates do not grow)
+    lg_grasp_candidate* cand_rows_dev = nullptr;
+    lg_grasp_candidate* cand_rows_host = nullptr;
+    size_t cand_rows_cap = 0;
     LgCnn cnn;
     LgLeafWs* leaf = nullptr;
     LgLeafProf* leaf_prof = nullptr;   // per-kernel times of the leaf stage (lg_profile_enable)
@@ -398,6 +403,8 @@ int lg_destroy(lg_handle h) {
     if (h->mask_ws) hipFree(h->mask_ws);
     if (h->ids_dev) hipFree(h->ids_dev);
     if (h->ids_host) hipHostFree(h->ids_host);
+    if (h->cand_rows_dev) hipFree(h->cand_rows_dev);
+    if (h->cand_rows_host) hipHostFree(h->cand_rows_host);
     lg_cnn_free(&h->cnn);
     lg_leaf_free(h->leaf);
     lg_leaf_prof_free(h->leaf_prof);
@@ -1135,13 +1142,16 @@ int lg_cnn_forward(lg_handle h, const float* patches, int N, float* logits, void
 
 static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* mask, const int16_t* labels, int B, int H, int W,
                                 const lg_params* pin, float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid,
-                                lg_grasp_result* results, void* stream_);
+                                lg_grasp_result* results, lg_grasp_candidate* cands, void* stream_);
+static int lg_select_grasp_labels_impl(lg_handle h, const float* depth, const int16_t* labels, const int32_t* leaf_ids, int B,
+                                       int H, int W, const lg_params* pin, float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid,
+                                       lg_grasp_result* results, lg_grasp_candidate* cands, void* stream_);
 
 int lg_select_grasp(lg_handle h, const float* depth, const uint8_t* mask, int B, int H, int W, const lg_params* pin,
                     float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid, lg_grasp_result* results, void* stream_) {
     if (!h) return LG_ERR_INVALID;
     LG_ENTER(h);
-    return lg_select_grasp_impl(h, depth, mask, nullptr, B, H, W, pin, out_maps, out_valid, results, stream_);
+    return lg_select_grasp_impl(h, depth, mask, nullptr, B, H, W, pin, out_maps, out_valid, results, nullptr, stream_);
 }
 
 // lg_select_grasp on mask[b] = (labels[b] == leaf_ids[b]): the node's `optimal_mask = mask_tensor == optimal_leaf_id` followed by
@@ -1151,6 +1161,39 @@ int lg_select_grasp_labels(lg_handle h, const float* depth, const int16_t* label
                            void* stream_) {
     if (!h) return LG_ERR_INVALID;
     LG_ENTER(h);
+    return lg_select_grasp_labels_impl(h, depth, labels, leaf_ids, B, H, W, pin, out_maps, out_valid, results, nullptr, stream_);
+}
+
+// Every candidate ranked (lg_candidates_kernel after lg_finish_kernel): the sparse-plane path, no plane outputs
+int lg_select_grasp_candidates(lg_handle h, const float* depth, const uint8_t* mask, int B, int H, int W, const lg_params* pin,
+                               lg_grasp_result* results, lg_grasp_candidate* cands, void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (!cands) return fail(h, LG_ERR_INVALID, "lg_select_grasp_candidates: cands is null");
+    return lg_select_grasp_impl(h, depth, mask, nullptr, B, H, W, pin, nullptr, nullptr, results, cands, stream_);
+}
+
+int lg_select_grasp_candidates_labels(lg_handle h, const float* depth, const int16_t* labels, const int32_t* leaf_ids, int B,
+                                      int H, int W, const lg_params* pin, lg_grasp_result* results, lg_grasp_candidate* cands,
+                                      void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (!cands) return fail(h, LG_ERR_INVALID, "lg_select_grasp_candidates_labels: cands is null");
+    return lg_select_grasp_labels_impl(h, depth, labels, leaf_ids, B, H, W, pin, nullptr, nullptr, results, cands, stream_);
+}
+
+int lg_rank_grasp_candidates(const double* trad, const double* comb, const int32_t* scored, int n, int rescoring, int32_t* order,
+                             double* pick, int32_t* by_ml) {
+    if (n < 0 || n > 64) return LG_ERR_INVALID;
+    if (n == 0) return LG_OK;
+    if (!trad || !comb || !scored || !order || !pick || !by_ml) return LG_ERR_INVALID;
+    lg_rank_candidates(trad, comb, scored, n, rescoring, order, pick, by_ml);
+    return LG_OK;
+}
+
+static int lg_select_grasp_labels_impl(lg_handle h, const float* depth, const int16_t* labels, const int32_t* leaf_ids, int B,
+                                       int H, int W, const lg_params* pin, float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid,
+                                       lg_grasp_result* results, lg_grasp_candidate* cands, void* stream_) {
     if (!labels || !leaf_ids || B < 1 || H < 1 || W < 1) return fail(h, LG_ERR_INVALID, "lg_select_grasp_labels: null or empty input");
     LG_HIP(h, hipSetDevice(h->device));
     const size_t need = (size_t)B * H * W;
@@ -1172,12 +1215,12 @@ int lg_select_grasp_labels(lg_handle h, const float* depth, const int16_t* label
     }
     memcpy(h->ids_host, leaf_ids, sizeof(int32_t) * B);   // (the previous call on this handle has been synchronised: one call in flight)
     LG_HIP(h, hipMemcpyAsync(h->ids_dev, h->ids_host, sizeof(int32_t) * B, hipMemcpyHostToDevice, (hipStream_t)stream_));
-    return lg_select_grasp_impl(h, depth, h->mask_ws, labels, B, H, W, pin, out_maps, out_valid, results, stream_);
+    return lg_select_grasp_impl(h, depth, h->mask_ws, labels, B, H, W, pin, out_maps, out_valid, results, cands, stream_);
 }
 
 static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* mask, const int16_t* labels, int B, int H, int W,
                                 const lg_params* pin, float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid,
-                                lg_grasp_result* results, void* stream_) {
+                                lg_grasp_result* results, lg_grasp_candidate* cands, void* stream_) {
     if (!results) return fail(h, LG_ERR_INVALID, "lg_select_grasp: results is null");
     Plan pl;
     int rc = make_plan(h, pl, depth, mask, B, H, W, pin, out_maps, out_valid, "lg_select_grasp");
@@ -1191,6 +1234,18 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     LG_HIP(h, hipSetDevice(h->device));
     rc = ensure_ws(h, B, H, W, P.top_k);
     if (rc) return rc;
+    if (cands && (size_t)B * P.top_k > h->cand_rows_cap) {   // candidate rows: on the first call that asks for them
+        if (h->cand_rows_dev) { hipDeviceSynchronize(); hipFree(h->cand_rows_dev); h->cand_rows_dev = nullptr; }
+        if (h->cand_rows_host) { hipHostFree(h->cand_rows_host); h->cand_rows_host = nullptr; }
+        h->cand_rows_cap = 0;
+        const size_t cap = (size_t)B * P.top_k;
+        if (hipMalloc((void**)&h->cand_rows_dev, sizeof(lg_grasp_candidate) * cap) != hipSuccess ||
+            hipHostMalloc((void**)&h->cand_rows_host, sizeof(lg_grasp_candidate) * cap) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, LG_ERR_NOMEM, "lg_select_grasp_candidates: candidate rows");
+        }
+        h->cand_rows_cap = cap;
+    }
     const bool use_cnn = h->cnn.loaded;
     // all eight planes are needed when the CNN rescoring runs; otherwise only distance + traditional
     for (int i = 0; i < LG_NUM_MAPS; i++)
@@ -1326,16 +1381,25 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         fa.B = B; fa.H = H; fa.W = W; fa.WW = pl.WW; fa.K = K; fa.use_cnn = use_cnn ? 1 : 0; fa.mask_is_bool = P.mask_is_bool;
         fa.cx = P.cx; fa.cy = P.cy; fa.f = P.f;
         lg_make_se_spans(2 * P.pregrasp_clearance + 1, &fa.se);
-        ProfScope ps(h, "finish", s);
-        lg_launch_finish(fa, s);
+        {
+            ProfScope ps(h, "finish", s);
+            lg_launch_finish(fa, s);
+        }
+        if (cands) {
+            ProfScope ps(h, "candidates", s);
+            lg_launch_candidates(fa, h->cand_rows_dev, s);
+        }
     }
     LG_HIP(h, hipMemcpyAsync(h->res_host, h->res_dev, sizeof(lg_grasp_result) * B, hipMemcpyDeviceToHost, s));
+    if (cands)
+        LG_HIP(h, hipMemcpyAsync(h->cand_rows_host, h->cand_rows_dev, sizeof(lg_grasp_candidate) * B * K, hipMemcpyDeviceToHost, s));
     const double t_enq2 = now();
     LG_HIP(h, hipStreamSynchronize(s));
     const double t_sync = now();
     LG_HIP(h, hipGetLastError());
     if (use_cnn && lg_cnn_take_error(&h->cnn)) return fail(h, LG_ERR_HIP, "lg_select_grasp: a split CNN item did not receive its parts");
     memcpy(results, h->res_host, sizeof(lg_grasp_result) * B);
+    if (cands) memcpy(cands, h->cand_rows_host, sizeof(lg_grasp_candidate) * B * K);
     if (trace && !piped) {
         float a[5] = {0};
         for (int i = 1; i <= 4; i++) hipEventElapsedTime(&a[i], tev[0], tev[i]);

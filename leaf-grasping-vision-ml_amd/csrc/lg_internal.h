@@ -152,6 +152,32 @@ struct LgFinishArgs {
     LgSeSpans se;                 // (2 * pregrasp_clearance + 1) ellipse
 };
 void lg_launch_finish(const LgFinishArgs& a, hipStream_t s);
+// Every candidate of every frame in rank order (lg_candidates_kernel, after lg_launch_finish on the same stream): rows [B][K]
+void lg_launch_candidates(const LgFinishArgs& a, lg_grasp_candidate* rows, hipStream_t s);
+
+// The reference's selection (grasp_point_selector.py:205-236) applied again to what is left after each pick: remaining = 0..n-1
+// in candidate order; rank r starts from the first remaining candidate j with best score trad[j] and, when rescoring and more
+// than one candidate remains, takes every scored remaining i with comb[i] > best (in candidate order); the pick leaves the
+// list.  Rank 0 is the reference's grasp point.  Comparisons only, as written: a NaN never wins and a NaN start is never
+// beaten.  n <= 64.  The device (lg_candidates_kernel) and the host export lg_rank_grasp_candidates run this code.
+__host__ __device__ inline void lg_rank_candidates(const double* trad, const double* comb, const int32_t* scored, int n,
+                                                   int rescoring, int32_t* order, double* pick, int32_t* by_ml) {
+    unsigned long long left = n >= 64 ? ~0ull : (1ull << n) - 1ull;
+    for (int r = 0; r < n; r++) {
+        const int j = __builtin_ctzll(left);
+        int best = j, ml = 0;
+        double bs = trad[j];                                   // :205-207
+        if (rescoring && (left & (left - 1ull)) != 0ull)      // :210, len(candidates) > 1
+            for (unsigned long long m = left; m; m &= m - 1ull) {
+                const int i = __builtin_ctzll(m);
+                if (scored[i] && comb[i] > bs) { bs = comb[i]; best = i; ml = 1; }   // :226-236
+            }
+        order[r] = best;
+        pick[r] = bs;
+        by_ml[r] = ml;
+        left &= ~(1ull << best);
+    }
+}
 
 // host-side contour analysis on the bit-packed mask (lg_contour.cpp)
 // returns 1 and fills out[0..4] = angle(rad,(0,pi]), major, minor, cx, cy ; 0 if the mask is empty

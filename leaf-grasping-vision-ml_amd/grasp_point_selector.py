@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import LG_NUM_MAPS, MAP_NAMES, LgGraspResult, check, lib
+from ._lib import LG_NUM_MAPS, MAP_NAMES, LgGraspCandidate, LgGraspResult, LgParams, check, lib
 from ._log import logerr, loginfo, logwarn
 from .cnn import pack_state_dict
 from .image_processor import flatness_config
@@ -23,6 +23,10 @@ from .image_processor import flatness_config
 # LgGraspResult rows as a numpy record (select_grasp_points_batch reads whole columns)
 _RESULT_DTYPE = np.dtype([(n, np.int32 if t is C.c_int else np.float32) for n, t in LgGraspResult._fields_])
 assert _RESULT_DTYPE.itemsize == C.sizeof(LgGraspResult)
+# lg_grasp_candidate rows (select_grasp_candidates_batch returns them as a [B, top_k] array of this dtype)
+GRASP_CANDIDATE_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.float32) for n, t in LgGraspCandidate._fields_])
+assert GRASP_CANDIDATE_DTYPE.itemsize == C.sizeof(LgGraspCandidate)
+_ML_FIELDS = ("ml_score", "ml_confidence", "combined")
 
 _VP = C.c_void_p
 
@@ -291,12 +295,7 @@ class GraspPointSelector:
             check(self._h, lib.lg_select_grasp(self._h, d.data_ptr(), m.data_ptr(), B, H, W, C.byref(p),
                                                C.byref(ptrs) if ptrs is not None else None, vptr, res,
                                                self._stream()), "lg_select_grasp")
-        # one structured view of the result rows instead of a ctypes attribute access per field and frame (0.12 -> 0.04 ms per 256
-        # frames; float32 -> Python float conversions are the same values either way)
-        a = np.frombuffer(res, dtype=_RESULT_DTYPE, count=B)
-        cols = [a[n].tolist() for n in ("found", "x", "y", "X", "Y", "Z", "has_pre", "pX", "pY", "pZ")]
-        out = [((x, y), (X, Y, Z), (pX, pY, pZ) if hp else None) if f else (None, None, None)
-               for f, x, y, X, Y, Z, hp, pX, pY, pZ in zip(*cols)]
+        out = _triples(res, B)
         self.last_results = res
         if return_maps:
             return out, {n: maps[i] for i, n in enumerate(MAP_NAMES)}, valid
@@ -325,11 +324,87 @@ class GraspPointSelector:
         for b, i in enumerate(leaf_ids):   # the node never calls select_grasp_point for a frame without a leaf (:113-116)
             if i is None:
                 res[b].found = 0
-        a = np.frombuffer(res, dtype=_RESULT_DTYPE, count=B)
-        cols = [a[n].tolist() for n in ("found", "x", "y", "X", "Y", "Z", "has_pre", "pX", "pY", "pZ")]
         self.last_results = res
-        return [((x, y), (X, Y, Z), (pX, pY, pZ) if hp else None) if f else (None, None, None)
-                for f, x, y, X, Y, Z, hp, pX, pY, pZ in zip(*cols)]
+        return _triples(res, B)
+
+    # ------------------------------------------------------------------ every candidate, ranked (:205-236)
+    def _candidate_params(self, image_processor, top_k, is_bool):
+        top_k = int(top_k)
+        if not 1 <= top_k <= 64:
+            raise ValueError(f"top_k must be in [1, 64] (got {top_k})")
+        p = LgParams.from_buffer_copy(self._sync_params(image_processor))   # the selector's own params keep their top_k
+        p.top_k = top_k
+        p.mask_is_bool = 1 if is_bool else 0
+        return p
+
+    def select_grasp_candidates_batch(self, leaf_masks, depth_tensors, image_processor=None, top_k=20):
+        """select_grasp_points_batch plus every candidate of every frame, ranked by the reference's own selection applied again
+        to what is left after each pick (lg_select_grasp_candidates).  Returns (triples, cands): triples as
+        select_grasp_points_batch returns them; cands a [B, top_k] numpy array of GRASP_CANDIDATE_DTYPE in rank order (rank 0 is
+        the triple's point), rows past a frame's candidate count with index -1.  Bad input raises."""
+        m, d, is_bool = self._prep_inputs(leaf_masks, depth_tensors)
+        B, H, W = m.shape
+        p = self._candidate_params(image_processor, top_k, is_bool)
+        res = (LgGraspResult * B)()
+        rows = (LgGraspCandidate * (B * p.top_k))()
+        with torch.cuda.device(self.device):
+            check(self._h, lib.lg_select_grasp_candidates(self._h, d.data_ptr(), m.data_ptr(), B, H, W, C.byref(p), res, rows,
+                                                          self._stream()), "lg_select_grasp_candidates")
+        self.last_results = res
+        return _triples(res, B), np.frombuffer(rows, dtype=GRASP_CANDIDATE_DTYPE).reshape(B, p.top_k)
+
+    def select_grasp_candidates_for_leaves(self, label_tensors, leaf_ids, depth_tensors, image_processor=None, top_k=20):
+        """select_grasp_candidates_batch(label_tensors == leaf_ids[:, None, None], depth_tensors) through the labels entry point
+        (as select_grasp_points_for_leaves; the mask counts as a torch.bool tensor).  A None leaf id gives the (None, None, None)
+        triple and zero candidate rows."""
+        lab = label_tensors
+        if not (torch.is_tensor(lab) and lab.dtype == torch.int16 and lab.is_cuda and lab.dim() == 3 and lab.is_contiguous()):
+            raise ValueError("label_tensors must be a contiguous [B,H,W] int16 tensor on the device")
+        d = depth_tensors.to(self.device, torch.float32).contiguous()
+        if d.shape != lab.shape:
+            raise ValueError(f"labels {tuple(lab.shape)} and depth {tuple(d.shape)} must both be [B,H,W]")
+        B, H, W = lab.shape
+        p = self._candidate_params(image_processor, top_k, True)
+        ids = (C.c_int32 * B)(*[(-(1 << 30)) if i is None else int(i) for i in leaf_ids])   # no label carries it: no candidates
+        res = (LgGraspResult * B)()
+        rows = (LgGraspCandidate * (B * p.top_k))()
+        with torch.cuda.device(self.device):
+            check(self._h, lib.lg_select_grasp_candidates_labels(self._h, d.data_ptr(), lab.data_ptr(), ids, B, H, W, C.byref(p),
+                                                                 res, rows, self._stream()), "lg_select_grasp_candidates_labels")
+        cands = np.frombuffer(rows, dtype=GRASP_CANDIDATE_DTYPE).reshape(B, p.top_k)
+        for b, i in enumerate(leaf_ids):   # no select_grasp_point call for a frame without a leaf: no triple, no candidates
+            if i is None:
+                res[b].found = 0
+                cands[b] = np.zeros((), GRASP_CANDIDATE_DTYPE)
+                cands[b]["index"] = -1
+        self.last_results = res
+        return _triples(res, B), cands
+
+    def select_grasp_candidates(self, leaf_mask, depth_tensor, image_processor=None, top_k=20):
+        """Every candidate of one frame in rank order, as a list of dicts: the lg_grasp_candidate fields plus point_2d, point_3d
+        and pre_grasp_point shaped like select_grasp_point's triple (a NaN ML field and a missing pre-grasp point are None).
+        The values the reference logs for each candidate (:210-236) and the runner-up grasps.  Never raises: errors are logged
+        and give []."""
+        try:
+            _, cands = self.select_grasp_candidates_batch(leaf_mask, depth_tensor, image_processor=image_processor, top_k=top_k)
+            out = []
+            for row in cands[0].tolist():
+                r = dict(zip(GRASP_CANDIDATE_DTYPE.names, row))
+                if r["index"] < 0:
+                    break
+                for k in _ML_FIELDS:
+                    if math.isnan(r[k]):
+                        r[k] = None
+                if not r["has_pre"]:
+                    r["pX"] = r["pY"] = r["pZ"] = None
+                r["point_2d"] = (r["x"], r["y"])
+                r["point_3d"] = (r["X"], r["Y"], r["Z"])
+                r["pre_grasp_point"] = (r["pX"], r["pY"], r["pZ"]) if r["has_pre"] else None
+                out.append(r)
+            return out
+        except Exception as e:  # noqa: BLE001
+            logerr(f"Error in grasp candidate ranking: {str(e)}")
+            return []
 
     def select_grasp_point(self, leaf_mask, depth_tensor, image_processor=None, pcl_data=None):
         """Select optimal grasp point using combined traditional and ML approach (reference :184)."""
@@ -424,6 +499,15 @@ class GraspPointSelector:
         except Exception as e:  # noqa: BLE001
             logerr(f"Error in midrib detection: {str(e)}")
             return None
+
+
+def _triples(res, B):
+    """(xy, XYZ, preXYZ) triples of B lg_grasp_result rows.  One structured view of the rows instead of a ctypes attribute access
+    per field and frame (0.12 -> 0.04 ms per 256 frames; float32 -> Python float conversions are the same values either way)."""
+    a = np.frombuffer(res, dtype=_RESULT_DTYPE, count=B)
+    cols = [a[n].tolist() for n in ("found", "x", "y", "X", "Y", "Z", "has_pre", "pX", "pY", "pZ")]
+    return [((x, y), (X, Y, Z), (pX, pY, pZ) if hp else None) if f else (None, None, None)
+            for f, x, y, X, Y, Z, hp, pX, pY, pZ in zip(*cols)]
 
 
 _clahe_handles = {}   # device index -> (lock, handle) of leafgrasp_amd.clahe
