@@ -60,6 +60,27 @@ def compare_step(tr, ref, loss, logits, gnorm, tight=True):
             assert e <= 2e-4, (k, e)
 
 
+def assert_adam_replay(tr, sd, params, names, own_g, own_norm):
+    """clip_grad_norm_ + torch.optim.Adam replayed on the host in float32 from the trainer's own gradients (own_g, own_norm:
+    one entry per step from `params`) must give the trainer's parameters `sd` to rounding, every element of every tensor."""
+    hp = tr.hp
+    lr, b1, b2, eps_, wd, mx = (np.float32(v) for v in (hp.lr, hp.beta1, hp.beta2, hp.eps, hp.weight_decay, hp.max_grad_norm))
+    one = np.float32(1.0)
+    for k in names:
+        pk = np.asarray(params[k], np.float32).copy()
+        m = np.zeros_like(pk)
+        v = np.zeros_like(pk)
+        for t_, (gd, gn) in enumerate(zip(own_g, own_norm), start=1):
+            coef = min(mx / (np.float32(gn) + np.float32(1e-6)), one)
+            gi = gd[k].astype(np.float32) * coef + wd * pk
+            m = b1 * m + (one - b1) * gi
+            v = b2 * v + (one - b2) * gi * gi
+            bc1, bc2 = one - b1 ** np.float32(t_), one - b2 ** np.float32(t_)
+            pk = pk - (lr / bc1) * (m / (np.sqrt(v) / np.sqrt(bc2) + eps_))
+        # (fp32 rounding of g * coef + wd * p where the two terms nearly cancel is amplified by 1 / sqrt(v): up to ~1e-6, 0.2 % of lr)
+        np.testing.assert_allclose(sd[k].numpy(), pk, rtol=2e-6, atol=2.5e-6, err_msg=f"Adam replay {k}")
+
+
 @pytest.mark.parametrize("att,filt,n", CASES)
 def test_train_step_matches_reference_fixture(att, filt, n):
     """Step 0 from the closed-form weights: loss, logits, total and per-tensor gradient norms, sampled gradients, BatchNorm
@@ -115,22 +136,7 @@ def test_train_step_matches_reference_fixture(att, filt, n):
     # (1) The optimiser itself, free of any ReLU / max-pool decision: clip_grad_norm_(1.0) + torch.optim.Adam (L2 weight decay,
     #     bias corrections; scripts/train_model.py:247-265) replayed on the host in float32 from THIS path's own two gradients
     #     must give this path's parameters to rounding, every element of every tensor.
-    hp = tr.hp
-    lr, b1, b2, eps_, wd, mx = (np.float32(v) for v in (hp.lr, hp.beta1, hp.beta2, hp.eps, hp.weight_decay, hp.max_grad_norm))
-    one = np.float32(1.0)
-    for k in names:
-        pk = np.asarray(params[k], np.float32).copy()
-        m = np.zeros_like(pk)
-        v = np.zeros_like(pk)
-        for t_, (gd, gn) in enumerate(zip(own_g, own_norm), start=1):
-            coef = min(mx / (np.float32(gn) + np.float32(1e-6)), one)
-            gi = gd[k].astype(np.float32) * coef + wd * pk
-            m = b1 * m + (one - b1) * gi
-            v = b2 * v + (one - b2) * gi * gi
-            bc1, bc2 = one - b1 ** np.float32(t_), one - b2 ** np.float32(t_)
-            pk = pk - (lr / bc1) * (m / (np.sqrt(v) / np.sqrt(bc2) + eps_))
-        # (fp32 rounding of g * coef + wd * p where the two terms nearly cancel is amplified by 1 / sqrt(v): up to ~1e-6, 0.2 % of lr)
-        np.testing.assert_allclose(sd[k].numpy(), pk, rtol=2e-6, atol=2.5e-6, err_msg=f"Adam replay {k}")
+    assert_adam_replay(tr, sd, params, names, own_g, own_norm)
     # (2) Against the reference fixture.  Adam's first update is lr * sign(g) and later ones depend on RATIOS of gradients, so a
     #     parameter can only leave the fixture's value where this path's gradient element differs from the reference's: where the
     #     sampled gradients of BOTH steps agree (every tensor within 1e-3 of its RMS: no ReLU / max-pool decision fell the other
@@ -186,6 +192,64 @@ def test_train_step_with_dropout_masks_vs_oracle(att, filt, n, seed):
     for k in ref2["opt_state"]["exp_avg"]:
         assert_close_robust(opt["exp_avg"][k].numpy(), ref2["opt_state"]["exp_avg"][k], 2e-2, 1e-5, 0.05, 0.08, what="m " + k)
         assert_close_robust(opt["exp_avg_sq"][k].numpy(), ref2["opt_state"]["exp_avg_sq"][k], 4e-2, 1e-9, 0.05, 0.1, what="v " + k)
+
+
+# lgt_conv_kernel's three shapes (launch_conv in lg_train.hip; forward and dgrad): large (256 px x 64 channels, several samples
+# per tile on the 8 x 8 and 4 x 4 layers), small, K-split.  The thresholds are read at lg_train_create: the environment forces
+# one form on every layer it can take (the K-split needs 32 input channels; layer 0 keeps its own choice there).
+CONV_FORMS = {"large": {"LG_TRAIN_CONV_SMALL": "0", "LG_TRAIN_CONV_SPLIT": "0"},
+              "small": {"LG_TRAIN_CONV_SMALL": "1073741824", "LG_TRAIN_CONV_SPLIT": "0"},
+              "split": {"LG_TRAIN_CONV_SPLIT": "1073741824"}}
+ENCODERS = [("spatial", (64, 128, 256)), ("spatial", (32, 64, 128)), ("none", (128, 256, 512)), ("hybrid", (64, 128, 256, 512))]
+
+
+def _first_step_vs_oracle(tr, params, x, y, filt, seed):
+    mk = random_masks(filt, len(x), seed)
+    ref = O.cnn_train_step(params, x, y, masks=mk)
+    loss, logits, gnorm = tr.train_step(x, y, masks=mk, return_logits=True)
+    compare_step(tr, ref, loss, logits, gnorm, tight=True)
+    sd = tr.state_dict()
+    for k in ref["params"]:
+        if "running_" in k:
+            np.testing.assert_allclose(sd[k].numpy(), ref["params"][k], rtol=1e-4, atol=1e-5, err_msg=k)
+    return gnorm
+
+
+@pytest.mark.parametrize("form", list(CONV_FORMS))
+@pytest.mark.parametrize("att,filt", ENCODERS, ids=["standard", "lightweight", "wide", "deep"])
+def test_train_step_every_conv_form_on_ragged_tiles(monkeypatch, att, filt, form):
+    """13 samples: ragged against every multi-sample tile of the large form (4 samples at 8 x 8, 16 at 4 x 4)."""
+    n, seed = 13, 40
+    params = S.cnn_closed_form_params(seed=seed, attention_type=att, filters=filt)
+    x = S.synthetic_patches(n, seed=seed)
+    y = (np.arange(n) % 3 == 0).astype(np.float32)
+    for k, v in CONV_FORMS[form].items():
+        monkeypatch.setenv(k, v)
+    tr = make_trainer(att, filt, 16)
+    for k in CONV_FORMS[form]:
+        monkeypatch.delenv(k)
+    tr.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()})
+    _first_step_vs_oracle(tr, params, x, y, filt, seed)
+
+
+def test_train_step_at_the_natural_large_form_batch():
+    """258 samples with the default thresholds: the 8 x 8 layers take the large form with a half-filled last tile and the
+    BatchNorm reductions run in sample chunks.  Step one against the oracle; two steps against the host replay of Adam."""
+    att, filt, n, seed = "spatial", (64, 128, 256), 258, 41
+    params = S.cnn_closed_form_params(seed=seed, attention_type=att, filters=filt)
+    x = S.synthetic_patches(n, seed=seed)
+    y = (np.random.default_rng(seed).random(n) < 0.4).astype(np.float32)
+    tr = make_trainer(att, filt, n)
+    tr.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()})
+    own_norm = [_first_step_vs_oracle(tr, params, x, y, filt, seed)]
+    own_g = [{k: v.numpy().copy() for k, v in tr.gradients().items()}]
+    _, _, gnorm1 = tr.train_step(x, y, masks=random_masks(filt, n, seed + 100), return_logits=True)
+    own_g.append({k: v.numpy().copy() for k, v in tr.gradients().items()})
+    own_norm.append(gnorm1)
+    from leafgrasp_amd.trainer import parameter_layout
+    names = [k for k, _ in parameter_layout(filt, att)[0]]
+    assert tr.optimizer_state()["step"] == 2
+    assert_adam_replay(tr, tr.state_dict(), params, names, own_g, own_norm)
 
 
 def test_gradients_only_and_determinism():
