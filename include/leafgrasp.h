@@ -82,8 +82,10 @@ typedef struct lg_params {
     float iso_ramp_top, iso_ramp_bottom;            /* 1.0 0.2                    (:623)     */
     float min_edge_distance;                        /* 20                         (:25,285)  */
     float stem_valid_thresh;                        /* 0.8                        (:287)     */
-    int32_t stem_se;                                /* ellipse 30                 (:696)     */
-    int32_t stem_bottom_div;                        /* bottom H//3 rows           (:693)     */
+    int32_t stem_se;                                /* ellipse 30                 (:696); 1..64 */
+    int32_t stem_bottom_div;                        /* bottom H//3 rows           (:693); >= 1.  A divisor larger than H follows
+                                                       numpy as the reference's line does: H // div == 0 and bottom[-0:, :] is the
+                                                       WHOLE frame, so every leaf pixel is stem (not "no row") */
     int32_t top_k;                                  /* 20                         (:197)     */
     int32_t nms_min_distance;                       /* 10                         (:198)     */
     int32_t pregrasp_clearance;                     /* 15 px (SE 31)              (:777-778) */

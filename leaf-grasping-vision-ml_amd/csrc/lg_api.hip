@@ -524,9 +524,11 @@ int enq_tail(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
     {
         LgSeSpans se;
         lg_make_se_spans(pl.P.stem_se, &se);
+        // bottom[-third:, :] = 1 (:693-694): a frame shorter than the divisor has third == 0, and numpy's [-0:] is every row
+        const int third = pl.H / pl.P.stem_bottom_div;
         ProfScope ps(h, "stem", s);
         lg_launch_stem_bits(h->bits + off * words, h->stem + off * words, n, pl.H, pl.W, pl.WW,
-                            pl.H - pl.H / pl.P.stem_bottom_div, se, s);
+                            third ? pl.H - third : 0, se, s);
     }
     return LG_OK;
 }

@@ -199,7 +199,7 @@ class GraspPointSelector:
 
     def _get_valid_regions(self, leaf_mask_np, scores):  # :282-288 (host helper for callers holding a scores dict)
         return ((scores["distance_map"] > self.min_edge_distance) & (np.asarray(leaf_mask_np) > 0)
-                & (scores["stem_penalty"] < 0.8))
+                & (scores["stem_penalty"] < self.params.stem_valid_thresh))
 
     # ------------------------------------------------------------------ candidates (:447-482)
     def _get_candidate_points(self, score_map, valid_regions, top_k=20, min_distance=10):

@@ -26,6 +26,7 @@ Parity status
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 import os
 import subprocess
@@ -241,28 +242,77 @@ def smooth_depth(depth_f32, gaussian_size=5):
     return _xcorr_valid_f32(padded, g)
 
 
-def flatness_map(depth_times_mask_f32, gaussian_size=5):
+def flatness_map(depth_times_mask_f32, gaussian_size=5, flat_scale=5.0):
     """GraspPointSelector._calculate_flatness_map (grasp_point_selector.py:635-657)."""
     g = smooth_depth(depth_times_mask_f32, gaussian_size)
     padded = np.pad(g, 1, mode="reflect")
     dx = _xcorr_valid_f32(padded, SOBEL_X)
     dy = _xcorr_valid_f32(padded, SOBEL_Y)
     mag = np.sqrt(dx * dx + dy * dy, dtype=np.float32)
-    return np.exp(-mag * np.float32(5.0), dtype=np.float32)
+    return np.exp(-mag * np.float32(flat_scale), dtype=np.float32)
 
 
 # --------------------------------------------------------------------------- grasp_point_selector.py
+@dataclasses.dataclass
+class RefParams:
+    """The constants of the scoring path under the field names of lg_params (include/leafgrasp.h; the camera fields travel
+    through set_camera_params).  The defaults are the reference's literals as the reference types them (Python ints where it
+    writes ints), so that a selector built with RefParams() computes bit for bit what the reference's own text computes."""
+    w_approach: float = 0.4           # :272-277
+    w_sdf: float = 0.3
+    w_flat: float = 0.2
+    w_access: float = 0.1
+    sdf_w_interior: float = 0.4       # :563-565
+    sdf_w_align: float = 0.4
+    sdf_w_sdf: float = 0.2
+    optimal_distance: float = 20      # :535-536
+    access_w_dist: float = 0.7        # :522
+    access_w_dir: float = 0.3
+    flat_scale: float = 5             # :655
+    iso_w_close: float = 0.7          # :620
+    iso_w_wide: float = 0.3
+    iso_ramp_top: float = 1.0         # :623
+    iso_ramp_bottom: float = 0.2
+    min_edge_distance: float = 20     # :25, :285
+    stem_valid_thresh: float = 0.8    # :287
+    stem_se: int = 30                 # :696
+    stem_bottom_div: int = 3          # :693
+    top_k: int = 20                   # :197
+    nms_min_distance: int = 10        # :198
+    pregrasp_clearance: int = 15      # :777-778 (SE 2 * 15 + 1)
+    mask_is_bool: int = 1             # the node's mask is a torch.bool tensor (SURVEY App. B.7)
+    gaussian_size: int = 5            # leaf_grasp_node_v3.py:37
+    chamfer_init_dist0: int = INIT_DIST0
+
+
+def ref_params(params=None, **changes):
+    """RefParams from None (the defaults), a RefParams or a dict of lg_params field names, with `changes` on top."""
+    if params is None:
+        params = RefParams()
+    elif isinstance(params, dict):
+        params = RefParams(**params)
+    return dataclasses.replace(params, **changes) if changes else params
+
+
 class RefGraspPointSelector:
     """Restatement of scripts/utils/grasp_point_selector.py::GraspPointSelector (CV maps, candidates,
-    CNN rescoring loop, 3-D back-projection, pre-grasp).  numpy in, numpy out."""
+    CNN rescoring loop, 3-D back-projection, pre-grasp).  numpy in, numpy out.
+    `params` (a RefParams or a dict of lg_params field names) puts other constants in the place of the reference's
+    literals; the arithmetic around them stays the reference's.  Without it `gaussian_size` / `init_dist0` are taken from
+    the two older arguments."""
 
-    def __init__(self, cnn=None, gaussian_size=5, init_dist0=INIT_DIST0):
-        self.init_dist0 = init_dist0   # OpenCV's INIT_DIST0 (library-revision dependent, see distance_transform)
+    def __init__(self, cnn=None, gaussian_size=5, init_dist0=INIT_DIST0, params=None):
+        if params is None:
+            params = RefParams(gaussian_size=gaussian_size, chamfer_init_dist0=init_dist0)
+        else:
+            assert gaussian_size == 5 and init_dist0 == INIT_DIST0, "pass gaussian_size / chamfer_init_dist0 inside params"
+        self.params = params = ref_params(params)
+        self.init_dist0 = params.chamfer_init_dist0   # OpenCV's INIT_DIST0 (library-revision dependent, see distance_transform)
         self.camera_cx = 707  # grasp_point_selector.py:29-31
         self.camera_cy = 494
         self.f_norm = None
-        self.min_edge_distance = 20  # :25
-        self.gaussian_size = gaussian_size  # leaf_grasp_node_v3.py:37
+        self.min_edge_distance = params.min_edge_distance  # :25
+        self.gaussian_size = params.gaussian_size  # leaf_grasp_node_v3.py:37
         self.cnn = cnn  # callable [B,9,32,32] float32 -> [B] logits, or None (= no best_model.pth, :52-54)
 
     # :145-150
@@ -280,7 +330,7 @@ class RefGraspPointSelector:
         max_dist = np.sqrt(width ** 2 + height ** 2)
         amap = 1 - (dist / max_dist)
         angle = np.arctan2(y_grid - self.camera_cy, x_grid - self.camera_cx)
-        return (0.7 * amap + 0.3 * np.cos(angle)) * m
+        return (self.params.access_w_dist * amap + self.params.access_w_dir * np.cos(angle)) * m
 
     # :569-593  (depth argument is unused by the reference)
     def calculate_approach_vector_score(self, m):
@@ -305,7 +355,7 @@ class RefGraspPointSelector:
         dist_inside = distance_transform(m, 5, init_dist0=self.init_dist0)
         dist_outside = distance_transform(1 - m, 5, init_dist0=self.init_dist0)
         sdf = dist_inside - dist_outside
-        optimal_distance = 20
+        optimal_distance = self.params.optimal_distance
         interior = np.exp(-((dist_inside - optimal_distance) ** 2) / (2 * optimal_distance ** 2))
         sdf = sdf / np.max(np.abs(sdf))
         y, x = np.indices(m.shape)
@@ -321,7 +371,8 @@ class RefGraspPointSelector:
             align = np.abs(vx * np.sin(angle) - vy * np.cos(angle))
         else:
             align = np.ones_like(sdf)
-        final = (0.4 * interior + 0.4 * align + 0.2 * sdf) * m
+        p = self.params
+        final = (p.sdf_w_interior * interior + p.sdf_w_align * align + p.sdf_w_sdf * sdf) * m
         if return_parts:
             return final, dict(dist_inside=dist_inside, dist_outside=dist_outside, angle=angle)
         return final
@@ -340,8 +391,8 @@ class RefGraspPointSelector:
         iw = dilate(other, kernel_wide)
         dw = distance_transform(1 - iw, 3, init_dist0=self.init_dist0)
         sw = dw / (np.max(dw) + 1e-6)
-        iso = (0.7 * sc + 0.3 * sw).astype(np.float32)  # float32 array * python float stays float32
-        yc = np.linspace(1.0, 0.2, height)[:, np.newaxis]
+        iso = (self.params.iso_w_close * sc + self.params.iso_w_wide * sw).astype(np.float32)  # float32 array * python float stays float32
+        yc = np.linspace(self.params.iso_ramp_top, self.params.iso_ramp_bottom, height)[:, np.newaxis]
         hp = np.tile(yc, (1, width))
         return iso * hp * current
 
@@ -349,10 +400,10 @@ class RefGraspPointSelector:
     def _calculate_stem_penalty(self, m):
         bottom = np.zeros_like(m)
         h, w = m.shape
-        third = h // 3
-        bottom[-third:, :] = 1
+        third = h // self.params.stem_bottom_div
+        bottom[-third:, :] = 1   # third == 0 (a frame shorter than the divisor): [-0:] is the WHOLE frame, as numpy reads it
         masked_bottom = m & bottom
-        stem = dilate(masked_bottom, ellipse_se(30)) & m
+        stem = dilate(masked_bottom, ellipse_se(self.params.stem_se)) & m
         return stem.astype(np.float32)
 
     # :256-280
@@ -363,22 +414,23 @@ class RefGraspPointSelector:
             "sdf_score": sdf,
             "approach_score": self.calculate_approach_vector_score(m),
             "flatness_map": flatness_map(np.asarray(depth_f32, np.float32) * m.astype(np.float32),
-                                         self.gaussian_size),
+                                         self.gaussian_size, self.params.flat_scale),
             "isolation_map": self._calculate_isolation_score(m),
             "distance_map": distance_transform(m, 5, init_dist0=self.init_dist0),  # :266 (recomputed by the reference)
             "accessibility_map": self._calculate_accessibility_score(m),
             "stem_penalty": self._calculate_stem_penalty(m).astype(np.float32),
         }
+        p = self.params
         scores["traditional_score"] = (
-            0.4 * scores["approach_score"] + 0.3 * scores["sdf_score"]
-            + 0.2 * scores["flatness_map"] + 0.1 * scores["accessibility_map"]
+            p.w_approach * scores["approach_score"] + p.w_sdf * scores["sdf_score"]
+            + p.w_flat * scores["flatness_map"] + p.w_access * scores["accessibility_map"]
         ) * (1 - scores["stem_penalty"])
         self._last_angle = parts["angle"]
         return scores
 
     # :282-288
     def _get_valid_regions(self, m, scores):
-        return (scores["distance_map"] > self.min_edge_distance) & (m > 0) & (scores["stem_penalty"] < 0.8)
+        return (scores["distance_map"] > self.min_edge_distance) & (m > 0) & (scores["stem_penalty"] < self.params.stem_valid_thresh)
 
     # :447-482.  tie_rule="total": score desc then flat index desc (the build's documented
     # total order); tie_rule="numpy": the reference's np.argsort()[::-1].
@@ -452,7 +504,7 @@ class RefGraspPointSelector:
             g = np.array(g3, dtype=np.float64)
             with np.errstate(all="ignore"):
                 direction = g / np.linalg.norm(g)
-            dil = dilate(m, ellipse_se(31))
+            dil = dilate(m, ellipse_se(2 * self.params.pregrasp_clearance + 1))
             min_d, max_d, step = 0.05, 0.10, 0.01
             for dist in np.arange(min_d, max_d, step):
                 t = (g3[0] - direction[0] * dist, g3[1] - direction[1] * dist, g3[2])
@@ -468,12 +520,15 @@ class RefGraspPointSelector:
             return None
 
     # :184-253
-    def select_grasp_point(self, m, depth_f32, tie_rule="total", mask_is_bool=True, return_debug=False):
+    def select_grasp_point(self, m, depth_f32, tie_rule="total", mask_is_bool=None, return_debug=False):
         m = np.ascontiguousarray(m, np.uint8)
         depth_f32 = np.asarray(depth_f32, np.float32)
         scores = self._calculate_all_scores(m, depth_f32)
         valid = self._get_valid_regions(m, scores)
-        cands = self._get_candidate_points(scores["traditional_score"], valid, 20, 10, tie_rule)
+        if mask_is_bool is None:   # (the older callers pass it; the parameter set carries the node's torch.bool by default)
+            mask_is_bool = bool(self.params.mask_is_bool)
+        cands = self._get_candidate_points(scores["traditional_score"], valid, self.params.top_k,
+                                           self.params.nms_min_distance, tie_rule)
         if not cands:
             return (None, None, None) if not return_debug else ((None, None, None), {})
         best = cands[0]

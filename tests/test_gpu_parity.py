@@ -35,10 +35,12 @@ def _oracle(P, cnn=None):
     return r
 
 
-def _compare_maps(sel, mask, depth, P, exact_dt=True):
+def _compare_maps(sel, mask, depth, P, exact_dt=True, ref=None, image_processor=None):
+    """`ref`: the oracle to hold the planes to (tests/test_gpu_params.py passes one built with the selector's constants);
+    `image_processor`: the caller's, whose Gaussian size the flatness plane follows."""
     sel.set_camera_params(P)
-    maps, valid, theta = sel.score_maps(torch.from_numpy(mask).cuda(), torch.from_numpy(depth).cuda())
-    ref = _oracle(P)
+    maps, valid, theta = sel.score_maps(torch.from_numpy(mask).cuda(), torch.from_numpy(depth).cuda(), image_processor)
+    ref = ref or _oracle(P)
     sc = ref._calculate_all_scores(mask, depth)
     if exact_dt:  # integer work: bit-exact
         np.testing.assert_array_equal(maps["distance_map"].cpu().numpy(), sc["distance_map"])

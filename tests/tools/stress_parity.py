@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Randomised GPU-vs-oracle parity sweep (many seeds / odd sizes / multi-component masks).
+"""Randomised GPU-vs-oracle parity sweep (many seeds / odd sizes / multi-component masks), every second case under a set of
+constants drawn from tests/param_sets.py instead of the defaults.
 Usage: python tests/tools/stress_parity.py [n_cases]"""
 import os
 import sys
@@ -10,9 +11,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import leafgrasp_amd as L  # noqa: E402
 from oracle import lg_oracle as O  # noqa: E402
+from tests import param_sets as PS  # noqa: E402
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-sel = L.GraspPointSelector("cuda:0", load_model=False)
 rng = np.random.default_rng(2024)
 bad = 0
 for case in range(n_cases):
@@ -33,10 +34,19 @@ for case in range(n_cases):
     else:
         mask = (labels == 2) | (labels == 3)
     mask = mask.astype(np.uint8)
+    pset = PS.SETS[int(rng.integers(len(PS.SETS)))] if case % 2 else None       # a random set of constants, or the defaults
+    params = PS.params_of(pset.changes if pset else {})
+    if case % 3 == 1:
+        params["gaussian_size"] = int(rng.choice([1, 3, 7]))      # the caller's ImageProcessor decides the smoothing (round 3)
+    gs = params["gaussian_size"]
+    sel = L.GraspPointSelector("cuda:0", load_model=False)
     sel.set_camera_params(P)
-    gs = int(rng.choice([1, 3, 7])) if case % 3 == 1 else 5      # the caller's ImageProcessor decides the smoothing (round 3)
+    for k, v in params.items():
+        if k not in ("min_edge_distance", "gaussian_size", "mask_is_bool"):
+            setattr(sel.params, k, v)
+    sel.min_edge_distance = params["min_edge_distance"]           # (the mirror writes these two into lg_params itself)
     maps, valid, theta = sel.score_maps(torch.from_numpy(mask).cuda(), torch.from_numpy(depth).cuda(), L.ImageProcessor(H, W, 21, gs))
-    ref = O.RefGraspPointSelector(gaussian_size=gs)
+    ref = O.RefGraspPointSelector(params=params)
     ref.set_camera_params(P)
     sc = ref._calculate_all_scores(mask, depth)
     msgs = []
@@ -61,6 +71,6 @@ for case in range(n_cases):
                 msgs.append(f"candidates(on the GPU planes, k={kk}, min_distance={md})")
     if msgs:
         bad += 1
-        print(f"case {case}: H={H} W={W} kind={kind} gaussian={gs}: " + "; ".join(msgs))
+        print(f"case {case}: H={H} W={W} kind={kind} gaussian={gs} set={pset.name if pset else 'defaults'}: " + "; ".join(msgs))
 print(f"{n_cases - bad}/{n_cases} cases clean")
 sys.exit(1 if bad else 0)
