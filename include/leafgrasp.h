@@ -246,6 +246,15 @@ int lg_select_grasp_candidates_labels(lg_handle h, const float* depth, const int
 int lg_rank_grasp_candidates(const double* trad, const double* comb, const int32_t* scored, int n, int rescoring,
                              int32_t* order, double* pick, int32_t* by_ml);
 
+/* The CNN rescoring of one candidate on the host (no device, no handle), the code the device runs (:133-136, :222-226):
+   ml = tanh(3 sigmoid(logit)) / 2 + 1/2, confidence = 1 - 2 |ml - 1/2|, combined = (1 - w) trad + w ml, w = min(0.3, 0.6 confidence).
+   lg_cnn_candidate_cannot_win: 1 if a candidate with traditional score trad_i can never be taken by the selection loop of a
+   frame whose candidate 0 scores trad_0, whatever its logit -- combined <= 0.7 trad_i + 0.225 (trad_i < 0.5), <= trad_i +
+   0.3 (1 - trad_i)^2 (else), compared with a margin of 1e-12 (1 + |trad_0| + |trad_i|); 0 for a NaN or an infinity in either
+   score.  lg_select_grasp does not put such a candidate's patch through the CNN (LG_CNN_PRUNE=0 at lg_create: it does). */
+int lg_ml_combined_score(double logit, double trad, double* ml, double* confidence, double* combined);
+int lg_cnn_candidate_cannot_win(double trad_i, double trad_0);
+
 /* The node's result message of every frame (leaf_grasp_node_v3.py:170-176: "x,y,X,Y,Z[,pX,pY,pZ]", each number as Python's
    str() prints it -- the shortest decimal string of the float32 value as a double), '\n'-terminated, one line per frame in
    order, an empty line for a frame without a result.  buf: HOST, cap bytes (>= 256 per frame); *used = bytes written.
@@ -349,6 +358,9 @@ int lg_debug_dt_max(lg_handle h, int frame, uint32_t out[2], int32_t win[4]);
 /* form[0] = 1: d_in of that frame came from the row search (0: from the two sweeps); form[1] = 1: its d_out sweeps were
    skipped (the maximum provably lies on the frame border).  Which form a batch takes is decided on the device. */
 int lg_debug_dt_form(lg_handle h, int frame, int32_t form[2]);
+/* *patches = how many patches the last lg_select_grasp* call on this handle put through the CNN (0 without a model;
+   B * top_k where every candidate is scored: lg_select_grasp_candidates*, LG_CNN_PRUNE=0).  Synchronises the device. */
+int lg_debug_cnn_scored(lg_handle h, int64_t* patches);
 
 /* ---- GraspPointCNN training step: one call = one iteration of the inner loop of
    scripts/train_model.py:247-265 (zero_grad, forward in train mode, BCEWithLogitsLoss(pos_weight), backward,

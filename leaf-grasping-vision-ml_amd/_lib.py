@@ -90,6 +90,9 @@ SYMBOLS = {
     "lg_select_grasp_candidates_labels": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(LgParams), C.POINTER(LgGraspResult), C.POINTER(LgGraspCandidate), _VP]),
     "lg_rank_grasp_candidates": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
+    "lg_ml_combined_score": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double)]),
+    "lg_cnn_candidate_cannot_win": (C.c_int, [C.c_double, C.c_double]),
     "lg_leaf_stats": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                 C.POINTER(LgLeafStat), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32), _VP]),
     "lg_leaf_stats_batch": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
@@ -106,6 +109,7 @@ SYMBOLS = {
     "lg_debug_dt_max": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "lg_format_grasp_results": (C.c_int, [_VP, C.c_int, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "lg_debug_dt_form": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int32)]),
+    "lg_debug_cnn_scored": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "lg_harvest_patches": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lg_negative_masks": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
     "lg_leaf_contour": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, C.c_int, C.POINTER(C.c_int), _VP]),

@@ -67,6 +67,14 @@ struct lg_ctx {
     uint8_t* ws_valid = nullptr;
     int32_t *cand_xy = nullptr, *cand_n = nullptr;
     float *cand_info = nullptr, *patches = nullptr, *logits = nullptr;
+    // CNN pruning (lg_select_grasp): the candidates that can still win (lg_cnn_cannot_win), found on the device behind top-k
+    unsigned long long* surv_keep = nullptr;  // [B] bit i: candidate i goes through the CNN (lg_topk_kernel)
+    int32_t* surv_list = nullptr;             // [B * K] patch slot -> frame * K + candidate, per sub-batch (lg_survivors_kernel)
+    int32_t* surv_slot = nullptr;             // [B * K] candidate -> patch slot of its sub-batch, -1: pruned
+    int32_t* surv_count = nullptr;            // [B] patches of sub-batch k (one sub-batch by default)
+    bool opt_cnn_prune = true;                // LG_CNN_PRUNE=0: every candidate's patch goes through the CNN (A/B, tests)
+    long long last_scored = 0;                // lg_debug_cnn_scored: patches of the last call, when the host knows them;
+    int last_scored_subs = 0;                 //   > 0: the sum of surv_count[0 .. last_scored_subs) instead
     lg_grasp_result* res_dev = nullptr;       // [B] result rows written by lg_finish_kernel
     lg_grasp_result* res_host = nullptr;      // pinned copy
     // lg_select_grasp_candidates*: [cand_rows_cap] rows of lg_candidates_kernel and their pinned copy, allocated on the first such
@@ -193,6 +201,9 @@ void free_ws(lg_ctx* h) {
     F(h->tmp); F(h->bits); F(h->stem); F(h->tilekeys); F(h->tile_state); F(h->maxfix); F(h->dt_batch); F(h->win); F(h->fp_dev);
     for (int i = 0; i < LG_NUM_MAPS; i++) { F(h->ws_maps_base[i]); h->ws_maps_base[i] = h->ws_maps[i] = nullptr; }
     F(h->ws_valid); F(h->cand_xy); F(h->cand_n); F(h->cand_info); F(h->patches); F(h->logits);
+    F(h->surv_keep); F(h->surv_list); F(h->surv_slot); F(h->surv_count);
+    h->surv_keep = nullptr; h->surv_list = h->surv_slot = h->surv_count = nullptr;
+    h->last_scored = 0; h->last_scored_subs = 0;
     auto HF = [](void* p) { if (p) hipHostFree(p); };
     HF(h->fp_host); HF(h->bits_host); HF(h->win_host); HF(h->res_host);
     F(h->res_dev);
@@ -236,6 +247,10 @@ int ensure_ws(lg_ctx* h, int B, int H, int W, int K) {
     LG_HIP(h, dev_alloc(&h->patches, (size_t)nB * nK * lg_cnn_halo_patch_floats()));
     LG_HIP(h, hipMemset(h->patches, 0, (size_t)nB * nK * lg_cnn_halo_patch_floats() * sizeof(float)));
     LG_HIP(h, dev_alloc(&h->logits, (size_t)nB * nK));
+    LG_HIP(h, dev_alloc(&h->surv_keep, (size_t)nB));
+    LG_HIP(h, dev_alloc(&h->surv_list, (size_t)nB * nK));
+    LG_HIP(h, dev_alloc(&h->surv_slot, (size_t)nB * nK));
+    LG_HIP(h, dev_alloc(&h->surv_count, (size_t)nB));
     LG_HIP(h, dev_alloc(&h->res_dev, (size_t)nB));
     LG_HIP(h, hipHostMalloc((void**)&h->res_host, sizeof(lg_grasp_result) * nB));
     if (!h->opt_host_orient && H <= 16384 && W <= 8192) {
@@ -367,6 +382,7 @@ int lg_create(int device, lg_handle* out) {
     if (const char* e = getenv("LG_NO_SKIP")) h->opt_no_skip = std::max(1, atoi(e)) & 3;   // (both bits leave the results unchanged)
     h->opt_nt_stores = getenv("LG_NT_STORES") != nullptr;
     h->opt_host_orient = getenv("LG_HOST_ORIENT") != nullptr;
+    if (const char* e = getenv("LG_CNN_PRUNE")) h->opt_cnn_prune = atoi(e) != 0;
     if (const char* e = getenv("LG_DT_SEARCH")) h->opt_dt_search = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("LG_DT_SEARCH_ALGO")) h->opt_dt_algo = std::max(0, std::min(4, atoi(e)));
     if (const char* e = getenv("LG_SIDE_TAIL")) h->opt_side_tail = std::max(0, std::min(2, atoi(e)));
@@ -473,6 +489,24 @@ int lg_debug_dt_max(lg_handle h, int frame, uint32_t out[2], int32_t win[4]) {
         win[0] = w.wx0; win[1] = w.wx0 + w.nw * lg_dt_geometry(h->capW, nullptr); win[2] = w.wy0; win[3] = w.wy1;
         if (win[1] > h->capW) win[1] = h->capW;
     }
+    return LG_OK;
+}
+
+int lg_debug_cnn_scored(lg_handle h, int64_t* patches) {
+    if (!h || !patches) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    long long n = h->last_scored;
+    if (h->last_scored_subs > 0) {
+        if (!h->surv_count || h->last_scored_subs > h->capB) return LG_ERR_INVALID;
+        hipSetDevice(h->device);
+        hipDeviceSynchronize();
+        std::vector<int32_t> c((size_t)h->last_scored_subs);
+        if (hipMemcpy(c.data(), h->surv_count, sizeof(int32_t) * c.size(), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(h, LG_ERR_HIP, "lg_debug_cnn_scored: copy failed");
+        n = 0;
+        for (int32_t v : c) n += v;
+    }
+    *patches = n;
     return LG_OK;
 }
 
@@ -1184,6 +1218,14 @@ int lg_select_grasp_candidates_labels(lg_handle h, const float* depth, const int
     return lg_select_grasp_labels_impl(h, depth, labels, leaf_ids, B, H, W, pin, nullptr, nullptr, results, cands, stream_);
 }
 
+int lg_ml_combined_score(double logit, double trad, double* ml, double* confidence, double* combined) {
+    if (!ml || !confidence || !combined) return LG_ERR_INVALID;
+    lg_ml_combine(logit, trad, ml, confidence, combined);
+    return LG_OK;
+}
+
+int lg_cnn_candidate_cannot_win(double trad_i, double trad_0) { return lg_cnn_cannot_win(trad_i, trad_0) ? 1 : 0; }
+
 int lg_rank_grasp_candidates(const double* trad, const double* comb, const int32_t* scored, int n, int rescoring, int32_t* order,
                              double* pick, int32_t* by_ml) {
     if (n < 0 || n > 64) return LG_ERR_INVALID;
@@ -1249,6 +1291,12 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         h->cand_rows_cap = cap;
     }
     const bool use_cnn = h->cnn.loaded;
+    // The CNN on the candidates that can still win only (the result row needs no other; the candidates entry reports an ML
+    // score for every candidate and scores them all).  Either way no item of the CNN is split: a patch's logit then does not
+    // depend on how many patches run beside it, and the rows of both entries, pruned or not, are equal bit for bit.
+    const bool prune = use_cnn && !cands && h->opt_cnn_prune && lg_cnn_counts_on_device(&h->cnn);
+    h->last_scored = use_cnn ? (long long)B * P.top_k : 0;
+    h->last_scored_subs = 0;
     // all eight planes are needed when the CNN rescoring runs; otherwise only distance + traditional
     for (int i = 0; i < LG_NUM_MAPS; i++)
         if (!pl.maps[i] && (use_cnn || i == LG_MAP_DISTANCE || i == LG_MAP_TRADITIONAL)) {
@@ -1290,13 +1338,20 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         const int off = k * SB, n = std::min(SB, B - off);
         if (piped) LG_HIP(h, hipStreamWaitEvent(sM, EV(k, 4), 0));
         if (use_cnn) {
+            const int32_t* list = prune ? h->surv_list + (size_t)off * K : nullptr;
+            const int32_t* count = prune ? h->surv_count + k : nullptr;
+            if (prune) {
+                ProfScope ps(h, "survivors", sM);
+                lg_launch_survivors(h->surv_keep + off, n, K, h->surv_list + (size_t)off * K, h->surv_slot + (size_t)off * K,
+                                    h->surv_count + k, sM);
+            }
             {
                 ProfScope ps(h, "gather", sM);
                 const float* mp[LG_NUM_MAPS];
                 for (int i = 0; i < LG_NUM_MAPS; i++) mp[i] = pl.maps[i] ? pl.maps[i] + off * px : nullptr;
                 lg_launch_gather(depth + off * px, mask + off * px, mp, pl.sparse ? h->tile_state + (size_t)off * tiles : nullptr,
                                  P.flat_scale, n, H, W, K, h->cand_xy + (size_t)off * K * 2,
-                                 h->cand_n + off, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, sM);
+                                 h->cand_n + off, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, sM, list, count);
             }
             std::string err;
             hipStream_t sC = sM;
@@ -1307,7 +1362,8 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
             }
             {
                 ProfScope ps(h, "cnn", sC);
-                int r2 = lg_cnn_run(&h->cnn, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, n * K, h->logits + (size_t)off * K, sC, &err);
+                int r2 = lg_cnn_run(&h->cnn, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, n * K, h->logits + (size_t)off * K, sC, &err,
+                                    false, count);
                 if (r2) return fail(h, r2, err.c_str());
             }
             if (h->s_cnn) {
@@ -1357,7 +1413,8 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
             lg_launch_topk(pl.maps[LG_MAP_TRADITIONAL] + off * px, pl.valid + off * px, depth + off * px,
                            h->tilekeys + (size_t)off * tiles, pl.sparse ? h->tile_state + (size_t)off * tiles : nullptr,
                            P.flat_scale, P.w_flat, true, n, H, W, K, P.nms_min_distance,
-                           h->cand_xy + (size_t)off * K * 2, h->cand_n + off, h->cand_info + (size_t)off * K * 2, sT);
+                           h->cand_xy + (size_t)off * K * 2, h->cand_n + off, h->cand_info + (size_t)off * K * 2, sT,
+                           prune ? h->surv_keep + off : nullptr, P.mask_is_bool);
         }
         if (trace && !piped) hipEventRecord(tev[3], s);   // after top-k
         if (piped) LG_HIP(h, hipEventRecord(EV(k, 4), sT));
@@ -1365,6 +1422,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     }
     rc = enq_G(nsub - 1);
     if (rc) return rc;
+    if (prune) h->last_scored_subs = nsub;
     if (trace && !piped) hipEventRecord(tev[4], s);       // after gather + CNN
     if (piped) {  // join: the caller's stream continues after every internal stream
         for (hipStream_t q : {sD[0], sD[1], sM, sT}) {
@@ -1379,6 +1437,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         LgFinishArgs fa;
         memset(&fa, 0, sizeof(fa));
         fa.cand_n = h->cand_n; fa.cand_xy = h->cand_xy; fa.cand_info = h->cand_info; fa.logits = h->logits;
+        fa.slot = prune ? h->surv_slot : nullptr; fa.slot_frames = SB;
         fa.fp = h->fp_dev; fa.bits = h->bits; fa.out = h->res_dev;
         fa.B = B; fa.H = H; fa.W = W; fa.WW = pl.WW; fa.K = K; fa.use_cnn = use_cnn ? 1 : 0; fa.mask_is_bool = P.mask_is_bool;
         fa.cx = P.cx; fa.cy = P.cy; fa.f = P.f;

@@ -48,7 +48,12 @@ int lg_cnn_upload(LgCnn* c, const lg_cnn_weights* w, std::string* err);
 void lg_cnn_free(LgCnn* c);
 // patches: dense [N][9][32][32] (haloed_in = false) or haloed planes [N][12][34][36] (planes 9..11 and all halos zero) (what lg_select_grasp's
 // gather writes directly; lg_cnn_halo_patch_floats() floats per patch)
-int lg_cnn_run(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err);
+// allow_split = false: no item of lg_wino4_kernel is split along the input channels, so a patch's logit does not depend on the
+// number of patches of the call.  n_dev (device; needs haloed_in and lg_cnn_counts_on_device): the call runs on the first *n_dev
+// of the N patch slots only -- N bounds the workspace, the grids and the slices; the logits of the other slots are not written.
+int lg_cnn_run(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err,
+               bool allow_split = true, const int* n_dev = nullptr);
+bool lg_cnn_counts_on_device(const LgCnn* c);
 size_t lg_cnn_halo_patch_floats(void);
 // after a synchronisation of the stream a forward ran on: true (once) if a split item of it gave up waiting for its parts
 bool lg_cnn_take_error(LgCnn* c);

@@ -574,8 +574,9 @@ __device__ __forceinline__ void lg_lds_wait2(lg_f32x4& a, lg_f32x4& b) {
 //   "roles" in the kernel): one transforms, the other issues the DMA transfers; ONE barrier per chunk.
 template <int CIN, int COUT, int WI, bool POOL, bool OUT_HALO, bool COB_MAJOR, bool SPLIT>
 __global__ __launch_bounds__(512) void lg_wino4_kernel(const float* __restrict__ in, const float* __restrict__ U4,
-                                                       const float* __restrict__ bias, float* __restrict__ out, int N, int ntb,
-                                                       float* __restrict__ kpart, unsigned* __restrict__ kflag, unsigned* __restrict__ kerr) {
+                                                       const float* __restrict__ bias, float* __restrict__ out, int N_host, int ntb_host,
+                                                       float* __restrict__ kpart, unsigned* __restrict__ kflag, unsigned* __restrict__ kerr,
+                                                       const int* __restrict__ n_dev, int n_off) {
     constexpr int KC = 4;
     constexpr int TC = WI / 4, TP = TC * TC;               // tile columns, tiles per patch
     constexpr int PB = TP >= 32 ? 1 : 32 / TP;             // patches per item
@@ -617,6 +618,11 @@ __global__ __launch_bounds__(512) void lg_wino4_kernel(const float* __restrict__
 
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    // Patch count: the launcher's, or -- n_dev: a count the device produced in front of this launch (the survivors of
+    // lg_select_grasp) -- what of *n_dev lies in this slice [n_off, n_off + N_host).  The item plan below follows from N, ntb
+    // and the grid alone, so a grid sized for N_host walks the items of the smaller N and its other workgroups leave at once.
+    const int N = n_dev ? max(0, min(*n_dev - n_off, N_host)) : N_host;
+    const int ntb = n_dev ? (TP >= 32 ? N * BPP : (N + PB - 1) / PB) : ntb_host;
     // XCD-aware item order (workgroups b, b + 8, ... share an XCD and its L2).  XCD x owns the tile blocks 8 * local + x and all
     // NCB channel blocks of them, as a list of ntbx * NCB items; its gx workgroups take list positions j, j + gx, j + 2 gx, ...
     // so at any time they work on neighbouring positions.  Small U (fits L2 beside the inputs): channel block fastest, the NCB
@@ -1144,10 +1150,12 @@ __global__ __launch_bounds__(256) void lg_head_kernel(const float* __restrict__ 
                                                       const float* __restrict__ b0, const float* __restrict__ w1,
                                                       const float* __restrict__ b1, const float* __restrict__ w2,
                                                       const float* __restrict__ b2, const float* __restrict__ w3,
-                                                      const float* __restrict__ b3, float* __restrict__ logits) {
+                                                      const float* __restrict__ b3, float* __restrict__ logits,
+                                                      const int* __restrict__ n_dev, int n_off) {
     __shared__ float s_a[4][32];
     __shared__ float s_f[512], s_g[512];
     const int n = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (n_dev && n >= *n_dev - n_off) return;   // (a patch count the device produced: the grid covers its upper bound)
     const float* hn = h + (size_t)n * Cp * npix;
     float v[2][16];
 #pragma unroll
@@ -1304,7 +1312,8 @@ static int lg_w4_num_cu() {
 constexpr size_t LG_W4_KPART_FLOATS = 16 * 512 * 4;   // partial outputs of one workgroup (lg_wino4_kernel, split items)
 
 bool launch_wino4_rt(int cin, int cout, int wi, bool pool, bool out_halo, const float* in, const float* U4, const float* bias,
-                     float* out, int N, int max_cus, float* kpart, unsigned* kflag, unsigned* kerr, hipStream_t s) {
+                     float* out, int N, int max_cus, float* kpart, unsigned* kflag, unsigned* kerr, hipStream_t s,
+                     bool allow_split = true, const int* n_dev = nullptr, int n_off = 0) {
     const int tp = (wi / 4) * (wi / 4);
     const int ntb = tp >= 32 ? N * (tp / 32) : (N + 32 / tp - 1) / (32 / tp);
     // persistent: one 512-thread workgroup per CU (140-156 KB of LDS each)
@@ -1321,7 +1330,9 @@ bool launch_wino4_rt(int cin, int cout, int wi, bool pool, bool out_halo, const 
         const int cap = std::min(std::min(gx / rem, 8), cin / 16);
         while (2 * P <= cap) P *= 2;
     }
-    const bool split = P > 1 && (cin / 4) * (P - 1) / P >= 26;
+    // allow_split = false: every item runs whole, so a patch's outputs do not depend on how many patches run beside it
+    // (lg_select_grasp: the rows of its two entries and of its pruned and unpruned CNN pass are equal bit for bit)
+    const bool split = allow_split && !n_dev && P > 1 && (cin / 4) * (P - 1) / P >= 26;
     if (items8 < gx) gx = (int)items8 * (split ? P : 1);
     const int grid = 8 * gx;
 #define X(CI, CO, W_, P_)                                                                                             \
@@ -1329,11 +1340,11 @@ bool launch_wino4_rt(int cin, int cout, int wi, bool pool, bool out_halo, const 
         constexpr bool CM = 36LL * CI * CO * 4 > 3 * 1024 * 1024;                                                     \
         constexpr bool CAN = CI >= 128;   /* (cin / 4 * 7 / 8 >= 26) */                                              \
         if (out_halo) {                                                                                               \
-            if (CAN && split) hipLaunchKernelGGL((lg_wino4_kernel<CI, CO, W_, P_, true, CM, CAN>), dim3(grid), dim3(512), 0, s, in, U4, bias, out, N, ntb, kpart, kflag, kerr); \
-            else hipLaunchKernelGGL((lg_wino4_kernel<CI, CO, W_, P_, true, CM, false>), dim3(grid), dim3(512), 0, s, in, U4, bias, out, N, ntb, kpart, kflag, kerr); \
+            if (CAN && split) hipLaunchKernelGGL((lg_wino4_kernel<CI, CO, W_, P_, true, CM, CAN>), dim3(grid), dim3(512), 0, s, in, U4, bias, out, N, ntb, kpart, kflag, kerr, n_dev, n_off); \
+            else hipLaunchKernelGGL((lg_wino4_kernel<CI, CO, W_, P_, true, CM, false>), dim3(grid), dim3(512), 0, s, in, U4, bias, out, N, ntb, kpart, kflag, kerr, n_dev, n_off); \
         } else {                                                                                                      \
-            if (CAN && split) hipLaunchKernelGGL((lg_wino4_kernel<CI, CO, W_, P_, false, CM, CAN>), dim3(grid), dim3(512), 0, s, in, U4, bias, out, N, ntb, kpart, kflag, kerr); \
-            else hipLaunchKernelGGL((lg_wino4_kernel<CI, CO, W_, P_, false, CM, false>), dim3(grid), dim3(512), 0, s, in, U4, bias, out, N, ntb, kpart, kflag, kerr); \
+            if (CAN && split) hipLaunchKernelGGL((lg_wino4_kernel<CI, CO, W_, P_, false, CM, CAN>), dim3(grid), dim3(512), 0, s, in, U4, bias, out, N, ntb, kpart, kflag, kerr, n_dev, n_off); \
+            else hipLaunchKernelGGL((lg_wino4_kernel<CI, CO, W_, P_, false, CM, false>), dim3(grid), dim3(512), 0, s, in, U4, bias, out, N, ntb, kpart, kflag, kerr, n_dev, n_off); \
         }                                                                                                             \
         return true;                                                                                                  \
     }
@@ -1589,22 +1600,31 @@ static int ensure_act(LgCnn* c, int N, hipStream_t s, std::string* err) {
     return LG_OK;
 }
 
-static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err);
+static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err,
+                            bool allow_split, const int* n_dev, int n_off);
+
+// every layer on lg_wino4_kernel: the kernels that can take their patch count from device memory
+bool lg_cnn_counts_on_device(const LgCnn* c) {
+    return c->loaded && !c->use_f23 && (c->wino_mask & 1) && (!c->standard || c->wino_mask == 0x3f);
+}
 
 // Slices bound the activation workspace (0.8 MB per patch for the standard model): at most 8192 patches at a time.
-int lg_cnn_run(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err) {
+int lg_cnn_run(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err,
+               bool allow_split, const int* n_dev) {
     if (!c->loaded) { *err = "no model"; return LG_ERR_NO_MODEL; }
+    if (n_dev && !(haloed_in && lg_cnn_counts_on_device(c))) { *err = "lg_cnn_run: no device-side patch count on this path"; return LG_ERR_UNSUPPORTED; }
     const int max_slice = 8192;
     const size_t pstride = haloed_in ? lg_cnn_halo_patch_floats() : (size_t)9 * 1024;
     for (int off = 0; off < N; off += max_slice) {
         const int n = N - off < max_slice ? N - off : max_slice;
-        int rc = lg_cnn_run_slice(c, patches + (size_t)off * pstride, haloed_in, n, logits + off, s, err);
+        int rc = lg_cnn_run_slice(c, patches + (size_t)off * pstride, haloed_in, n, logits + off, s, err, allow_split, n_dev, off);
         if (rc) return rc;
     }
     return LG_OK;
 }
 
-static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err) {
+static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err,
+                            bool allow_split, const int* n_dev, int n_off) {
     int rc = ensure_act(c, N, s, err);
     if (rc) return rc;
     const float* x = patches;
@@ -1614,7 +1634,7 @@ static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int 
     }
     // layer 0: the F(4x4,3x3) kernel on 12 input planes (3 chunks); the direct 9-channel kernel with LG_CNN_DIRECT / _F23 / mask bit 0 clear
     if (!c->use_f23 && (c->wino_mask & 1) &&
-        launch_wino4_rt(12, c->layers[0].coutp, 32, false, true, x, c->uwino4[0], c->bconv[0], c->act[0], N, c->max_cus, c->kpart, c->kflag, c->kerr_dev, s)) {
+        launch_wino4_rt(12, c->layers[0].coutp, 32, false, true, x, c->uwino4[0], c->bconv[0], c->act[0], N, c->max_cus, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off)) {
         // (a shape the F(4x4) table lacks falls through to the direct kernel instead of leaving act[0] unwritten)
     } else if (c->layers[0].coutp == 64) launch_conv0<64>(x, c, c->act[0], N, s);
     else launch_conv0<128>(x, c, c->act[0], N, s);
@@ -1626,7 +1646,7 @@ static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int 
         const RtLayer& l = c->layers[L];                                                                            \
         if (!(wmask & (1 << L))) launch_conv<L, KC, PP, CP>(cur, c, c->act[L], N, s);                               \
         else if (c->use_f23) launch_wino_rt(l.cinp, l.coutp, l.wi, l.pool, L != 5, cur, c->uwino[L], c->bconv[L], c->act[L], N, s); \
-        else launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L != 5, cur, c->uwino4[L], c->bconv[L], c->act[L], N, c->max_cus, c->kpart, c->kflag, c->kerr_dev, s); \
+        else launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L != 5, cur, c->uwino4[L], c->bconv[L], c->act[L], N, c->max_cus, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off); \
         cur = c->act[L];                                                                                            \
     } while (0)
         LG_LAYER(1, 8, 4, 1);   // 64 -> 64, pool -> 16x16
@@ -1639,7 +1659,7 @@ static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int 
         for (int L = 1; L < c->n_layers; L++) {
             const RtLayer& l = c->layers[L];
             const bool okl = c->use_f23 ? launch_wino_rt(l.cinp, l.coutp, l.wi, l.pool, L + 1 < c->n_layers, cur, c->uwino[L], c->bconv[L], c->act[L], N, s)
-                                        : launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L + 1 < c->n_layers, cur, c->uwino4[L], c->bconv[L], c->act[L], N, c->max_cus, c->kpart, c->kflag, c->kerr_dev, s);
+                                        : launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L + 1 < c->n_layers, cur, c->uwino4[L], c->bconv[L], c->act[L], N, c->max_cus, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off);
             if (!okl) {
                 *err = "lg_cnn_forward: unsupported layer shape";
                 return LG_ERR_UNSUPPORTED;
@@ -1651,7 +1671,7 @@ static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int 
     if (c->F == F_ && c->npix == NP_) {                                                                                \
         hipLaunchKernelGGL((lg_head_kernel<F_, NP_>), dim3(N), dim3(256), 0, s, cur, c->Fp, c->att_type, c->att_w, c->att_b, \
                            c->ca_w1, c->ca_b1, c->ca_w2, c->ca_b2, c->fcw[0], c->fcb[0], c->fcw[1], c->fcb[1], c->fcw[2],  \
-                           c->fcb[2], c->fcw[3], c->fcb[3], logits);                                                   \
+                           c->fcb[2], c->fcw[3], c->fcb[3], logits, n_dev, n_off);                                                 \
         return LG_OK;                                                                                                  \
     }
     LG_HEAD(256, 16) LG_HEAD(128, 16) LG_HEAD(512, 16) LG_HEAD(512, 4)

@@ -1894,14 +1894,14 @@ __device__ inline bool lg_ml_rescore(const LgFinishArgs& a, int b, int i, int x,
                                      double* conf_out, double* comb_out) {
 #pragma clang fp contract(off)
     if (a.mask_is_bool && (x < 16 || y < 16 || x + 16 > a.W || y + 16 > a.H)) return false;
-    const double logit = (double)a.logits[(size_t)b * a.K + i];
-    const double sg = 1.0 / (1.0 + exp(-logit));
-    const double ml = tanh(sg * 3.0) * 0.5 + 0.5;               // :133-136
-    const double conf = 1.0 - fabs(ml - 0.5) * 2.0;              // :222
-    const double wml = fmin(0.3, conf * 0.6);                    // :223
-    *comb_out = (1.0 - wml) * trad + wml * ml;                   // :226
-    *ml_out = ml;
-    *conf_out = conf;
+    // (a.slot: the CNN ran on the survivors only; a candidate that cannot beat candidate 0 has no patch and is never taken)
+    int j = b * a.K + i;
+    if (a.slot) {
+        j = a.slot[j];
+        if (j < 0) return false;
+        j += (b / a.slot_frames) * a.slot_frames * a.K;
+    }
+    lg_ml_combine((double)a.logits[j], trad, ml_out, conf_out, comb_out);
     return true;
 }
 
@@ -2160,7 +2160,8 @@ __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restr
                                                             float w_flat, int H,
                                                             int W, int tiles_x, int tiles_y, int k, int md,
                                                             int32_t* __restrict__ out_xy, int32_t* __restrict__ out_n,
-                                                            float* __restrict__ out_info) {
+                                                            float* __restrict__ out_info,
+                                                            unsigned long long* __restrict__ keep, int mask_is_bool) {
     __shared__ unsigned long long s_keys[LG_MAX_TILES];
     __shared__ uint8_t s_state[LG_MAX_TILES];   // 1: the tile's planes were written (every tile when tile_state is null)
     __shared__ unsigned long long s_best;
@@ -2328,25 +2329,85 @@ __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restr
     if (t == 0) out_n[frame] = n;
     // traditional score + depth at the picks, gathered once after the walk (a dependent global load inside
     // every round would sit on the critical path of the next arg-max)
+    float tr = 0.0f;
     if (out_info && t < n) {
         const size_t o = fo + (size_t)s_cy[t] * W + s_cx[t];
         const int tile = (s_cy[t] / LG_TH) * tiles_x + s_cx[t] / LG_TW;
-        out_info[((size_t)frame * k + t) * 2 + 0] = s_state[tile] ? trad[o] : trad1;
+        tr = s_state[tile] ? trad[o] : trad1;
+        out_info[((size_t)frame * k + t) * 2 + 0] = tr;
         out_info[((size_t)frame * k + t) * 2 + 1] = depth ? depth[o] : 0.0f;
     }
+    // which candidates the CNN rescoring can still take (lg_finish_kernel's eligibility and lg_cnn_cannot_win against
+    // candidate 0, on the float32 scores written above): the first wave holds all n <= 64 of them
+    if (keep && out_info && t < 64) {
+        const float tr0 = __shfl(tr, 0, 64);
+        bool kp = false;
+        if (t < n && n > 1) {
+            const int x = s_cx[t], y = s_cy[t];
+            const bool border = mask_is_bool && (x < 16 || y < 16 || x + 16 > W || y + 16 > H);
+            kp = !border && !lg_cnn_cannot_win((double)tr, (double)tr0);
+        }
+        const unsigned long long m = __ballot(kp);
+        if (t == 0) keep[frame] = m;
+    }
+}
+
+// ============================================================================ survivor list
+// keep[b] (lg_topk_kernel) -> the compact list of (frame, candidate) pairs that go through the CNN, in (frame, candidate)
+// order, its length and the map back.  One 1024-thread workgroup, thread = frame (frames t, t + 1024, ... in rounds with a
+// running base): popcount, exclusive scan over the workgroup, then every thread writes its frame's K map entries and its list
+// entries.  No atomics: the order does not depend on timing.
+__global__ __launch_bounds__(1024) void lg_survivors_kernel(const unsigned long long* __restrict__ keep, int B, int K,
+                                                            int32_t* __restrict__ list, int32_t* __restrict__ slot,
+                                                            int32_t* __restrict__ count) {
+    __shared__ int s_wave[16];
+    __shared__ int s_base;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) s_base = 0;
+    __syncthreads();
+    for (int b0 = 0; b0 < B; b0 += 1024) {
+        const int b = b0 + t;
+        const unsigned long long m = b < B ? keep[b] : 0ull;
+        const int c = __popcll(m);
+        int incl = c;   // inclusive scan inside the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += v;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int pos = s_base + incl - c;
+        for (int w = 0; w < wave; w++) pos += s_wave[w];
+        __syncthreads();   // everyone has read s_base and s_wave
+        if (t == 1023) s_base = pos + c;
+        if (b < B) {
+            for (int i = 0; i < K; i++) {
+                const bool on = (m >> i) & 1ull;
+                slot[(size_t)b * K + i] = on ? pos : -1;
+                if (on) list[pos++] = b * K + i;
+            }
+        }
+        __syncthreads();
+    }
+    if (t == 0) *count = s_base;
+}
+
+void lg_launch_survivors(const unsigned long long* keep, int B, int K, int32_t* list, int32_t* slot, int32_t* count, hipStream_t s) {
+    hipLaunchKernelGGL(lg_survivors_kernel, dim3(1), dim3(1024), 0, s, keep, B, K, list, slot, count);
 }
 
 void lg_launch_topk(const float* trad, const uint8_t* valid, const float* depth, unsigned long long* tilekeys,
                     const uint8_t* tile_state, float flat_scale, float w_flat,
                     bool keys_ready, int B, int H, int W, int k, int min_dist, int32_t* out_xy, int32_t* out_n,
-                    float* out_info, hipStream_t s) {
+                    float* out_info, hipStream_t s, unsigned long long* keep, int mask_is_bool) {
     int tiles_x = (W + LG_TW - 1) / LG_TW, tiles_y = (H + LG_TH - 1) / LG_TH;
     if (!keys_ready)   // (keys from the planes themselves: every plane written)
         hipLaunchKernelGGL(lg_tilekeys_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, s, trad, valid, tilekeys, H, W,
                            tiles_x, tiles_y);
     hipLaunchKernelGGL(lg_topk_kernel, dim3(B), dim3(LG_TOPK_T), 0, s, trad, valid, depth, tilekeys,
                        keys_ready ? tile_state : nullptr, flat_scale, w_flat, H, W, tiles_x, tiles_y, k, min_dist, out_xy,
-                       out_n, out_info);
+                       out_n, out_info, keep, mask_is_bool);
 }
 
 // ============================================================================ 9-channel patch gather
@@ -2364,13 +2425,21 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
                                                         const uint8_t* __restrict__ mask, LgGatherMaps maps,
                                                         const uint8_t* __restrict__ tile_state, float flat_scale, int H,
                                                         int W, int k, const int32_t* __restrict__ xy,
-                                                        const int32_t* __restrict__ n, float* __restrict__ patches) {
+                                                        const int32_t* __restrict__ n, float* __restrict__ patches,
+                                                        const int32_t* __restrict__ list, const int32_t* __restrict__ count) {
     __shared__ float s_mn[4], s_mx[4];
     __shared__ int s_mat[3][2];   // state of the <= 3 x 2 tiles under the window (rows ty_lo.., columns tx_lo..)
     constexpr int PL = HALO ? 34 * 36 : 1024, RP = HALO ? 36 : 32, O0 = HALO ? 37 : 0;
-    const int ci = blockIdx.x, frame = blockIdx.y;
+    int ci = blockIdx.x, frame = blockIdx.y;
     const int t = threadIdx.x;
-    float* outp = patches + ((size_t)frame * k + ci) * (HALO ? 12 : 9) * PL + O0;   // haloed patches carry 3 more (zero) planes
+    const int j = frame * k + ci;   // patch slot
+    if (list) {                     // survivors only: slot j takes list entry j (a candidate below n[frame]), the rest is left alone
+        if (j >= *count) return;
+        const int e = list[j];
+        frame = e / k;
+        ci = e - frame * k;
+    }
+    float* outp = patches + (size_t)j * (HALO ? 12 : 9) * PL + O0;   // haloed patches carry 3 more (zero) planes
     if (ci >= n[frame]) {
         for (int c = 0; c < 9; c++)
             for (int i = t; i < 1024; i += 256) outp[c * PL + (i >> 5) * RP + (i & 31)] = 0.0f;
@@ -2447,15 +2516,15 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
 
 void lg_launch_gather(const float* depth, const uint8_t* mask, const float* const* maps_host, const uint8_t* tile_state,
                       float flat_scale, int B, int H, int W, int k, const int32_t* xy, const int32_t* n, float* patches,
-                      bool haloed, hipStream_t s) {
+                      bool haloed, hipStream_t s, const int32_t* list, const int32_t* count) {
     LgGatherMaps gm;
     for (int i = 0; i < 7; i++) gm.p[i] = maps_host[i];
     if (haloed)
         hipLaunchKernelGGL(lg_gather_kernel<true>, dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W, k,
-                           xy, n, patches);
+                           xy, n, patches, list, count);
     else
         hipLaunchKernelGGL(lg_gather_kernel<false>, dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W,
-                           k, xy, n, patches);
+                           k, xy, n, patches, list, count);
 }
 
 // ============================================================================ training-sample harvesting

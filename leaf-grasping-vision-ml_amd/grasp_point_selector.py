@@ -192,6 +192,16 @@ class GraspPointSelector:
             raise RuntimeError(lib.lg_last_error(self._h).decode())
         return bool(form[0]), bool(form[1])
 
+    def cnn_scored(self):
+        """Inspection: how many patches the last select_grasp_point(s) / select_grasp_candidates call put through the CNN --
+        the candidates that could still beat candidate 0 (lg_cnn_candidate_cannot_win), or every one (B * top_k) for the
+        candidates entry and with LG_CNN_PRUNE=0."""
+        n = C.c_int64()
+        rc = lib.lg_debug_cnn_scored(self._h, C.byref(n))
+        if rc != 0:
+            raise RuntimeError(lib.lg_last_error(self._h).decode())
+        return int(n.value)
+
     def _calculate_all_scores(self, leaf_mask_np, depth_tensor, image_processor=None):
         """Reference signature (:256): numpy uint8 mask in, dict of numpy planes out."""
         out, _, _ = self.score_maps(leaf_mask_np, depth_tensor, image_processor)
