@@ -361,6 +361,22 @@ int lg_debug_dt_form(lg_handle h, int frame, int32_t form[2]);
 /* *patches = how many patches the last lg_select_grasp* call on this handle put through the CNN (0 without a model;
    B * top_k where every candidate is scored: lg_select_grasp_candidates*, LG_CNN_PRUNE=0).  Synchronises the device. */
 int lg_debug_cnn_scored(lg_handle h, int64_t* patches);
+/* The CNN pass of the last lg_select_grasp* call on this handle, patch by patch.  The call's B frames run as *n_sub
+   sub-batches of *sub_frames frames (one sub-batch of B frames unless LG_SUBBATCH was set at lg_create); sub-batch k owns
+   the entries [k * *sub_frames * top_k, ...) of list, slot and logits, one per candidate slot of its frames, and every index
+   below counts from the sub-batch's first entry:
+     counts[k]   patches of sub-batch k that went through the CNN (counts_cap >= *n_sub entries);
+     list[j]     j < counts[k]: frame * top_k + candidate of patch j (frame-major, candidates ascending); -1 past the count;
+     slot[i]     candidate slot i = frame * top_k + candidate -> its patch, -1: pruned (no patch, no logit);
+     logits[j]   the logit of patch j; entries past the count are whatever the buffer held before the call.
+   *n_slots = B * top_k, the entries written to each of list, slot and logits (cap >= *n_slots entries each).  Where every
+   candidate is scored (lg_select_grasp_candidates*, LG_CNN_PRUNE=0) this is the identity: counts[k] = its frames * top_k,
+   list[j] = slot[j] = j.  Synchronises the device and launches nothing.  Size query: counts, list, slot and logits all NULL
+   with counts_cap = cap = 0 sets *sub_frames, *n_sub and *n_slots, copies nothing and returns LG_OK.  LG_ERR_INVALID: any
+   other NULL pointer, arrays too small, or no such call with a model loaded since the workspace was last (re)allocated;
+   LG_ERR_BUSY: a call in flight. */
+int lg_debug_cnn_survivors(lg_handle h, int32_t* sub_frames, int32_t* n_sub, int32_t* counts, int32_t counts_cap,
+                           int32_t* list, int32_t* slot, float* logits, int64_t cap, int64_t* n_slots);
 
 /* ---- GraspPointCNN training step: one call = one iteration of the inner loop of
    scripts/train_model.py:247-265 (zero_grad, forward in train mode, BCEWithLogitsLoss(pos_weight), backward,

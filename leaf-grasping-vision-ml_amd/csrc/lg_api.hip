@@ -75,6 +75,10 @@ struct lg_ctx {
     bool opt_cnn_prune = true;                // LG_CNN_PRUNE=0: every candidate's patch goes through the CNN (A/B, tests)
     long long last_scored = 0;                // lg_debug_cnn_scored: patches of the last call, when the host knows them;
     int last_scored_subs = 0;                 //   > 0: the sum of surv_count[0 .. last_scored_subs) instead
+    // lg_debug_cnn_survivors: the shape of the last lg_select_grasp* call that ran the CNN (last_cnn_B = 0: none) -- frames,
+    // top_k, frames per sub-batch, and whether the pass was pruned (the survivor buffers then hold that call's lists)
+    int last_cnn_B = 0, last_cnn_K = 0, last_cnn_SB = 0;
+    bool last_cnn_pruned = false;
     lg_grasp_result* res_dev = nullptr;       // [B] result rows written by lg_finish_kernel
     lg_grasp_result* res_host = nullptr;      // pinned copy
     // lg_select_grasp_candidates*: [cand_rows_cap] rows of lg_candidates_kernel and their pinned copy, allocated on the first such
@@ -203,7 +207,7 @@ void free_ws(lg_ctx* h) {
     F(h->ws_valid); F(h->cand_xy); F(h->cand_n); F(h->cand_info); F(h->patches); F(h->logits);
     F(h->surv_keep); F(h->surv_list); F(h->surv_slot); F(h->surv_count);
     h->surv_keep = nullptr; h->surv_list = h->surv_slot = h->surv_count = nullptr;
-    h->last_scored = 0; h->last_scored_subs = 0;
+    h->last_scored = 0; h->last_scored_subs = 0; h->last_cnn_B = 0;
     auto HF = [](void* p) { if (p) hipHostFree(p); };
     HF(h->fp_host); HF(h->bits_host); HF(h->win_host); HF(h->res_host);
     F(h->res_dev);
@@ -507,6 +511,46 @@ int lg_debug_cnn_scored(lg_handle h, int64_t* patches) {
         for (int32_t v : c) n += v;
     }
     *patches = n;
+    return LG_OK;
+}
+
+int lg_debug_cnn_survivors(lg_handle h, int32_t* sub_frames, int32_t* n_sub, int32_t* counts, int32_t counts_cap,
+                           int32_t* list, int32_t* slot, float* logits, int64_t cap, int64_t* n_slots) {
+    if (!h || !sub_frames || !n_sub || !n_slots) return LG_ERR_INVALID;
+    const bool query = !counts && !list && !slot && !logits && counts_cap == 0 && cap == 0;   // sizes only
+    if (!query && (!counts || !list || !slot || !logits)) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    const int B = h->last_cnn_B, K = h->last_cnn_K, SB = h->last_cnn_SB;
+    if (B <= 0 || K <= 0 || SB <= 0 || B > h->capB || K > h->capK || !h->logits || !h->surv_count)
+        return fail(h, LG_ERR_INVALID, "lg_debug_cnn_survivors: no lg_select_grasp call with the CNN on this workspace");
+    const int nsub = (B + SB - 1) / SB;
+    const size_t total = (size_t)B * K;
+    *sub_frames = SB; *n_sub = nsub; *n_slots = (int64_t)total;
+    if (query) return LG_OK;
+    if (counts_cap < nsub || cap < 0 || (size_t)cap < total)
+        return fail(h, LG_ERR_INVALID, "lg_debug_cnn_survivors: output arrays too small");
+    hipSetDevice(h->device);
+    hipDeviceSynchronize();
+    if (hipMemcpy(logits, h->logits, sizeof(float) * total, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(h, LG_ERR_HIP, "lg_debug_cnn_survivors: copy failed");
+    if (h->last_cnn_pruned) {
+        if (hipMemcpy(counts, h->surv_count, sizeof(int32_t) * nsub, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(list, h->surv_list, sizeof(int32_t) * total, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(slot, h->surv_slot, sizeof(int32_t) * total, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(h, LG_ERR_HIP, "lg_debug_cnn_survivors: copy failed");
+    }
+    for (int k = 0; k < nsub; k++) {
+        const int off = k * SB, n = std::min(SB, B - off);
+        int32_t* const l = list + (size_t)off * K;
+        const int32_t slots = n * K;
+        if (!h->last_cnn_pruned) {   // every candidate has a patch, in its own place
+            counts[k] = slots;
+            for (int32_t j = 0; j < slots; j++) l[j] = slot[(size_t)off * K + j] = j;
+        } else {                     // (the device wrote the first counts[k] entries of the list only)
+            const int32_t c = std::max(0, std::min(counts[k], slots));
+            for (int32_t j = c; j < slots; j++) l[j] = -1;
+        }
+    }
     return LG_OK;
 }
 
@@ -1297,6 +1341,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     const bool prune = use_cnn && !cands && h->opt_cnn_prune && lg_cnn_counts_on_device(&h->cnn);
     h->last_scored = use_cnn ? (long long)B * P.top_k : 0;
     h->last_scored_subs = 0;
+    h->last_cnn_B = 0;
     // all eight planes are needed when the CNN rescoring runs; otherwise only distance + traditional
     for (int i = 0; i < LG_NUM_MAPS; i++)
         if (!pl.maps[i] && (use_cnn || i == LG_MAP_DISTANCE || i == LG_MAP_TRADITIONAL)) {
@@ -1461,6 +1506,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     if (use_cnn && lg_cnn_take_error(&h->cnn)) return fail(h, LG_ERR_HIP, "lg_select_grasp: a split CNN item did not receive its parts");
     memcpy(results, h->res_host, sizeof(lg_grasp_result) * B);
     if (cands) memcpy(cands, h->cand_rows_host, sizeof(lg_grasp_candidate) * B * K);
+    if (use_cnn) { h->last_cnn_B = B; h->last_cnn_K = K; h->last_cnn_SB = SB; h->last_cnn_pruned = prune; }
     if (trace && !piped) {
         float a[5] = {0};
         for (int i = 1; i <= 4; i++) hipEventElapsedTime(&a[i], tev[0], tev[i]);

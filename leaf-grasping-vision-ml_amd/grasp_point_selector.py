@@ -202,6 +202,29 @@ class GraspPointSelector:
             raise RuntimeError(lib.lg_last_error(self._h).decode())
         return int(n.value)
 
+    def cnn_survivors(self):
+        """Inspection: the CNN pass of the last select_grasp_point(s) / select_grasp_candidates call, patch by patch
+        (lg_debug_cnn_survivors).  Returns a dict: sub_frames, n_sub (the call's sub-batches; one of B frames by default),
+        counts [n_sub] (patches each sub-batch put through the CNN), and list, slot (int32) and logits (float32), each
+        [B * top_k] with sub-batch k's entries from k * sub_frames * top_k on and indices counted from there: list[j] = frame *
+        top_k + candidate of patch j (-1 past the count), slot[frame * top_k + candidate] = its patch or -1 (pruned), logits[j]
+        = the logit of patch j (stale past the count).  The identity where every candidate is scored."""
+        sub_frames, n_sub, n_slots = C.c_int32(), C.c_int32(), C.c_int64()
+        i32 = C.POINTER(C.c_int32)
+        rc = lib.lg_debug_cnn_survivors(self._h, C.byref(sub_frames), C.byref(n_sub), None, 0, None, None, None, 0,
+                                        C.byref(n_slots))   # the sizes
+        if rc != 0:
+            raise RuntimeError(lib.lg_last_error(self._h).decode())
+        n = int(n_slots.value)
+        counts = np.zeros(int(n_sub.value), np.int32)
+        lst, slot, logits = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        rc = lib.lg_debug_cnn_survivors(self._h, C.byref(sub_frames), C.byref(n_sub), counts.ctypes.data_as(i32), counts.size,
+                                        lst.ctypes.data_as(i32), slot.ctypes.data_as(i32),
+                                        logits.ctypes.data_as(C.POINTER(C.c_float)), n, C.byref(n_slots))
+        if rc != 0:
+            raise RuntimeError(lib.lg_last_error(self._h).decode())
+        return dict(sub_frames=int(sub_frames.value), n_sub=int(n_sub.value), counts=counts, list=lst, slot=slot, logits=logits)
+
     def _calculate_all_scores(self, leaf_mask_np, depth_tensor, image_processor=None):
         """Reference signature (:256): numpy uint8 mask in, dict of numpy planes out."""
         out, _, _ = self.score_maps(leaf_mask_np, depth_tensor, image_processor)
