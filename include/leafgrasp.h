@@ -358,6 +358,18 @@ int lg_debug_dt_max(lg_handle h, int frame, uint32_t out[2], int32_t win[4]);
 /* form[0] = 1: d_in of that frame came from the row search (0: from the two sweeps); form[1] = 1: its d_out sweeps were
    skipped (the maximum provably lies on the frame border).  Which form a batch takes is decided on the device. */
 int lg_debug_dt_form(lg_handle h, int frame, int32_t form[2]);
+/* The near tiles of a frame on the host (no device, no handle), the code the device runs: the tiles (64 x 16 pixels) of the
+   score-plane kernel whose look at the mask can meet the mask's bounding box [bx0, bx1] x [by0, by1] (bx1 < bx0: empty) in an
+   H x W frame, halo = gaussian_size / 2 + 1.  They form a rectangle of the tile grid: rect = {tx_lo, tx_hi, ty_lo, ty_hi},
+   inclusive; returns their number, 0 with rect = {0, -1, 0, -1} when there is none, LG_ERR_INVALID for a bad argument.  Every
+   other tile is constant whatever the mask.  In sparse mode lg_select_grasp* launches the plane kernel on the near tiles only
+   (LG_FINAL_NEAR=0 at lg_create: on every tile, as lg_score_maps does). */
+int lg_near_tile_rect(int bx0, int bx1, int by0, int by1, int H, int W, int halo, int32_t rect[4]);
+/* off[0 .. B] = first entry of every frame's near tiles in the list the last lg_select_grasp* call on this handle launched its
+   plane kernel on (off[0] = 0, off[B] = the list's length; frame b has off[b + 1] - off[b] near tiles).  cap >= B + 1.
+   LG_ERR_INVALID when that call did not take the near launch (planes or validity taken back, LG_FINAL_NEAR=0, LG_SUBBATCH,
+   LG_NO_SKIP, LG_FINAL_PERSIST / LG_FINAL_TPW) or cap is too small.  Launches nothing. */
+int lg_debug_near_tiles(lg_handle h, int32_t* off, int cap);
 /* *patches = how many patches the last lg_select_grasp* call on this handle put through the CNN (0 without a model;
    B * top_k where every candidate is scored: lg_select_grasp_candidates*, LG_CNN_PRUNE=0).  Synchronises the device. */
 int lg_debug_cnn_scored(lg_handle h, int64_t* patches);

@@ -35,6 +35,13 @@ struct LgProfSlot {
     double total_ms = 0.0;
 };
 
+// list entries per workgroup of the near launch (lg_launch_final; LG_FINAL_NEAR=n overrides).  256 frames of 1080p, plane kernel
+// alone: 1 / 2 / 4 / 8 entries 0.275 / 0.273 / 0.305 / 0.328 ms (profiles/NOTES_near_tiles.md).  The launch applies at every batch
+// size: the enumeration kernel and its copy in front of the orientation kernel did not lengthen a call of 1 or 32 frames.
+#ifndef LG_FINAL_NEAR_TPW
+#define LG_FINAL_NEAR_TPW 1
+#endif
+
 struct lg_ctx {
     int device = 0;
     std::string err;
@@ -49,6 +56,11 @@ struct lg_ctx {
     uint32_t* tmp = nullptr;
     unsigned long long *bits = nullptr, *stem = nullptr, *tilekeys = nullptr;
     uint8_t* tile_state = nullptr;   // [B][tiles]: which tiles' planes lg_final_kernel wrote (sparse planes, Plan::sparse)
+    // near launch of lg_final_kernel (sparse planes): first list entry of every frame's near tiles, [B + 1], written by
+    // lg_near_tiles_kernel on the copy stream, and its pinned copy (read by enq_final, after the event the host waits for anyway)
+    int32_t* near_off = nullptr;
+    int32_t* near_off_host = nullptr;
+    int last_near_B = 0;             // lg_debug_near_tiles: frames of the last lg_select_grasp* call if it took the near launch, else 0
     uint32_t* maxfix = nullptr;
     LgDtBatch* dt_batch = nullptr;   // search-or-sweeps sums of a batch (lg_bbox_kernel)
     uint8_t* mask_ws = nullptr;      // lg_select_grasp_labels: the 0 / 1 mask it derives from the labels (grown on demand)
@@ -104,6 +116,8 @@ struct lg_ctx {
     bool opt_trace = false;      // LG_TRACE: per-call timeline on stderr
     int opt_no_skip = 0;         // LG_NO_SKIP=1: lg_final_kernel without the constant-tile fast path (dense-path roofline);
                                  //            =3: also without the wave-level off-leaf shortcut
+    int opt_final_near = LG_FINAL_NEAR_TPW;   // LG_FINAL_NEAR=0: lg_final_kernel walks every tile in sparse mode too (the launch before the
+                                 //            near launch; A/B, tests); =n: near launch with n list entries per workgroup
     bool opt_nt_stores = false;  // LG_NT_STORES: non-temporal plane stores (measured slower)
     int opt_side_tail = 1;         // LG_SIDE_TAIL=0: frame-border maxima + stem bits after the sweeps on the caller's stream (round 1); 1: on the
                                    // side stream behind the orientation kernel; 2: on a third stream
@@ -206,10 +220,12 @@ void free_ws(lg_ctx* h) {
     for (int i = 0; i < LG_NUM_MAPS; i++) { F(h->ws_maps_base[i]); h->ws_maps_base[i] = h->ws_maps[i] = nullptr; }
     F(h->ws_valid); F(h->cand_xy); F(h->cand_n); F(h->cand_info); F(h->patches); F(h->logits);
     F(h->surv_keep); F(h->surv_list); F(h->surv_slot); F(h->surv_count);
+    F(h->near_off); h->near_off = nullptr; h->last_near_B = 0;
     h->surv_keep = nullptr; h->surv_list = h->surv_slot = h->surv_count = nullptr;
     h->last_scored = 0; h->last_scored_subs = 0; h->last_cnn_B = 0;
     auto HF = [](void* p) { if (p) hipHostFree(p); };
-    HF(h->fp_host); HF(h->bits_host); HF(h->win_host); HF(h->res_host);
+    HF(h->fp_host); HF(h->bits_host); HF(h->win_host); HF(h->res_host); HF(h->near_off_host);
+    h->near_off_host = nullptr;
     F(h->res_dev);
     h->tmp = nullptr; h->bits = h->stem = h->tilekeys = nullptr; h->tile_state = nullptr; h->maxfix = nullptr; h->dt_batch = nullptr; h->win = nullptr; h->fp_dev = nullptr;
     h->ws_valid = nullptr; h->cand_xy = h->cand_n = nullptr; h->cand_info = h->patches = h->logits = nullptr;
@@ -231,6 +247,8 @@ int ensure_ws(lg_ctx* h, int B, int H, int W, int K) {
     LG_HIP(h, dev_alloc(&h->stem, words));
     LG_HIP(h, dev_alloc(&h->tilekeys, (size_t)nB * tiles));
     LG_HIP(h, dev_alloc(&h->tile_state, (size_t)nB * tiles));
+    LG_HIP(h, dev_alloc(&h->near_off, (size_t)nB + 1));
+    LG_HIP(h, hipHostMalloc((void**)&h->near_off_host, sizeof(int32_t) * ((size_t)nB + 1)));
     LG_HIP(h, dev_alloc(&h->maxfix, (size_t)nB * 2));
     LG_HIP(h, dev_alloc(&h->dt_batch, (size_t)1));
     LG_HIP(h, hipMemset(h->dt_batch, 0, sizeof(LgDtBatch)));
@@ -384,6 +402,8 @@ int lg_create(int device, lg_handle* out) {
     if (const char* e = getenv("LG_SUBBATCH")) h->opt_subbatch = std::max(1, atoi(e));
     h->opt_trace = getenv("LG_TRACE") != nullptr;
     if (const char* e = getenv("LG_NO_SKIP")) h->opt_no_skip = std::max(1, atoi(e)) & 3;   // (both bits leave the results unchanged)
+    if (const char* e = getenv("LG_FINAL_NEAR")) h->opt_final_near = std::max(0, std::min(64, atoi(e)));
+    if (getenv("LG_FINAL_PERSIST") || getenv("LG_FINAL_TPW")) h->opt_final_near = 0;   // launch-shape experiments of the full tile walk
     h->opt_nt_stores = getenv("LG_NT_STORES") != nullptr;
     h->opt_host_orient = getenv("LG_HOST_ORIENT") != nullptr;
     if (const char* e = getenv("LG_CNN_PRUNE")) h->opt_cnn_prune = atoi(e) != 0;
@@ -554,6 +574,23 @@ int lg_debug_cnn_survivors(lg_handle h, int32_t* sub_frames, int32_t* n_sub, int
     return LG_OK;
 }
 
+int lg_near_tile_rect(int bx0, int bx1, int by0, int by1, int H, int W, int halo, int32_t rect[4]) {
+    if (!rect || H < 1 || W < 1 || halo < 0) return LG_ERR_INVALID;
+    int r[4];
+    const int n = lg_near_tiles(bx0, bx1, by0, by1, H, W, halo, &r[0], &r[1], &r[2], &r[3]);
+    for (int i = 0; i < 4; i++) rect[i] = r[i];
+    return n;
+}
+
+int lg_debug_near_tiles(lg_handle h, int32_t* off, int cap) {
+    if (!h || !off) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (h->last_near_B <= 0 || !h->near_off_host) return fail(h, LG_ERR_INVALID, "lg_debug_near_tiles: the last call did not take the near launch");
+    if (cap < h->last_near_B + 1) return fail(h, LG_ERR_INVALID, "lg_debug_near_tiles: cap must hold B + 1 entries");
+    memcpy(off, h->near_off_host, sizeof(int32_t) * (h->last_near_B + 1));   // (the call that wrote it has been synchronised)
+    return LG_OK;
+}
+
 int lg_debug_dt_form(lg_handle h, int frame, int32_t form[2]) {
     if (!h || !form || frame < 0 || frame >= h->capB || !h->win) return LG_ERR_INVALID;
     LG_ENTER(h);
@@ -582,7 +619,11 @@ struct Plan {  // one call's geometry, parameters and plane pointers (absolute, 
     // sparse planes: the caller takes no plane and no validity back (lg_select_grasp*): constant tiles of the workspace planes
     // stay unwritten, lg_final_kernel records per tile which were written (tile_state), top-k and the gather read that
     bool sparse = false;
+    // near launch: lg_final_kernel takes only the tiles around the leaves (lg_near_tiles), the others get their constant key and
+    // state byte from lg_near_tiles_kernel beside the distance transform.  Sparse mode, one sub-batch, constant-tile path on.
+    bool near = false;
 };
+
 
 // which form of the row search a batch of n frames takes (LG_DT_SEARCH_ALGO forces one): one level up to 64 frames of 1080p (one
 // launch, the device is not full: 32 of 1080p 0.14 vs 0.18 ms), anchors + bands above (fewer evaluations: 64 of 4K 1.08 vs 1.54 ms)
@@ -630,11 +671,22 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
     }
     LG_HIP(h, hipEventRecord(ev_prep, s));
     LG_HIP(h, hipStreamWaitEvent(h->copy_stream, ev_prep, 0));
+    if (pl.near) {   // (one sub-batch: off = 0, n = B)  list offsets of the near tiles + the far tiles' keys and state bytes
+        ProfScope ps(h, "near_tiles", h->copy_stream);
+        lg_launch_near_tiles(h->win, n, pl.H, pl.W, pl.P.gaussian_size / 2 + 1, h->near_off, h->tilekeys, h->tile_state, h->copy_stream);
+    }
+    // its offsets come back in front of the event the host waits for before it enqueues the plane kernel: ev_orient, or ev_copy
+    // of the bit-row export where the host analyses every frame
+    auto near_copy = [&]() {
+        return hipMemcpyAsync(h->near_off_host, h->near_off, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost, h->copy_stream);
+    };
+    if (pl.near && !h->orient) LG_HIP(h, near_copy());
     if (h->orient) {   // contour analysis on the device, beside the sweeps; the host reads theta / status back
         {
             ProfScope ps(h, "orient", h->copy_stream);
             lg_launch_orient(h->orient, h->bits + off * words, h->win + off, h->fp_dev + off, off, n, pl.H, pl.W, pl.WW, h->copy_stream);
         }
+        if (pl.near) LG_HIP(h, near_copy());
         LG_HIP(h, hipMemcpyAsync(h->fp_host + off, h->fp_dev + off, sizeof(LgFrameParams) * n, hipMemcpyDeviceToHost, h->copy_stream));
         LG_HIP(h, hipMemcpyAsync(h->orient->h_status + off, h->orient->status + off, sizeof(int) * n, hipMemcpyDeviceToHost,
                                  h->copy_stream));
@@ -802,6 +854,11 @@ int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upl
     a.no_skip = h->opt_no_skip;
     a.persist = 0;   // (lg_launch_final: the tile walk stays an experiment switch)
     a.nt_stores = h->opt_nt_stores ? 1 : 0;  // measured: non-temporal plane stores are slower here (0.57 vs 0.50 ms)
+    if (pl.near) {   // (one sub-batch: off = 0, n = B; the host has waited for ev_orient / ev_copy, behind the copy of near_off)
+        a.near_off = h->near_off;
+        a.near_total = h->near_off_host[n];
+        a.near_tpw = h->opt_final_near;
+    }
     {
         ProfScope ps(h, "final", s, true);
         lg_launch_final(a, s, ps.slot ? ps.e0 : nullptr, ps.slot ? ps.e1 : nullptr);
@@ -1367,6 +1424,8 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     if (h->opt_subbatch > 0) SB = h->opt_subbatch;
     const int nsub = (B + SB - 1) / SB;
     const bool piped = nsub > 1;
+    pl.near = pl.sparse && h->opt_final_near > 0 && h->opt_subbatch == 0 && h->opt_no_skip == 0;
+    h->last_near_B = 0;
     hipStream_t sD[2] = {piped ? h->s_dt[0] : s, piped ? h->s_dt[1] : s};
     hipStream_t sM = piped ? h->s_main : s, sT = piped ? h->s_topk : s;
     while ((int)h->ev_pool.size() < 6 * nsub) {
@@ -1507,6 +1566,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     memcpy(results, h->res_host, sizeof(lg_grasp_result) * B);
     if (cands) memcpy(cands, h->cand_rows_host, sizeof(lg_grasp_candidate) * B * K);
     if (use_cnn) { h->last_cnn_B = B; h->last_cnn_K = K; h->last_cnn_SB = SB; h->last_cnn_pruned = prune; }
+    if (pl.near) h->last_near_B = B;
     if (trace && !piped) {
         float a[5] = {0};
         for (int i = 1; i <= 4; i++) hipEventElapsedTime(&a[i], tev[0], tev[i]);

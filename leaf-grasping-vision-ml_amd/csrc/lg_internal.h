@@ -53,6 +53,35 @@ struct LgWin {
     int pad_[1];
 };
 
+// Near tiles of a frame: the tiles of the fused score-plane kernel (LG_TW x LG_TH, stencil reach `halo` = Gaussian radius + 1)
+// whose bit-row test can meet the mask's bounding box [bx0, bx1] x [by0, by1].  The test reads columns tx0-8 .. tx0+LG_TW+7 and
+// rows ty0-halo .. ty0+LG_TH-1+halo reflected at the frame border -- at the bottom that reaches up to LG_TH+halo rows above ty0
+// (a last tile row of one pixel), at the top it stays inside the tile -- so tile (tx, ty), tx0 = tx * LG_TW, ty0 = ty * LG_TH, is
+// near when
+//     bx1 >= bx0  &&  bx0 <= tx0 + LG_TW + 7  &&  bx1 >= tx0 - 8  &&  by0 <= ty0 + LG_TH - 1 + halo  &&  by1 >= ty0 - LG_TH - halo.
+// Each inequality bounds tx or ty alone: the near tiles are the rectangle [*tx_lo, *tx_hi] x [*ty_lo, *ty_hi] of the frame's
+// tile grid.  Returns their number; 0 (an empty box, or one that no tile of the grid reaches) with the rectangle (0, -1, 0, -1).
+// Every other tile is constant whatever the mask: key and state byte depend on the tile index alone.  lg_final_kernel, the
+// enumeration (lg_near_tiles_kernel) and the host export lg_near_tile_rect run this code.
+__host__ __device__ inline int lg_near_tiles(int bx0, int bx1, int by0, int by1, int H, int W, int halo, int* tx_lo, int* tx_hi,
+                                             int* ty_lo, int* ty_hi) {
+    const int tiles_x = (W + LG_TW - 1) / LG_TW, tiles_y = (H + LG_TH - 1) / LG_TH;
+    const int xa = bx0 - (LG_TW + 7), xb = bx1 + 8;                     // xa <= tx0 <= xb
+    const int ya = by0 - (LG_TH - 1 + halo), yb = by1 + LG_TH + halo;   // ya <= ty0 <= yb
+    const int x_lo = xa > 0 ? (xa + LG_TW - 1) / LG_TW : 0, y_lo = ya > 0 ? (ya + LG_TH - 1) / LG_TH : 0;
+    const int x_hi = xb < 0 ? -1 : (xb / LG_TW < tiles_x ? xb / LG_TW : tiles_x - 1);
+    const int y_hi = yb < 0 ? -1 : (yb / LG_TH < tiles_y ? yb / LG_TH : tiles_y - 1);
+    if (bx1 < bx0 || x_lo > x_hi || y_lo > y_hi) {
+        *tx_lo = 0; *tx_hi = -1; *ty_lo = 0; *ty_hi = -1;
+        return 0;
+    }
+    *tx_lo = x_lo; *tx_hi = x_hi; *ty_lo = y_lo; *ty_hi = y_hi;
+    return (x_hi - x_lo + 1) * (y_hi - y_lo + 1);
+}
+__host__ __device__ inline int lg_near_tiles(const LgWin& w, int H, int W, int halo, int* tx_lo, int* tx_hi, int* ty_lo, int* ty_hi) {
+    return lg_near_tiles(w.bx0, w.bx1, w.by0, w.by1, H, W, halo, tx_lo, tx_hi, ty_lo, ty_hi);
+}
+
 struct LgFrameParams {  // per frame: leaf orientation, written by lg_orient_kernel (or by the host analysis for frames it hands back)
     float sin_t, cos_t;
     int has_angle;
@@ -96,6 +125,11 @@ struct LgFinalArgs {
     int nt_stores;  // 0: plain stores (default); 1: non-temporal plane stores (LG_NT_STORES=1; measured slower)
     int persist;    // 1: resident workgroups walk the tiles (lg_launch_final); 0: one workgroup per tile
     int tpw;        // > 0: consecutive tiles per workgroup (set by lg_launch_final)
+    // near launch (sparse mode): the workgroups take the entries of the batch's list of near tiles (lg_near_tiles) instead of
+    // every tile; the far tiles' keys and state bytes were written by lg_launch_near_tiles.  null: every tile
+    const int32_t* near_off;   // [B + 1] DEVICE: first list entry of every frame, near_off[B] = near_total
+    int near_total;            // entries of the list (the host's copy of near_off[B])
+    int near_tpw;              // consecutive list entries per workgroup (>= 1)
 };
 
 // kernel launchers (lg_kernels.hip)
@@ -126,6 +160,12 @@ int lg_launch_dt(bool bwd, const uint8_t* mask, uint32_t* tmp, float* dist_out, 
 void lg_launch_dout_border(const unsigned long long* bits, const LgWin* win, uint32_t* maxfix, int B, int H, int W, int WW,
                            hipStream_t s);
 void lg_launch_final(const LgFinalArgs& a, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+// Near tiles of a batch, in front of the near launch of lg_final_kernel (LgFinalArgs::near_off): near_off[b] = near tiles of the
+// frames before b (exclusive scan of lg_near_tiles over win[0 .. B), near_off[B] = their total), and every FAR tile's constant
+// key and state byte 0 into tilekeys / tile_state -- exactly what lg_final_kernel's constant path stores.  No atomics: the
+// same output on every run.  halo: Gaussian radius + 1 of the plane kernel that follows.
+void lg_launch_near_tiles(const LgWin* win, int B, int H, int W, int halo, int32_t* near_off, unsigned long long* tilekeys,
+                          uint8_t* tile_state, hipStream_t s);
 void lg_launch_smooth(const float* src, float* dst, int B, int H, int W, int S, const LgGaussTaps& taps, hipStream_t s);
 // tile_state (sparse planes, LgFinalArgs::sparse): [B][tiles] from lg_final_kernel, null when every plane was written.  The
 // planes of a tile with state 0 were not written: top-k and the gather use the constant tile's values instead (flat_scale,

@@ -1367,8 +1367,8 @@ int lg_launch_dtsearch(int phase, int algo, const unsigned long long* bits, uint
 // validity mask (grasp_point_selector.py:256-288) from depth + mask bits + distance_map (+ frame scalars).
 // Tile 64 x LG_TH (16), 256 threads, each thread 4 consecutive pixels x LG_TH/16 rows (16-byte stores per lane).
 //
-// Launch shape: one workgroup per tile, or (LG_FINAL_PERSIST, lg_launch_final) resident workgroups that walk the tiles; the
-// same code serves both -- blockIdx % 8 is the XCD, every XCD owns a contiguous range of tiles and its workgroups take them
+// Launch shape: one workgroup per tile, or (LG_FINAL_PERSIST, lg_launch_final) resident workgroups that walk the tiles, or (near
+// launch, sparse mode) one workgroup per entry of the batch's list of near tiles; the same code serves all -- blockIdx % 8 is the XCD, every XCD owns a contiguous range of tiles and its workgroups take them
 // with the XCD's workgroup count as stride, so neighbouring workgroups work on neighbouring tiles at the same time (shared
 // halos hit in the XCD's L2).
 // What the tile loop needs from the code: nothing loop-invariant may stay in registers across tiles at 64 VGPRs (8 waves per
@@ -1411,14 +1411,18 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
     (void)a_;
 
     // ---- the tile walk, in scalar registers (total < 2^31: lg_launch_final)
+    // Near launch (ap->near_off): the walk runs over the batch's list of near tiles (lg_near_tiles; frame b owns the entries
+    // near_off[b] .. near_off[b + 1] - 1, the tiles of its rectangle row by row) instead of over every tile of every frame.
     const int ntile = ap->tiles_x * ap->tiles_y;
-    const int total = ntile * ap->B;
+    typedef const __attribute__((address_space(4))) int32_t* lg_off_ptr;
+    const bool near = ap->near_off != nullptr;
+    const int total = near ? ap->near_total : ntile * ap->B;
     const int xcd = (int)(blockIdx.x & 7u), tq = total >> 3, tr = total & 7;
     const int xcd_first = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
     const int xcd_count = tq + (xcd < tr ? 1 : 0);
     // tiles per workgroup (ap->tpw > 0): workgroup j of the XCD takes the tpw consecutive tiles j * tpw ...; otherwise one tile
     // each, or, as resident workgroups, tiles j, j + n, j + 2n ... of the XCD's range
-    const int tpw = ap->tpw;
+    const int tpw = near ? ap->near_tpw : ap->tpw;
     const int stride = tpw > 0 ? 1 : (int)((gridDim.x + 7u) >> 3);
     int it = (int)(blockIdx.x >> 3) * (tpw > 0 ? tpw : 1);
     const int it_end = tpw > 0 ? min(it + tpw, xcd_count) : xcd_count;
@@ -1433,11 +1437,36 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
     int t = threadIdx.x;
     asm volatile("" : "+v"(t));
     const int tiles_x = ap->tiles_x;
+    const int H = ap->H, W = ap->W, WW = ap->WW;
+    int li = 0;
+    if (near) {   // the frame of list entry li: the last one that starts at or before it (scalar binary search; frames without near tiles own no entry)
+        lg_off_ptr noff = (lg_off_ptr)ap->near_off;
+        li = xcd_first + it;
+        int lo = 0, hi = ap->B;   // near_off[lo] <= li < near_off[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (noff[mid] <= li) lo = mid; else hi = mid;
+        }
+        frame = lo;
+        li -= noff[lo];
+    }
+    // the frame's near tiles: can a tile's bit-row test below meet the mask's bounding box at all?  (win / fp / maxfix were
+    // written by earlier kernels and are only read here: constant-address-space loads, i.e. the scalar cache, instead of a vector
+    // load + readfirstlane per value)
+    int rx0, rx1, ry0, ry1;
+    {
+        const __attribute__((address_space(4))) LgWin* wp = (const __attribute__((address_space(4))) LgWin*)(ap->win + frame);
+        lg_near_tiles(wp->bx0, wp->bx1, wp->by0, wp->by1, H, W, HALO, &rx0, &rx1, &ry0, &ry1);
+    }
+    if (near) {   // entry li of the rectangle, row by row (li < 8192, at most 128 tiles per row: the float quotient as below)
+        const int nx = rx1 - rx0 + 1;
+        const int q = __builtin_amdgcn_readfirstlane((int)(((float)li + 0.5f) * __frcp_rn((float)nx)));
+        tile = (ry0 + q) * tiles_x + rx0 + (li - q * nx);
+    }
     // tile < 8192, tiles_x <= 128: the float quotient of (tile + 0.5) is at least 0.5 / 128 away from an integer, its error < 0.001
     const int by = __builtin_amdgcn_readfirstlane((int)(((float)tile + 0.5f) * __frcp_rn((float)tiles_x)));
     const int bx = tile - by * tiles_x;
     const int tx0 = bx * LG_TW, ty0 = by * LG_TH;
-    const int H = ap->H, W = ap->W, WW = ap->WW;
     const size_t fo = (size_t)frame * H * W;
     const char* depth = (const char*)(ap->depth + fo);
     const char* bits = (const char*)(ap->bits + (size_t)frame * H * WW);
@@ -1452,19 +1481,12 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
     static_assert(LG_TH % 16 == 0 && RPT >= 1, "tile height must be a multiple of 16");
     // distance_map is only computed inside the frame's sweep window (LgWin, tile aligned); outside it is exactly 0 and
     // this kernel writes the plane instead of reading it
-    // (win / fp / maxfix were written by earlier kernels and are only read here: constant-address-space loads, i.e. the
-    //  scalar cache, instead of a vector load + readfirstlane per value)
-    bool in_win, near_leaf;
+    bool in_win;
+    const bool near_leaf = bx >= rx0 && bx <= rx1 && by >= ry0 && by <= ry1;   // (always, in the near launch)
     {
         const __attribute__((address_space(4))) LgWin* wp = (const __attribute__((address_space(4))) LgWin*)(ap->win + frame);
         const int wx0 = wp->wx0;
         in_win = tx0 >= wx0 && tx0 < min(W, wx0 + wp->nw * ap->win_wc) && ty0 >= wp->wy0 && ty0 < wp->wy1;
-        // can the bit-row test below meet the mask's bounding box at all?  Its columns are tx0-8 .. tx0+71; its rows
-        // ty0-HALO .. ty0+LG_TH-1+HALO, reflected at the frame border -- at the bottom that reaches up to LG_TH+HALO rows
-        // above ty0 (a last tile row of one pixel), at the top it stays inside the tile
-        const int bx0 = wp->bx0, bx1 = wp->bx1;
-        near_leaf = bx1 >= bx0 && bx0 <= tx0 + LG_TW + 7 && bx1 >= tx0 - 8 && wp->by0 <= ty0 + LG_TH - 1 + HALO &&
-                    wp->by1 >= ty0 - LG_TH - HALO;
     }
     // 4 floats of one plane at pixel offset `off` of this frame (uniform plane base + 32-bit byte offset)
     auto st4 = [&](int mi, unsigned off, int x0, const float* v) {
@@ -1827,6 +1849,11 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
 // per workgroup 0.48 / 0.45 / 0.44-0.46 / 0.44-0.45 / 0.51 / 0.63 ms; resident walk with 8 / 2 workgroups per CU 0.53 / 0.96 ms.
 // One tile per workgroup launches 518 k nearly empty workgroups; past 32 tiles the leaf tiles' stencil work collects on too
 // few workgroups.
+// The near launch (LgFinalArgs::near_off) needs neither: its grid holds the tiles around the leaves only (lg_near_tiles: 43 008
+// of the headline's 522 240, 32 928 of them on the stencil path), one per workgroup, and takes 0.262 ms where the form above
+// takes 0.436-0.438 (kernel trace); the other tiles' keys and state bytes come from lg_near_tiles_kernel (0.008 ms, beside the
+// distance transform).  lg_select_grasp* uses it in sparse mode; the form above stays for LG_FINAL_NEAR=0, the sub-batch
+// pipeline and the experiment switches.
 #ifndef LG_FINAL_SPARSE_TPW
 #define LG_FINAL_SPARSE_TPW 16
 #endif
@@ -1855,11 +1882,25 @@ void lg_launch_final(const LgFinalArgs& a_in, hipStream_t s, hipEvent_t ev_start
     // the dense launch within the noise: the workgroup launch rate is not what limits either)
     static const int tpw_env = getenv("LG_FINAL_TPW") ? atoi(getenv("LG_FINAL_TPW")) : -1;
     LgFinalArgs a = a_in;
-    const bool walk = resident && total > 2ll * resident;
+    // Near launch (a.near_off; the caller offers it in sparse mode only and never beside the experiment switches above): the
+    // list of near tiles takes the place of the tile grid, near_tpw consecutive entries per workgroup.  An empty list launches
+    // nothing: every tile of the batch is a far tile and has its key and state byte already.
+    const bool near = a.near_off != nullptr;
+    if (near) {
+        if (a.near_total <= 0) {
+            if (ev_start && ev_stop) { hipEventRecord(ev_start, s); hipEventRecord(ev_stop, s); }
+            return;
+        }
+        total = a.near_total;
+        a.near_tpw = std::max(1, a.near_tpw);
+    }
+    const bool walk = !near && resident && total > 2ll * resident;
     a.tpw = walk ? 0 : std::max(0, tpw_env >= 0 ? tpw_env : a.sparse ? LG_FINAL_SPARSE_TPW : 0);
+    const int tpw = near ? a.near_tpw : a.tpw;
     const long long per_xcd = (total + 7) / 8;
-    const unsigned grid = (unsigned)(walk ? resident : a.tpw > 1 ? 8 * ((per_xcd + a.tpw - 1) / a.tpw) : total);
+    const unsigned grid = (unsigned)(walk ? resident : tpw > 1 ? 8 * ((per_xcd + tpw - 1) / tpw) : total);
     if (a.tpw == 1) a.tpw = 0;
+    if (a.near_tpw == 1) a.near_tpw = 0;
     bool all = a.valid != nullptr;
     for (int i = 0; i < LG_NUM_MAPS; i++) all = all && a.maps[i] != nullptr;
     const bool vec = (a.W & 3) == 0;
@@ -1878,6 +1919,63 @@ void lg_launch_final(const LgFinalArgs& a_in, hipStream_t s, hipEvent_t ev_start
         hipExtLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, ev_start, ev_stop, 0, a);
     else
         hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, a);
+}
+
+// ============================================================================ near tiles of a batch
+// In front of the near launch of lg_final_kernel, beside the distance transform.  One thread per (frame, tile): a tile outside
+// its frame's rectangle (lg_near_tiles) gets the constant path's key -- score 0, largest flat index of the tile -- and state
+// byte 0.  Workgroup 0 then scans the frames' near counts into near_off (thread = frame, frames t, t + 256, ... in rounds with
+// a running base, as lg_survivors_kernel).  No atomics: the same output on every run.
+__global__ __launch_bounds__(256) void lg_near_tiles_kernel(const LgWin* __restrict__ win, int B, int H, int W, int halo,
+                                                            int32_t* __restrict__ near_off,
+                                                            unsigned long long* __restrict__ tilekeys,
+                                                            uint8_t* __restrict__ tile_state) {
+    const int tiles_x = (W + LG_TW - 1) / LG_TW, tiles_y = (H + LG_TH - 1) / LG_TH, ntile = tiles_x * tiles_y;
+    const int t = threadIdx.x;
+    int x0, x1, y0, y1;
+    const long long i = (long long)blockIdx.x * 256 + t;   // < 2^31 (lg_launch_final)
+    if (i < (long long)B * ntile) {
+        const int frame = (int)(i / ntile), tile = (int)(i - (long long)frame * ntile);
+        const int by = tile / tiles_x, bx = tile - by * tiles_x;
+        lg_near_tiles(win[frame], H, W, halo, &x0, &x1, &y0, &y1);
+        if (!(bx >= x0 && bx <= x1 && by >= y0 && by <= y1)) {
+            const int ymax = min(by * LG_TH + LG_TH, H) - 1, xmax = min(bx * LG_TW + LG_TW, W) - 1;
+            tilekeys[i] = ((unsigned long long)lg_orderable(0.0f) << 32) | (uint32_t)(ymax * W + xmax);
+            tile_state[i] = 0;
+        }
+    }
+    if (blockIdx.x != 0) return;
+    __shared__ int s_wave[4];
+    __shared__ int s_base;
+    const int lane = t & 63, wave = t >> 6;
+    if (t == 0) s_base = 0;
+    __syncthreads();
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int b = b0 + t;
+        const int c = b < B ? lg_near_tiles(win[b], H, W, halo, &x0, &x1, &y0, &y1) : 0;
+        int incl = c;   // inclusive scan inside the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += v;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int pos = s_base + incl - c;
+        for (int w = 0; w < wave; w++) pos += s_wave[w];
+        __syncthreads();   // everyone has read s_base and s_wave
+        if (t == 255) s_base = pos + c;
+        if (b < B) near_off[b] = pos;
+        __syncthreads();
+    }
+    if (t == 0) near_off[B] = s_base;
+}
+
+void lg_launch_near_tiles(const LgWin* win, int B, int H, int W, int halo, int32_t* near_off, unsigned long long* tilekeys,
+                          uint8_t* tile_state, hipStream_t s) {
+    const long long total = (long long)((W + LG_TW - 1) / LG_TW) * ((H + LG_TH - 1) / LG_TH) * B;
+    hipLaunchKernelGGL(lg_near_tiles_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, win, B, H, W, halo, near_off,
+                       tilekeys, tile_state);
 }
 
 // ============================================================================ the tail of select_grasp_point, per frame
