@@ -389,6 +389,22 @@ int lg_debug_cnn_scored(lg_handle h, int64_t* patches);
    LG_ERR_BUSY: a call in flight. */
 int lg_debug_cnn_survivors(lg_handle h, int32_t* sub_frames, int32_t* n_sub, int32_t* counts, int32_t counts_cap,
                            int32_t* list, int32_t* slot, float* logits, int64_t cap, int64_t* n_slots);
+/* Deferred planes.  A call that takes no plane and no validity back (sparse mode) does not store five of the feature planes
+   (sdf, approach, isolation, accessibility, stem): its plane kernel stores what top-k reads and flatness, and the patch gather
+   computes those five itself at the pixels of its 32 x 32 windows, with the plane kernel's per-pixel code -- the patches are the
+   same floats.  LG_DEFER_PLANES=0 at lg_create: such calls store and read the planes as calls that take planes back do.
+   lg_debug_patch: out[9][32][32] = the patch in slot `slot` of the last lg_select_grasp* call with a model loaded, as the CNN
+   read it (slot: an entry of lg_debug_cnn_survivors' list, counted from the start of the buffer: sub-batch k's slots start at
+   k * sub_frames * top_k).  LG_ERR_INVALID past the slots of that call.  Synchronises the device, launches nothing.
+   lg_debug_ws_plane_bytes: bytes[i] = device memory the handle holds for its own copy of plane i (0: never needed; a handle
+   that has only made sparse calls holds distance, traditional and flatness only).
+   lg_wave_rows_on_mask (no device, no handle; the code the gather runs): 1 when any mask bit is set in word w of the rows
+   (y & ~3) .. (y & ~3) + 3 below H of the bit rows bits[H][WW] -- the rows and columns one wave of the plane kernel covers: where
+   it is 0 that wave stored +0.0 in every masked plane, where it is 1 a pixel off the mask got (expression) * 0, which can be
+   -0.0.  0 otherwise, LG_ERR_INVALID for a bad argument. */
+int lg_debug_patch(lg_handle h, int64_t slot, float* out);
+int lg_debug_ws_plane_bytes(lg_handle h, int64_t bytes[LG_NUM_MAPS]);
+int lg_wave_rows_on_mask(const uint64_t* bits, int H, int WW, int y, int w);
 
 /* ---- GraspPointCNN training step: one call = one iteration of the inner loop of
    scripts/train_model.py:247-265 (zero_grad, forward in train mode, BCEWithLogitsLoss(pos_weight), backward,

@@ -114,6 +114,9 @@ SYMBOLS = {
     "lg_debug_cnn_scored": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "lg_debug_cnn_survivors": (C.c_int, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), _FP, C.c_int64, C.POINTER(C.c_int64)]),
+    "lg_debug_patch": (C.c_int, [_VP, C.c_int64, _FP]),
+    "lg_debug_ws_plane_bytes": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    "lg_wave_rows_on_mask": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int]),
     "lg_harvest_patches": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lg_negative_masks": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
     "lg_leaf_contour": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, C.c_int, C.POINTER(C.c_int), _VP]),

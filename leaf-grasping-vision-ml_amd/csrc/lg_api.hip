@@ -118,6 +118,8 @@ struct lg_ctx {
                                  //            =3: also without the wave-level off-leaf shortcut
     int opt_final_near = LG_FINAL_NEAR_TPW;   // LG_FINAL_NEAR=0: lg_final_kernel walks every tile in sparse mode too (the launch before the
                                  //            near launch; A/B, tests); =n: near launch with n list entries per workgroup
+    bool opt_defer_planes = true;   // LG_DEFER_PLANES=0: sparse calls store and read all six feature planes, as before the deferred mode (A/B, tests)
+    long long last_patch_floats = 0;   // lg_debug_patch: floats of h->patches the last lg_select_grasp* call with the CNN could write (0: none)
     bool opt_nt_stores = false;  // LG_NT_STORES: non-temporal plane stores (measured slower)
     int opt_side_tail = 1;         // LG_SIDE_TAIL=0: frame-border maxima + stem bits after the sweeps on the caller's stream (round 1); 1: on the
                                    // side stream behind the orientation kernel; 2: on a third stream
@@ -222,7 +224,7 @@ void free_ws(lg_ctx* h) {
     F(h->surv_keep); F(h->surv_list); F(h->surv_slot); F(h->surv_count);
     F(h->near_off); h->near_off = nullptr; h->last_near_B = 0;
     h->surv_keep = nullptr; h->surv_list = h->surv_slot = h->surv_count = nullptr;
-    h->last_scored = 0; h->last_scored_subs = 0; h->last_cnn_B = 0;
+    h->last_scored = 0; h->last_scored_subs = 0; h->last_cnn_B = 0; h->last_patch_floats = 0;
     auto HF = [](void* p) { if (p) hipHostFree(p); };
     HF(h->fp_host); HF(h->bits_host); HF(h->win_host); HF(h->res_host); HF(h->near_off_host);
     h->near_off_host = nullptr;
@@ -407,6 +409,7 @@ int lg_create(int device, lg_handle* out) {
     h->opt_nt_stores = getenv("LG_NT_STORES") != nullptr;
     h->opt_host_orient = getenv("LG_HOST_ORIENT") != nullptr;
     if (const char* e = getenv("LG_CNN_PRUNE")) h->opt_cnn_prune = atoi(e) != 0;
+    if (const char* e = getenv("LG_DEFER_PLANES")) h->opt_defer_planes = atoi(e) != 0;
     if (const char* e = getenv("LG_DT_SEARCH")) h->opt_dt_search = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("LG_DT_SEARCH_ALGO")) h->opt_dt_algo = std::max(0, std::min(4, atoi(e)));
     if (const char* e = getenv("LG_SIDE_TAIL")) h->opt_side_tail = std::max(0, std::min(2, atoi(e)));
@@ -574,6 +577,36 @@ int lg_debug_cnn_survivors(lg_handle h, int32_t* sub_frames, int32_t* n_sub, int
     return LG_OK;
 }
 
+int lg_debug_patch(lg_handle h, int64_t slot, float* out) {
+    if (!h || !out || slot < 0) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    const long long pf = lg_cnn_halo_patch_floats();   // [12][34][36], pixel (y, x) at [y + 1][x + 1]
+    if (!h->patches || (slot + 1) * pf > h->last_patch_floats)
+        return fail(h, LG_ERR_INVALID, "lg_debug_patch: no such patch slot in the last lg_select_grasp call with the CNN on this workspace");
+    hipSetDevice(h->device);
+    hipDeviceSynchronize();
+    std::vector<float> buf((size_t)pf);
+    if (hipMemcpy(buf.data(), h->patches + (size_t)slot * pf, sizeof(float) * pf, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(h, LG_ERR_HIP, "lg_debug_patch: copy failed");
+    for (int c = 0; c < 9; c++)
+        for (int y = 0; y < 32; y++)
+            memcpy(out + ((size_t)c * 32 + y) * 32, buf.data() + ((size_t)c * 34 + y + 1) * 36 + 1, sizeof(float) * 32);
+    return LG_OK;
+}
+
+int lg_debug_ws_plane_bytes(lg_handle h, int64_t bytes[LG_NUM_MAPS]) {
+    if (!h || !bytes) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    for (int i = 0; i < LG_NUM_MAPS; i++)
+        bytes[i] = h->ws_maps[i] ? (int64_t)sizeof(float) * h->capB * h->capH * h->capW : 0;
+    return LG_OK;
+}
+
+int lg_wave_rows_on_mask(const uint64_t* bits, int H, int WW, int y, int w) {
+    if (!bits || H < 1 || WW < 1 || y < 0 || y >= H || w < 0 || w >= WW) return LG_ERR_INVALID;
+    return lg_wave_on_mask((const unsigned long long*)bits, H, WW, y, w) ? 1 : 0;
+}
+
 int lg_near_tile_rect(int bx0, int bx1, int by0, int by1, int H, int W, int halo, int32_t rect[4]) {
     if (!rect || H < 1 || W < 1 || halo < 0) return LG_ERR_INVALID;
     int r[4];
@@ -622,6 +655,10 @@ struct Plan {  // one call's geometry, parameters and plane pointers (absolute, 
     // near launch: lg_final_kernel takes only the tiles around the leaves (lg_near_tiles), the others get their constant key and
     // state byte from lg_near_tiles_kernel beside the distance transform.  Sparse mode, one sub-batch, constant-tile path on.
     bool near = false;
+    // deferred planes (sparse mode, unless LG_DEFER_PLANES=0): lg_final_kernel stores what top-k reads and flatness (score-only);
+    // sdf, approach, isolation, accessibility and stem are neither allocated nor written: the gather computes them at the
+    // pixels of its windows
+    bool defer = false;
 };
 
 
@@ -812,7 +849,7 @@ int finish_orient(lg_ctx* h, const Plan& pl, int off, int n, bool* upload) {
 }
 
 // frame scalars H2D + the fused score-plane kernel
-int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upload_fp) {
+int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upload_fp, LgFinalArgs* keep = nullptr) {
     const size_t px = (size_t)pl.H * pl.W, words = (size_t)pl.H * pl.WW;
     const int H = pl.H, W = pl.W;
     const lg_params& P = pl.P;
@@ -829,6 +866,7 @@ int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upl
     a.tilekeys = h->tilekeys + (size_t)off * pl.tiles_x * pl.tiles_y;
     a.tile_state = pl.sparse ? h->tile_state + (size_t)off * pl.tiles_x * pl.tiles_y : nullptr;
     a.sparse = pl.sparse ? 1 : 0;
+    a.score_only = pl.defer ? 1 : 0;
     a.B = n; a.H = H; a.W = W; a.WW = pl.WW; a.tiles_x = pl.tiles_x; a.tiles_y = pl.tiles_y;
     a.cxi = (int)floor(P.cx); a.cyi = (int)floor(P.cy);
     a.cxf = (float)(P.cx - floor(P.cx)); a.cyf = (float)(P.cy - floor(P.cy)); a.f = (float)P.f;
@@ -863,6 +901,7 @@ int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upl
         ProfScope ps(h, "final", s, true);
         lg_launch_final(a, s, ps.slot ? ps.e0 : nullptr, ps.slot ? ps.e1 : nullptr);
     }
+    if (keep) *keep = a;   // (the deferred gather of these frames runs the same per-pixel code on the same arguments)
     return LG_OK;
 }
 
@@ -1399,9 +1438,11 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     h->last_scored = use_cnn ? (long long)B * P.top_k : 0;
     h->last_scored_subs = 0;
     h->last_cnn_B = 0;
-    // all eight planes are needed when the CNN rescoring runs; otherwise only distance + traditional
+    pl.defer = pl.sparse && h->opt_defer_planes;
+    // all eight planes are needed when the CNN rescoring runs and the planes are not deferred (deferred: flatness, which the
+    // gather still reads); otherwise only distance + traditional
     for (int i = 0; i < LG_NUM_MAPS; i++)
-        if (!pl.maps[i] && (use_cnn || i == LG_MAP_DISTANCE || i == LG_MAP_TRADITIONAL)) {
+        if (!pl.maps[i] && ((use_cnn && (!pl.defer || i == LG_MAP_FLATNESS)) || i == LG_MAP_DISTANCE || i == LG_MAP_TRADITIONAL)) {
             rc = ensure_ws_map(h, i);
             if (rc) return rc;
             pl.maps[i] = h->ws_maps[i];
@@ -1424,6 +1465,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     if (h->opt_subbatch > 0) SB = h->opt_subbatch;
     const int nsub = (B + SB - 1) / SB;
     const bool piped = nsub > 1;
+    std::vector<LgFinalArgs> fargs((size_t)nsub);   // the plane launches' arguments, for the deferred gather
     pl.near = pl.sparse && h->opt_final_near > 0 && h->opt_subbatch == 0 && h->opt_no_skip == 0;
     h->last_near_B = 0;
     hipStream_t sD[2] = {piped ? h->s_dt[0] : s, piped ? h->s_dt[1] : s};
@@ -1455,7 +1497,8 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
                 for (int i = 0; i < LG_NUM_MAPS; i++) mp[i] = pl.maps[i] ? pl.maps[i] + off * px : nullptr;
                 lg_launch_gather(depth + off * px, mask + off * px, mp, pl.sparse ? h->tile_state + (size_t)off * tiles : nullptr,
                                  P.flat_scale, n, H, W, K, h->cand_xy + (size_t)off * K * 2,
-                                 h->cand_n + off, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, sM, list, count);
+                                 h->cand_n + off, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, sM, list, count,
+                                 pl.defer ? &fargs[k] : nullptr);
             }
             std::string err;
             hipStream_t sC = sM;
@@ -1505,7 +1548,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     for (int k = 0; k < nsub; k++) {
         const int off = k * SB, n = std::min(SB, B - off);
         if (piped) LG_HIP(h, hipStreamWaitEvent(sM, EV(k, 2), 0));
-        rc = enq_final(h, pl, off, n, sM, upload_fp);
+        rc = enq_final(h, pl, off, n, sM, upload_fp, &fargs[k]);
         if (rc) return rc;
         if (trace && !piped) hipEventRecord(tev[2], s);   // after the fused planes
         if (piped) {
@@ -1566,6 +1609,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     memcpy(results, h->res_host, sizeof(lg_grasp_result) * B);
     if (cands) memcpy(cands, h->cand_rows_host, sizeof(lg_grasp_candidate) * B * K);
     if (use_cnn) { h->last_cnn_B = B; h->last_cnn_K = K; h->last_cnn_SB = SB; h->last_cnn_pruned = prune; }
+    h->last_patch_floats = use_cnn ? (long long)B * K * lg_cnn_halo_patch_floats() : 0;
     if (pl.near) h->last_near_B = B;
     if (trace && !piped) {
         float a[5] = {0};

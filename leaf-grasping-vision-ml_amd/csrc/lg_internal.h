@@ -82,6 +82,19 @@ __host__ __device__ inline int lg_near_tiles(const LgWin& w, int H, int W, int h
     return lg_near_tiles(w.bx0, w.bx1, w.by0, w.by1, H, W, halo, tx_lo, tx_hi, ty_lo, ty_hi);
 }
 
+// The plane kernel's wave-level shortcut, as the deferred gather has to evaluate it for one pixel: a wave of lg_final_kernel
+// holds four rows of a tile, y & ~3 .. (y & ~3) + 3 (LG_TH % 4 == 0, 16 lanes of 4 pixels per row), over the tile's 64 columns
+// = word w = x >> 6 of the bit rows.  When none of those pixels lies on the mask the wave stores +0.0 in every "* mask" plane;
+// otherwise a pixel off the mask stores (expression) * 0, which is -0.0 where the expression is negative.  bits: the frame's
+// bit rows [H][WW] (bits past W are 0).  lg_gather_kernel and the host export lg_wave_rows_on_mask run this code.
+__host__ __device__ inline bool lg_wave_on_mask(const unsigned long long* bits, int H, int WW, int y, int w) {
+    const int y4 = y & ~3;
+    unsigned long long any = 0;
+    for (int r = 0; r < 4; r++)
+        if (y4 + r < H) any |= bits[(size_t)(y4 + r) * WW + w];
+    return any != 0;
+}
+
 struct LgFrameParams {  // per frame: leaf orientation, written by lg_orient_kernel (or by the host analysis for frames it hands back)
     float sin_t, cos_t;
     int has_angle;
@@ -108,6 +121,8 @@ struct LgFinalArgs {
     unsigned long long* tilekeys; // [B][tiles]
     uint8_t* tile_state;          // [B][tiles] or null: 1 = the tile's planes and validity were written, 0 = constant tile
     int sparse;                   // 1: constant tiles write no plane and no validity byte (only their key and state byte)
+    int score_only;               // 1 (deferred planes; with sparse): stencil tiles store traditional, validity, flatness and
+                                  //   distance = 0 outside the sweep window only; lg_launch_gather computes the other five planes at its windows
     int B, H, W, WW, tiles_x, tiles_y;
     int cxi, cyi;      // floor of the optical centre; (x - cxi) is exact, the fraction is subtracted afterwards
     float cxf, cyf, f;  // fractions in [0,1) and the focal length
@@ -176,9 +191,13 @@ void lg_launch_topk(const float* trad, const uint8_t* valid, const float* depth,
                     bool keys_ready, int B, int H, int W, int k, int min_dist, int32_t* out_xy, int32_t* out_n,
                     float* out_info, hipStream_t s, unsigned long long* keep = nullptr, int mask_is_bool = 0);
 // list / count (lg_launch_survivors; both null: every candidate): patch slot j takes entry list[j], slots >= *count are left alone
+// defer (deferred planes; haloed patches, tile_state given): the arguments of the score-only lg_launch_final over the same
+// frames.  Of maps_dev only flatness and distance are read then; sdf, approach, isolation, accessibility and stem of a window's
+// pixels on a state-1 tile are computed here, by the plane kernel's own per-pixel code.
 void lg_launch_gather(const float* depth, const uint8_t* mask, const float* const* maps_dev, const uint8_t* tile_state,
                       float flat_scale, int B, int H, int W, int k, const int32_t* xy, const int32_t* n, float* patches,
-                      bool haloed, hipStream_t s, const int32_t* list = nullptr, const int32_t* count = nullptr);
+                      bool haloed, hipStream_t s, const int32_t* list = nullptr, const int32_t* count = nullptr,
+                      const LgFinalArgs* defer = nullptr);
 
 // The host half of select_grasp_point on the device (lg_finish_kernel): CNN rescoring of the candidates, 3-D point, pre-grasp point
 struct LgFinishArgs {

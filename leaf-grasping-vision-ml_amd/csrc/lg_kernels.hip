@@ -6,6 +6,7 @@
 
 #include <limits.h>
 #include <algorithm>
+#include <type_traits>
 #include <stdlib.h>
 
 // ============================================================================ helpers
@@ -1387,12 +1388,144 @@ int lg_launch_dtsearch(int phase, int algo, const unsigned long long* bits, uint
 #endif
 #define LG_FINAL_WPE_ATTR __attribute__((amdgpu_waves_per_eu(LG_FINAL_WPE, LG_FINAL_WPE)))
 __device__ __forceinline__ float lg_uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-// VEC: W % 4 == 0 (16-byte loads / stores everywhere); ALL: every plane and the validity plane are wanted (the grasp-selection
+// ---- the per-pixel arithmetic, stated once: lg_final_kernel and the deferred form of lg_gather_kernel both call these, so a
+//      plane the gather computes at its windows is the float the plane kernel would have stored there.  hipcc contracts a * b + c
+//      to an FMA where it likes, and the same inlined source did not contract alike in two kernels (sdf and the gradient's square
+//      came out with the other product fused): contraction is therefore off in lg_flat4 and lg_pixels4 and every FMA is written
+//      out -- in the form the plane kernel has been compiled to all along, so its planes keep their bits.
+//      FROZEN HISTORY, NOT A NUMERICAL CHOICE: which product is fused where (pixel 0 of four unfused, f^2 fused for pixels 0-1,
+//      FUSE_SY by instantiation) is what one compiler version happened to emit for the plane kernel before these functions
+//      existed.  No form is more accurate than another; they are written down so that the planes, the patches and every test
+//      that compares them byte for byte stay what they were.  Do not tidy them up.  The Gaussian taps below are NOT pinned
+//      (see there): a toolchain change can still alter the last bit of flatness, in every kernel alike.
+// Gaussian taps in ascending order, along a row (stride 1) and down a column (stride S floats)
+// (These two stay under the compiler's contraction: inside lg_final_kernel's unrolled row loops it compiles them to a mixture of
+// packed multiplies + adds and FMAs that depends on the row's place in the tile.  The smoothed plane, and with it flatness, can
+// therefore not be recomputed bit for bit anywhere else without changing the plane kernel's own output: flatness stays a
+// stored plane, profiles/NOTES_deferred_planes.md.)
+template <int R>
+__device__ __forceinline__ float lg_tap_row(const float (&kw)[2 * R + 1], const float* p) {
+    float acc = kw[0] * p[0];
+#pragma unroll
+    for (int i = 1; i < 2 * R + 1; i++) acc += kw[i] * p[i];
+    return acc;
+}
+template <int R, int S>
+__device__ __forceinline__ float lg_tap_col(const float (&kw)[2 * R + 1], const float* p) {
+    float acc = kw[0] * p[0];
+#pragma unroll
+    for (int i = 1; i < 2 * R + 1; i++) acc += kw[i] * p[i * S];
+    return acc;
+}
+// flatness of four pixels x .. x + 3 of a row: Sobel cross-correlation on the smoothed, reflect-padded plane, exp(-scale |grad|)
+// (:646-655).  ga, gb, gc: rows y - 1, y, y + 1 of that plane at columns x - 1 .. x + 4.  (2 * g is exact: the sums round the
+// same fused or not.)  FUSE_SY: which square of sx^2 + sy^2 is fused -- the instantiations of the plane kernel had been compiled
+// either way: every plane wanted and W % 4 == 0 fused sy, the others sx; the score-only form follows the dense call of its width.
+template <bool FUSE_SY>
+__device__ __forceinline__ void lg_flat4(const float (&ga)[6], const float (&gb)[6], const float (&gc)[6], float flat_scale,
+                                         float (&o_flat)[4]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        float sx = (ga[j + 2] - ga[j]) + 2.0f * (gb[j + 2] - gb[j]) + (gc[j + 2] - gc[j]);
+        float sy = (gc[j] + 2.0f * gc[j + 1] + gc[j + 2]) - (ga[j] + 2.0f * ga[j + 1] + ga[j + 2]);
+        const float g2 = FUSE_SY ? __builtin_fmaf(sy, sy, sx * sx) : __builtin_fmaf(sx, sx, sy * sy);
+        o_flat[j] = __expf(-flat_scale * __builtin_amdgcn_sqrtf(g2));  // v_sqrt_f32, 1 ulp
+    }
+}
+// frame scalars of the per-pixel block.  AP: a pointer to the LgFinalArgs (the plane kernel's kernarg segment, or the
+// gather's by-value copy); FP / MP: the frame's LgFrameParams and its two maxfix words
+struct LgPixFrame {
+    int has_angle;
+    float sin_t, cos_t, inv_maxabs, opt_d, inv_2s2, focal, f2, ramp_step;
+};
+template <class AP, class FP, class MP>
+__device__ __forceinline__ LgPixFrame lg_pix_frame(AP ap, FP fpp, MP mfp) {
+    LgPixFrame c;
+    c.has_angle = fpp->has_angle;
+    c.sin_t = fpp->sin_t; c.cos_t = fpp->cos_t;
+    const uint32_t mfi = mfp[0], mfo = mfp[1];
+    const float maxabs = fmaxf((float)mfi * (1.0f / 65536.0f), (float)mfo * (1.0f / 65536.0f));
+    c.inv_maxabs = lg_uniform_f(__frcp_rn(maxabs));
+    c.opt_d = ap->optimal_distance;
+    c.inv_2s2 = ap->inv_2s2;
+    c.focal = ap->f;
+    c.f2 = c.focal * c.focal;
+    c.ramp_step = ap->iso_ramp_step;
+    return c;
+}
+// the four pixels x0 .. x0 + 3 of row y on a wave that holds a leaf pixel: geometry, SDF / edge term, isolation (ISO: it is no
+// part of `traditional`, the score-only plane kernel leaves it out), fusion, validity.  mnib / snib: their mask and stem bits;
+// din: distance_map; o_flat: lg_flat4.  Returns the validity bytes (bit 8 j: pixel j).
+// Which products are fused is the plane kernel's compiled form, by the pixel's place x & 3 in its lane's four (x0 % 4 == 0
+// there; the gather's groups start anywhere): pixel 0 rounds dx^2 and dy^2 separately (they were one packed multiply), pixels
+// 1-3 fuse dx^2; pixels 0-1 fuse f^2 into r^2 + f^2, pixels 2-3 add the rounded f^2.
+template <bool ISO, class AP>
+__device__ __forceinline__ uint32_t lg_pixels4(AP ap, const LgPixFrame& c, int y, int x0, int H, int W, unsigned mnib, unsigned snib,
+                                               const float* din, const float (&o_flat)[4], float w_flat, float (&o_sdf)[4],
+                                               float (&o_app)[4], float (&o_iso)[4], float (&o_acc)[4], float (&o_stem)[4],
+                                               float (&o_trad)[4], bool (&o_valid)[4]) {
+#pragma clang fp contract(off)
+    uint32_t vbytes = 0;
+    const float dyp = (float)(y - ap->cyi) - ap->cyf;  // exact integer part first: no cancellation near the centre
+    const float dyp2 = dyp * dyp;
+    const int dyb = min(y + 1, H - y);
+    const float ramp = __builtin_fmaf(c.ramp_step, (float)y, ap->iso_ramp_top);
+    const float w_approach = ap->w_approach, w_sdf = ap->w_sdf, w_access = ap->w_access;
+    const int has_angle = c.has_angle;
+    const float sin_t = c.sin_t, cos_t = c.cos_t, inv_maxabs = c.inv_maxabs, opt_d = c.opt_d, inv_2s2 = c.inv_2s2;
+    const float focal = c.focal, f2 = c.f2;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int x = x0 + j;
+        const float m = ((mnib >> j) & 1u) ? 1.0f : 0.0f;
+        const float st = ((snib >> j) & 1u) ? 1.0f : 0.0f;
+        // closed-form geometry planes                                           (:502-524, :569-593)
+        const float dxp = (float)(x - ap->cxi) - ap->cxf;
+        const int jj = x & 3;
+        const float r2 = jj == 0 ? dxp * dxp + dyp2 : __builtin_fmaf(dxp, dxp, dyp2);
+        const float inv_r = r2 > 0.0f ? rsqrtf(r2) : 0.0f;
+        const float r = r2 * inv_r;
+        const float r2f2 = jj < 2 ? __builtin_fmaf(focal, focal, r2) : f2 + r2;
+        const float app = focal * rsqrtf(r2f2) * m;
+        const float cosang = r2 > 0.0f ? dxp * inv_r : 1.0f;
+        const float acc = __builtin_fmaf(ap->access_w_dir, cosang, ap->access_w_dist * __builtin_fmaf(-ap->inv_maxd, r, 1.0f)) * m;
+        // SDF / edge term                                                        (:526-567)
+        const float align = has_angle ? fabsf(__builtin_fmaf(sin_t, dxp * inv_r, -(cos_t * (dyp * inv_r)))) : 1.0f;
+        const float dd = din[j] - opt_d;
+        const float interior = __expf(-(dd * dd) * inv_2s2);
+        const float sdfn = din[j] * inv_maxabs;  // inside the mask d_out == 0
+        const float sdf = __builtin_fmaf(ap->sdf_w_sdf, sdfn, __builtin_fmaf(ap->sdf_w_interior, interior, ap->sdf_w_align * align)) * m;
+        float iso = 0.0f;
+        if (ISO) {
+            // degenerate isolation map: chamfer-3 transform of an image with no zero pixel (:595-633)
+            const int dbrd = min(min(x + 1, W - x), dyb);
+            const float dt3 = (float)(ap->init0 + (uint32_t)dbrd * LG_A3) * (1.0f / 65536.0f);
+            const float s = dt3 * ap->iso_inv_max;
+            iso = __builtin_fmaf(ap->iso_w_close, s, ap->iso_w_wide * s) * ramp * m;
+        }
+        // fusion + validity                                                      (:272-288)
+        const float trad = __builtin_fmaf(w_access, acc, __builtin_fmaf(w_flat, o_flat[j], __builtin_fmaf(w_approach, app, w_sdf * sdf))) *
+                           (1.0f - st);
+        const bool valid = (din[j] > ap->min_edge_distance) && (m > 0.0f) && (st < ap->stem_valid_thresh);
+        o_sdf[j] = sdf; o_app[j] = app; o_iso[j] = iso; o_acc[j] = acc; o_stem[j] = st; o_trad[j] = trad;
+        o_valid[j] = valid;
+        if (valid) vbytes |= 1u << (8 * j);
+    }
+    return vbytes;
+}
+
+// VEC: W % 4 == 0 (16-byte loads / stores everywhere); ALL: every plane and the validity plane are wanted (the dense
 // call with the CNN): the instantiation for the usual case carries no per-plane null checks and no scalar store paths.
+// SCORE (deferred planes, LgFinalArgs::score_only; with ALL = false): what top-k reads is stored -- traditional, validity --,
+// distance = 0 outside the sweep window, which the gather still reads, and flatness (see lg_tap_row), again without null
+// checks; sdf, approach, isolation, accessibility and stem are not stored and the isolation arithmetic is not done:
+// lg_gather_kernel computes those five at its windows.
 // R: radius of the separable Gaussian of ImageProcessor.smooth_depth (gaussian_size = 2R+1: 1, 3, 5 = the node's, 7); the
 // stencil reaches HALO = R + 1 pixels (Gaussian, then the 3x3 Sobel).
-template <bool VEC, bool ALL, int R>
+template <bool VEC, bool ALL, int R, bool SCORE = false>
 __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinalArgs a_) {
+    static_assert(!(ALL && SCORE), "score-only stores fewer planes than ALL");
     constexpr int HALO = R + 1;
     static_assert(R >= 0 && HALO <= 4, "the depth tile carries 4 halo columns");
     constexpr int DW = 72;             // dm tile: cols tx0-4 .. tx0+67
@@ -1490,8 +1623,10 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
     }
     // 4 floats of one plane at pixel offset `off` of this frame (uniform plane base + 32-bit byte offset)
     auto st4 = [&](int mi, unsigned off, int x0, const float* v) {
+        if (SCORE && mi != LG_MAP_TRADITIONAL && mi != LG_MAP_DISTANCE && mi != LG_MAP_FLATNESS) return;   // (mi is a literal at every call)
         float* dst = ap->maps[mi];
-        if (!ALL && !dst) return;
+        if (!ALL && !SCORE && !dst) return;
+        if (SCORE && mi == LG_MAP_FLATNESS && !dst) return;   // (a call without a model has no gather: nobody reads flatness, the plane is not there)
 #ifdef LG_FINAL_ABLATE   // timing ablation builds only (tools/build_variants.sh): wrong results by design
         if ((LG_FINAL_ABLATE & 8) && mi != LG_MAP_TRADITIONAL) return;   // arithmetic without the plane stores
 #endif
@@ -1507,7 +1642,7 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
         }
     };
     auto st_valid = [&](unsigned off, int x0, uint32_t vbytes) {
-        if (!ALL && !ap->valid) return;
+        if (!ALL && !SCORE && !ap->valid) return;
         uint8_t* p = ap->valid + fo + off;
         if (vec) {
             __builtin_nontemporal_store(vbytes, reinterpret_cast<uint32_t*>(p));
@@ -1662,18 +1797,8 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
         float kw[2 * R + 1];
 #pragma unroll
         for (int i = 0; i < 2 * R + 1; i++) kw[i] = ap->k1[i];
-        auto tap_row = [&](const float* p) {   // taps in ascending order, like the 5-tap form this generalises
-            float acc = kw[0] * p[0];
-#pragma unroll
-            for (int i = 1; i < 2 * R + 1; i++) acc += kw[i] * p[i];
-            return acc;
-        };
-        auto tap_col = [&](const float* p) {
-            float acc = kw[0] * p[0];
-#pragma unroll
-            for (int i = 1; i < 2 * R + 1; i++) acc += kw[i] * p[i * GW];
-            return acc;
-        };
+        auto tap_row = [&](const float* p) { return lg_tap_row<R>(kw, p); };   // taps in ascending order, like the 5-tap form this generalises
+        auto tap_col = [&](const float* p) { return lg_tap_col<R, GW>(kw, p); };
         const int ec = t & 63;
         int lc = lg_reflect(tx0 - 1 + ec, W) - (tx0 - 4);
         lc = lc < R ? R : (lc > DW - 1 - R ? DW - 1 - R : lc);
@@ -1709,17 +1834,8 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
 
     // ---- per-pixel planes
     const __attribute__((address_space(4))) LgFrameParams* fpp = (const __attribute__((address_space(4))) LgFrameParams*)(ap->fp + frame);
-    const int has_angle = fpp->has_angle;
-    const float sin_t = fpp->sin_t, cos_t = fpp->cos_t;
     const __attribute__((address_space(4))) uint32_t* mfp = (const __attribute__((address_space(4))) uint32_t*)(ap->maxfix + frame * 2);
-    const uint32_t mfi = mfp[0], mfo = mfp[1];
-    const float maxabs = fmaxf((float)mfi * (1.0f / 65536.0f), (float)mfo * (1.0f / 65536.0f));
-    const float inv_maxabs = lg_uniform_f(__frcp_rn(maxabs));
-    const float opt_d = ap->optimal_distance;
-    const float inv_2s2 = ap->inv_2s2;
-    const float focal = ap->f;
-    const float f2 = focal * focal;
-    const float ramp_step = ap->iso_ramp_step;
+    const LgPixFrame pf = lg_pix_frame(ap, fpp, mfp);
     unsigned long long best = 0;
 #pragma unroll
     for (int rr = 0; rr < RPT; rr++) {
@@ -1746,13 +1862,7 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
                 ga[0] = a4.x; ga[1] = a4.y; ga[2] = a4.z; ga[3] = a4.w; ga[4] = a2.x; ga[5] = a2.y;
                 gb[0] = b4.x; gb[1] = b4.y; gb[2] = b4.z; gb[3] = b4.w; gb[4] = b2.x; gb[5] = b2.y;
                 gc[0] = c4.x; gc[1] = c4.y; gc[2] = c4.z; gc[3] = c4.w; gc[4] = c2.x; gc[5] = c2.y;
-                const float flat_scale = ap->flat_scale;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    float sx = (ga[j + 2] - ga[j]) + 2.0f * (gb[j + 2] - gb[j]) + (gc[j + 2] - gc[j]);
-                    float sy = (gc[j] + 2.0f * gc[j + 1] + gc[j + 2]) - (ga[j] + 2.0f * ga[j + 1] + ga[j + 2]);
-                    o_flat[j] = __expf(-flat_scale * __builtin_amdgcn_sqrtf(sx * sx + sy * sy));  // v_sqrt_f32, 1 ulp
-                }
+                lg_flat4<VEC && (ALL || SCORE)>(ga, gb, gc, ap->flat_scale, o_flat);
             }
             st4(LG_MAP_FLATNESS, off, x0, o_flat);
             if (!in_win) { const float z4[4] = {zero, zero, zero, zero}; st4(LG_MAP_DISTANCE, off, x0, z4); }
@@ -1765,45 +1875,16 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
             const bool wave_on_mask = (ap->no_skip & 2) || __ballot(mnib != 0) != 0ull;
             if (wave_on_mask) {
                 float o_sdf[4], o_app[4], o_iso[4], o_acc[4], o_stem[4];
-                const float dyp = (float)(y - ap->cyi) - ap->cyf;  // exact integer part first: no cancellation near the centre
-                const int dyb = min(y + 1, H - y);
-                const float ramp = ap->iso_ramp_top + ramp_step * (float)y;
-                const float w_approach = ap->w_approach, w_sdf = ap->w_sdf, w_access = ap->w_access;
+                bool o_valid[4];
+                vbytes = lg_pixels4<!SCORE>(ap, pf, y, x0, H, W, mnib, snib, din, o_flat, w_flat, o_sdf, o_app, o_iso, o_acc, o_stem,
+                                            o_trad, o_valid);
 #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int x = x0 + j;
-                    const float m = ((mnib >> j) & 1u) ? 1.0f : 0.0f;
-                    const float st = ((snib >> j) & 1u) ? 1.0f : 0.0f;
-                    // closed-form geometry planes                                           (:502-524, :569-593)
-                    const float dxp = (float)(x - ap->cxi) - ap->cxf;
-                    const float r2 = dxp * dxp + dyp * dyp;
-                    const float inv_r = r2 > 0.0f ? rsqrtf(r2) : 0.0f;
-                    const float r = r2 * inv_r;
-                    const float app = focal * rsqrtf(r2 + f2) * m;
-                    const float cosang = r2 > 0.0f ? dxp * inv_r : 1.0f;
-                    const float acc = (ap->access_w_dist * (1.0f - r * ap->inv_maxd) + ap->access_w_dir * cosang) * m;
-                    // SDF / edge term                                                        (:526-567)
-                    const float align = has_angle ? fabsf(dxp * inv_r * sin_t - dyp * inv_r * cos_t) : 1.0f;
-                    const float dd = din[j] - opt_d;
-                    const float interior = __expf(-(dd * dd) * inv_2s2);
-                    const float sdfn = din[j] * inv_maxabs;  // inside the mask d_out == 0
-                    const float sdf = (ap->sdf_w_interior * interior + ap->sdf_w_align * align + ap->sdf_w_sdf * sdfn) * m;
-                    // degenerate isolation map: chamfer-3 transform of an image with no zero pixel (:595-633)
-                    const int dbrd = min(min(x + 1, W - x), dyb);
-                    const float dt3 = (float)(ap->init0 + (uint32_t)dbrd * LG_A3) * (1.0f / 65536.0f);
-                    const float s = dt3 * ap->iso_inv_max;
-                    const float iso = (ap->iso_w_close * s + ap->iso_w_wide * s) * ramp * m;
-                    // fusion + validity                                                      (:272-288)
-                    const float trad = (w_approach * app + w_sdf * sdf + w_flat * o_flat[j] + w_access * acc) * (1.0f - st);
-                    const bool valid = (din[j] > ap->min_edge_distance) && (m > 0.0f) && (st < ap->stem_valid_thresh);
-                    o_sdf[j] = sdf; o_app[j] = app; o_iso[j] = iso; o_acc[j] = acc; o_stem[j] = st; o_trad[j] = trad;
-                    if (valid) vbytes |= 1u << (8 * j);
-                    if (x < W) {
+                for (int j = 0; j < 4; j++)
+                    if (x0 + j < W) {
                         unsigned long long key =
-                            ((unsigned long long)lg_orderable(lg_valid_score(trad, valid)) << 32) | (uint32_t)(y * W + x);
+                            ((unsigned long long)lg_orderable(lg_valid_score(o_trad[j], o_valid[j])) << 32) | (uint32_t)(y * W + x0 + j);
                         best = key > best ? key : best;
                     }
-                }
                 st4(LG_MAP_SDF, off, x0, o_sdf);
                 st4(LG_MAP_APPROACH, off, x0, o_app);
                 st4(LG_MAP_ISOLATION, off, x0, o_iso);
@@ -1904,10 +1985,11 @@ void lg_launch_final(const LgFinalArgs& a_in, hipStream_t s, hipEvent_t ev_start
     bool all = a.valid != nullptr;
     for (int i = 0; i < LG_NUM_MAPS; i++) all = all && a.maps[i] != nullptr;
     const bool vec = (a.W & 3) == 0;
+    const bool score = a.score_only != 0;   // (the caller sets it in sparse mode only: traditional, distance and validity are there)
     void (*k)(LgFinalArgs) = nullptr;
 #define LG_FINAL_PICK(RR)                                                                                  \
-    k = vec ? (all ? lg_final_kernel<true, true, RR> : lg_final_kernel<true, false, RR>)                   \
-            : (all ? lg_final_kernel<false, true, RR> : lg_final_kernel<false, false, RR>)
+    k = vec ? (score ? lg_final_kernel<true, false, RR, true> : all ? lg_final_kernel<true, true, RR> : lg_final_kernel<true, false, RR>)    \
+            : (score ? lg_final_kernel<false, false, RR, true> : all ? lg_final_kernel<false, true, RR> : lg_final_kernel<false, false, RR>)
     switch (a.gauss_r) {   // make_plan admits gaussian_size 1, 3, 5, 7 only
         case 0: LG_FINAL_PICK(0); break;
         case 1: LG_FINAL_PICK(1); break;
@@ -2518,13 +2600,21 @@ struct LgGatherMaps { const float* p[7]; };
 // tile_state (sparse planes): on a tile with state 0 the seven planes were not written; its pixels take the constant tile's
 // values (flatness lg_const_flat(flat_scale), every other plane 0 -- distance too: the sweeps write 0 at a pixel off the leaf,
 // and the final kernel's constant path writes 0 outside their window), so the patches are those of the written planes.
-template <bool HALO>
+// DEFER (deferred planes; fa = the arguments of the score-only plane launch over these frames): sdf, approach, isolation,
+// accessibility and stem were not stored.  A window's distinct pixels form one rectangle of at most 32 x 32 (replicate clamping
+// only repeats its border pixels); every pixel of it on a state-1 tile goes through lg_pixels4, four pixels of a row per
+// thread as in the plane kernel, with the stored flatness and distance, behind the plane kernel's own wave-level predicate
+// (lg_wave_on_mask: the sign of a zero depends on it).  The window then reads those five planes from LDS.
+struct LgGatherNoDefer { int unused; };
+template <bool HALO, bool DEFER>
 __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict__ depth,
                                                         const uint8_t* __restrict__ mask, LgGatherMaps maps,
                                                         const uint8_t* __restrict__ tile_state, float flat_scale, int H,
                                                         int W, int k, const int32_t* __restrict__ xy,
                                                         const int32_t* __restrict__ n, float* __restrict__ patches,
-                                                        const int32_t* __restrict__ list, const int32_t* __restrict__ count) {
+                                                        const int32_t* __restrict__ list, const int32_t* __restrict__ count,
+                                                        typename std::conditional<DEFER, LgFinalArgs, LgGatherNoDefer>::type fa) {
+    __shared__ float s_pl[DEFER ? 5 : 1][DEFER ? 1024 : 1];   // sdf, approach, isolation, accessibility, stem of the rectangle
     __shared__ float s_mn[4], s_mx[4];
     __shared__ int s_mat[3][2];   // state of the <= 3 x 2 tiles under the window (rows ty_lo.., columns tx_lo..)
     constexpr int PL = HALO ? 34 * 36 : 1024, RP = HALO ? 36 : 32, O0 = HALO ? 37 : 0;
@@ -2556,6 +2646,8 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
     __syncthreads();
     bool mat[4];
     size_t o_[4];
+    int li_[4];   // (deferred planes) the pixel's place in the rectangle
+    const int ry0 = max(py - 16, 0), rx0 = max(px - 16, 0);   // first row and column of the window's rectangle
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         int i = t + 256 * q;
@@ -2563,9 +2655,53 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
         yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);
         xx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
         o_[q] = fo + (size_t)yy * W + xx;
+        li_[q] = (yy - ry0) * 32 + (xx - rx0);
         mat[q] = s_mat[yy / LG_TH - ty_lo][xx / LG_TW - tx_lo] != 0;
     }
     const float flat1 = lg_const_flat(flat_scale);
+    if constexpr (DEFER) {
+        const int RH = min(py + 15, H - 1) - ry0 + 1, RW = min(px + 15, W - 1) - rx0 + 1;
+        const int WW = fa.WW;
+        const unsigned long long* bits = fa.bits + (size_t)frame * H * WW;
+        const unsigned long long* stemb = fa.stem_bits + (size_t)frame * H * WW;
+        // four pixels of a rectangle row per thread (columns past the rectangle or the frame store nothing)
+        const int ry = t >> 3, gx = 4 * (t & 7);
+        if (ry < RH && gx < RW) {
+            const int y = ry0 + ry, x0 = rx0 + gx;
+            float o_flat[4];
+            unsigned mnib = 0, snib = 0, on = 0, live = 0;   // per pixel: mask bit, stem bit, its wave of the plane kernel held a leaf pixel, state-1 tile
+            float din[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int x = min(x0 + j, W - 1);
+                const size_t wi = (size_t)y * WW + (x >> 6);
+                mnib |= (unsigned)((bits[wi] >> (x & 63)) & 1ull) << j;
+                snib |= (unsigned)((stemb[wi] >> (x & 63)) & 1ull) << j;
+                // (on a state-0 tile the distance plane holds stale or unwritten data in sparse mode: whatever is computed from
+                // it is dropped below, where `live` picks the constant tile's values)
+                din[j] = maps.p[LG_MAP_DISTANCE][fo + (size_t)y * W + x];
+                o_flat[j] = 0.0f;   // flatness enters `traditional` only, which the gather does not use: no load
+                if ((fa.no_skip & 2) || lg_wave_on_mask(bits, H, WW, y, x >> 6)) on |= 1u << j;
+                if (s_mat[y / LG_TH - ty_lo][x / LG_TW - tx_lo] != 0) live |= 1u << j;
+            }
+            float o_sdf[4], o_app[4], o_iso[4], o_acc[4], o_stem[4], o_trad[4];
+            bool o_valid[4];
+            const LgPixFrame pf = lg_pix_frame(&fa, fa.fp + frame, fa.maxfix + 2 * (size_t)frame);
+            lg_pixels4<true>(&fa, pf, y, x0, H, W, mnib, snib, din, o_flat, fa.w_flat, o_sdf, o_app, o_iso, o_acc, o_stem, o_trad, o_valid);
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (gx + j < RW) {
+                    const bool lv = (live >> j) & 1u, w_on = (on >> j) & 1u;   // off a state-1 tile: the constant tile's values
+                    const int li = ry * 32 + gx + j;
+                    s_pl[0][li] = lv && w_on ? o_sdf[j] : 0.0f;
+                    s_pl[1][li] = lv && w_on ? o_app[j] : 0.0f;
+                    s_pl[2][li] = lv && w_on ? o_iso[j] : 0.0f;
+                    s_pl[3][li] = lv && w_on ? o_acc[j] : 0.0f;
+                    s_pl[4][li] = lv && w_on ? o_stem[j] : 0.0f;
+                }
+        }
+        __syncthreads();
+    }
     for (int c = 0; c < 9; c++) {
         float v[4];
         float mn = INFINITY, mx = -INFINITY;
@@ -2573,7 +2709,11 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const size_t o = o_[q];
-            float val = (c == 0) ? depth[o] : (c == 1) ? (mask[o] ? 1.0f : 0.0f) : mat[q] ? maps.p[c - 2][o] : cst;
+            float val;
+            if (DEFER && c >= 2 && c != 2 + LG_MAP_DISTANCE && c != 2 + LG_MAP_FLATNESS)   // sdf, approach | isolation | accessibility, stem
+                val = s_pl[c - 2 < LG_MAP_FLATNESS ? c - 2 : c - 2 < LG_MAP_DISTANCE ? c - 3 : c - 4][li_[q]];
+            else
+                val = (c == 0) ? depth[o] : (c == 1) ? (mask[o] ? 1.0f : 0.0f) : mat[q] ? maps.p[c - 2][o] : cst;
             v[q] = val;
             mn = fminf(mn, val);
             mx = fmaxf(mx, val);
@@ -2614,15 +2754,19 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
 
 void lg_launch_gather(const float* depth, const uint8_t* mask, const float* const* maps_host, const uint8_t* tile_state,
                       float flat_scale, int B, int H, int W, int k, const int32_t* xy, const int32_t* n, float* patches,
-                      bool haloed, hipStream_t s, const int32_t* list, const int32_t* count) {
+                      bool haloed, hipStream_t s, const int32_t* list, const int32_t* count, const LgFinalArgs* defer) {
     LgGatherMaps gm;
     for (int i = 0; i < 7; i++) gm.p[i] = maps_host[i];
-    if (haloed)
-        hipLaunchKernelGGL(lg_gather_kernel<true>, dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W, k,
-                           xy, n, patches, list, count);
+    const LgGatherNoDefer nd = {0};
+    if (defer)   // (lg_select_grasp*: haloed patches; the frames and their tile_state are those of *defer)
+        hipLaunchKernelGGL((lg_gather_kernel<true, true>), dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W, k,
+                           xy, n, patches, list, count, *defer);
+    else if (haloed)
+        hipLaunchKernelGGL((lg_gather_kernel<true, false>), dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W, k,
+                           xy, n, patches, list, count, nd);
     else
-        hipLaunchKernelGGL(lg_gather_kernel<false>, dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W,
-                           k, xy, n, patches, list, count);
+        hipLaunchKernelGGL((lg_gather_kernel<false, false>), dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W,
+                           k, xy, n, patches, list, count, nd);
 }
 
 // ============================================================================ training-sample harvesting

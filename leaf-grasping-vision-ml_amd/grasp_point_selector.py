@@ -225,6 +225,25 @@ class GraspPointSelector:
             raise RuntimeError(lib.lg_last_error(self._h).decode())
         return dict(sub_frames=int(sub_frames.value), n_sub=int(n_sub.value), counts=counts, list=lst, slot=slot, logits=logits)
 
+    def patch(self, slot):
+        """Inspection: [9, 32, 32] float32, the patch in slot `slot` of the last select call with a model loaded, as the CNN read
+        it (lg_debug_patch; slots as in cnn_survivors()['list'])."""
+        out = np.zeros((9, 32, 32), np.float32)
+        rc = lib.lg_debug_patch(self._h, int(slot), out.ctypes.data_as(C.POINTER(C.c_float)))
+        if rc != 0:
+            raise RuntimeError(lib.lg_last_error(self._h).decode())
+        return out
+
+    def ws_plane_bytes(self):
+        """Inspection: dict plane name -> bytes of device memory this handle holds for its own copy of that plane
+        (lg_debug_ws_plane_bytes).  A selector that has only made calls without return_maps holds distance_map,
+        traditional_score and flatness_map only."""
+        b = (C.c_int64 * LG_NUM_MAPS)()
+        rc = lib.lg_debug_ws_plane_bytes(self._h, b)
+        if rc != 0:
+            raise RuntimeError(lib.lg_last_error(self._h).decode())
+        return {n: int(b[i]) for i, n in enumerate(MAP_NAMES)}
+
     def _calculate_all_scores(self, leaf_mask_np, depth_tensor, image_processor=None):
         """Reference signature (:256): numpy uint8 mask in, dict of numpy planes out."""
         out, _, _ = self.score_maps(leaf_mask_np, depth_tensor, image_processor)
