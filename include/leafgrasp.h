@@ -365,6 +365,14 @@ int lg_debug_dt_form(lg_handle h, int frame, int32_t form[2]);
    other tile is constant whatever the mask.  In sparse mode lg_select_grasp* launches the plane kernel on the near tiles only
    (LG_FINAL_NEAR=0 at lg_create: on every tile, as lg_score_maps does). */
 int lg_near_tile_rect(int bx0, int bx1, int by0, int by1, int H, int W, int halo, int32_t rect[4]);
+/* A frame's sweep window on the host (no device, no handle), the code the device runs.  The bit-row pass reduces a mask to five
+   words that all start from zero: box = {max of W - 1 - x, max of x, max of H - 1 - y, max of y, number} over the set pixels
+   (the two minima are held as maxima; number 0: empty mask, whatever the other four say).  out = {wx0, wx1, wy0, wy1 (the window:
+   columns [wx0, wx1), rows [wy0, wy1)), bx0, bx1, by0, by1 (the bounding box; bx1 < bx0: empty), skip_out (the d_out sweeps have
+   nothing to add), search_in (the frame's own eligibility for the row search: search_mode != 0, not empty, at least one zero
+   pixel -- a batch may still take the sweeps), area, columns per sweep wave}.  LG_ERR_INVALID for a bad argument or a width
+   the sweeps do not take (W > 8192). */
+int lg_window_from_box(const uint32_t box[5], int H, int W, int search_mode, int32_t out[12]);
 /* off[0 .. B] = first entry of every frame's near tiles in the list the last lg_select_grasp* call on this handle launched its
    plane kernel on (off[0] = 0, off[B] = the list's length; frame b has off[b + 1] - off[b] near tiles).  cap >= B + 1.
    LG_ERR_INVALID when that call did not take the near launch (planes or validity taken back, LG_FINAL_NEAR=0, LG_SUBBATCH,

@@ -62,13 +62,12 @@ struct lg_ctx {
     int32_t* near_off_host = nullptr;
     int last_near_B = 0;             // lg_debug_near_tiles: frames of the last lg_select_grasp* call if it took the near launch, else 0
     uint32_t* maxfix = nullptr;
-    LgDtBatch* dt_batch = nullptr;   // search-or-sweeps sums of a batch (lg_bbox_kernel)
     uint8_t* mask_ws = nullptr;      // lg_select_grasp_labels: the 0 / 1 mask it derives from the labels (grown on demand)
     size_t mask_ws_cap = 0;
     int32_t* ids_dev = nullptr;      //   and the frames' leaf ids (device / pinned host staging)
     int32_t* ids_host = nullptr;
     int ids_cap = 0;
-    LgWin* win = nullptr;           // [B] sweep windows (lg_bbox_kernel)
+    LgWin* win = nullptr;           // [B] sweep windows (lg_window_kernel)
     LgFrameParams* fp_dev = nullptr;
     LgFrameParams* fp_host = nullptr;        // pinned
     unsigned long long* bits_host = nullptr;  // pinned
@@ -218,7 +217,7 @@ hipError_t dev_alloc(T** p, size_t n) {
 
 void free_ws(lg_ctx* h) {
     auto F = [](void* p) { if (p) hipFree(p); };
-    F(h->tmp); F(h->bits); F(h->stem); F(h->tilekeys); F(h->tile_state); F(h->maxfix); F(h->dt_batch); F(h->win); F(h->fp_dev);
+    F(h->tmp); F(h->bits); F(h->stem); F(h->tilekeys); F(h->tile_state); F(h->maxfix); F(h->win); F(h->fp_dev);
     for (int i = 0; i < LG_NUM_MAPS; i++) { F(h->ws_maps_base[i]); h->ws_maps_base[i] = h->ws_maps[i] = nullptr; }
     F(h->ws_valid); F(h->cand_xy); F(h->cand_n); F(h->cand_info); F(h->patches); F(h->logits);
     F(h->surv_keep); F(h->surv_list); F(h->surv_slot); F(h->surv_count);
@@ -229,7 +228,7 @@ void free_ws(lg_ctx* h) {
     HF(h->fp_host); HF(h->bits_host); HF(h->win_host); HF(h->res_host); HF(h->near_off_host);
     h->near_off_host = nullptr;
     F(h->res_dev);
-    h->tmp = nullptr; h->bits = h->stem = h->tilekeys = nullptr; h->tile_state = nullptr; h->maxfix = nullptr; h->dt_batch = nullptr; h->win = nullptr; h->fp_dev = nullptr;
+    h->tmp = nullptr; h->bits = h->stem = h->tilekeys = nullptr; h->tile_state = nullptr; h->maxfix = nullptr; h->win = nullptr; h->fp_dev = nullptr;
     h->ws_valid = nullptr; h->cand_xy = h->cand_n = nullptr; h->cand_info = h->patches = h->logits = nullptr;
     h->fp_host = nullptr; h->bits_host = nullptr; h->win_host = nullptr; h->bits_host_dev = nullptr; h->res_dev = h->res_host = nullptr;
     h->capB = h->capH = h->capW = h->capK = 0;
@@ -251,9 +250,7 @@ int ensure_ws(lg_ctx* h, int B, int H, int W, int K) {
     LG_HIP(h, dev_alloc(&h->tile_state, (size_t)nB * tiles));
     LG_HIP(h, dev_alloc(&h->near_off, (size_t)nB + 1));
     LG_HIP(h, hipHostMalloc((void**)&h->near_off_host, sizeof(int32_t) * ((size_t)nB + 1)));
-    LG_HIP(h, dev_alloc(&h->maxfix, (size_t)nB * 2));
-    LG_HIP(h, dev_alloc(&h->dt_batch, (size_t)1));
-    LG_HIP(h, hipMemset(h->dt_batch, 0, sizeof(LgDtBatch)));
+    LG_HIP(h, dev_alloc(&h->maxfix, (size_t)nB * LG_MF));
     LG_HIP(h, dev_alloc(&h->win, (size_t)nB));
     LG_HIP(h, dev_alloc(&h->fp_dev, (size_t)nB));
     LG_HIP(h, hipHostMalloc((void**)&h->fp_host, sizeof(LgFrameParams) * nB));
@@ -507,7 +504,7 @@ int lg_debug_dt_max(lg_handle h, int frame, uint32_t out[2], int32_t win[4]) {
     LG_ENTER(h);
     hipSetDevice(h->device);
     hipDeviceSynchronize();
-    if (hipMemcpy(out, h->maxfix + 2 * (size_t)frame, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(out, h->maxfix + LG_MF * (size_t)frame, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(h, LG_ERR_HIP, "lg_debug_dt_max: copy failed");
     if (win) {
         LgWin w;
@@ -615,6 +612,18 @@ int lg_near_tile_rect(int bx0, int bx1, int by0, int by1, int H, int W, int halo
     return n;
 }
 
+int lg_window_from_box(const uint32_t box[5], int H, int W, int search_mode, int32_t out[12]) {
+    int nw = 0;
+    const int wc = (H >= 1 && W >= 1) ? lg_dt_geometry(W, &nw) : 0;
+    if (!box || !out || wc == 0 || search_mode < 0 || search_mode > 2) return LG_ERR_INVALID;
+    if (box[4] != 0 && (box[0] >= (uint32_t)W || box[1] >= (uint32_t)W || box[2] >= (uint32_t)H || box[3] >= (uint32_t)H)) return LG_ERR_INVALID;
+    const LgWin w = lg_win_from_box(box, H, W, wc, nw, search_mode);
+    out[0] = w.wx0; out[1] = std::min(W, w.wx0 + w.nw * wc); out[2] = w.wy0; out[3] = w.wy1;
+    out[4] = w.bx0; out[5] = w.bx1; out[6] = w.by0; out[7] = w.by1;
+    out[8] = w.skip_out; out[9] = w.search_in; out[10] = w.area; out[11] = wc;
+    return LG_OK;
+}
+
 int lg_debug_near_tiles(lg_handle h, int32_t* off, int cap) {
     if (!h || !off) return LG_ERR_INVALID;
     LG_ENTER(h);
@@ -674,7 +683,7 @@ int enq_tail(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
     const size_t words = (size_t)pl.H * pl.WW;
     {
         ProfScope ps(h, "dt_border", s);
-        lg_launch_dout_border(h->bits + off * words, h->win + off, h->maxfix + 2 * (size_t)off, n, pl.H, pl.W, pl.WW, s);
+        lg_launch_dout_border(h->bits + off * words, h->win + off, h->maxfix + LG_MF * (size_t)off, n, pl.H, pl.W, pl.WW, s);
     }
     // (on the side stream both run before the bit-row export, which slows every concurrent memory-bound kernel 4x)
     {
@@ -693,18 +702,18 @@ int enq_tail(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
 int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_t ev_prep) {
     h->export_pending = true;
     const size_t px = (size_t)pl.H * pl.W, words = (size_t)pl.H * pl.WW;
-    LG_HIP(h, hipMemsetAsync(h->maxfix + 2 * (size_t)off, 0, sizeof(uint32_t) * 2 * n, s));
+    LG_HIP(h, hipMemsetAsync(h->maxfix + LG_MF * (size_t)off, 0, sizeof(uint32_t) * LG_MF * n, s));
     {
         ProfScope ps(h, "prep", s);
         if (pl.labels)
             lg_launch_pack_labels(pl.labels + off * px, h->ids_dev + off, h->mask_ws + off * px, h->bits + off * words, n, pl.H, pl.W,
-                                  pl.WW, s);
+                                  pl.WW, s, h->maxfix + LG_MF * (size_t)off);
         else
-            lg_launch_pack_bits(pl.mask + off * px, h->bits + off * words, n, pl.H, pl.W, pl.WW, s);
+            lg_launch_pack_bits(pl.mask + off * px, h->bits + off * words, n, pl.H, pl.W, pl.WW, s, h->maxfix + LG_MF * (size_t)off);
     }
     {
         ProfScope ps(h, "bbox", s);
-        lg_launch_bbox(h->bits + off * words, h->win + off, n, pl.H, pl.W, pl.WW, h->opt_dt_search, h->dt_batch, s);
+        lg_launch_window(h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, h->opt_dt_search, s);
     }
     LG_HIP(h, hipEventRecord(ev_prep, s));
     LG_HIP(h, hipStreamWaitEvent(h->copy_stream, ev_prep, 0));
@@ -767,7 +776,7 @@ int enq_export(lg_ctx* h, const Plan& pl, int off, int n, hipEvent_t after) {
 // forward + backward distance sweeps (+ frame-border maxima and stem bits when they do not run on the side stream)
 int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
     const size_t px = (size_t)pl.H * pl.W, words = (size_t)pl.H * pl.WW;
-    // d_in by the row search for the frames lg_bbox_kernel picked (LgWin::search_in), on a stream of its own beside the sweeps of
+    // d_in by the row search for the frames lg_window_kernel picked (LgWin::search_in), on a stream of its own beside the sweeps of
     // the other frames (and the d_out sweeps of the few frames that need them): throughput-bound work on every CU next to
     // latency-bound work on one workgroup per frame.  Inside the sub-batch pipeline (whose stages own the side streams): in line.
     hipStream_t ss = (s == h->s_dt[0] || s == h->s_dt[1]) ? s : h->s_dt[1];
@@ -780,7 +789,7 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
         const int algo = dt_algo(h, n, pl.H, pl.W);
         auto launch = [&](int phase) {
             return lg_launch_dtsearch(phase, algo, h->bits + off * words, h->tmp + 2 * off * px, pl.maps[LG_MAP_DISTANCE] + off * px,
-                                      h->maxfix + 2 * (size_t)off, h->win + off, n, pl.H, pl.W, pl.WW, ss);
+                                      h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, pl.WW, ss);
         };
         {
             ProfScope ps(h, "dt_search", ss);   // the one-level search, or the anchor rows
@@ -794,14 +803,14 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
     }
     {
         ProfScope ps(h, "dt_fwd", s);
-        if (lg_launch_dt(false, pl.mask + off * px, h->tmp + 2 * off * px, nullptr, h->maxfix + 2 * (size_t)off, h->win + off, n,
+        if (lg_launch_dt(false, pl.mask + off * px, h->tmp + 2 * off * px, nullptr, h->maxfix + LG_MF * (size_t)off, h->win + off, n,
                          pl.H, pl.W, (uint32_t)pl.P.chamfer_init_dist0, s))
             return fail(h, LG_ERR_UNSUPPORTED, "dt: width");
     }
     {
         ProfScope ps(h, "dt_bwd", s);
         lg_launch_dt(true, pl.mask + off * px, h->tmp + 2 * off * px, pl.maps[LG_MAP_DISTANCE] + off * px,
-                     h->maxfix + 2 * (size_t)off, h->win + off, n, pl.H, pl.W, (uint32_t)pl.P.chamfer_init_dist0, s);
+                     h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, (uint32_t)pl.P.chamfer_init_dist0, s);
     }
     if (h->opt_dt_search && ss != s) LG_HIP(h, hipStreamWaitEvent(s, h->ev_search, 0));
     if (!h->opt_side_tail) return enq_tail(h, pl, off, n, s);
@@ -859,7 +868,7 @@ int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upl
     LgFinalArgs a;
     memset(&a, 0, sizeof(a));
     a.depth = pl.depth + off * px; a.bits = h->bits + off * words; a.stem_bits = h->stem + off * words;
-    a.maxfix = h->maxfix + 2 * (size_t)off; a.fp = h->fp_dev + off;
+    a.maxfix = h->maxfix + LG_MF * (size_t)off; a.fp = h->fp_dev + off;
     a.win = h->win + off; a.win_wc = lg_dt_geometry(W, nullptr);
     for (int i = 0; i < LG_NUM_MAPS; i++) a.maps[i] = pl.maps[i] ? pl.maps[i] + off * px : nullptr;
     a.valid = pl.valid ? pl.valid + off * px : nullptr;
@@ -1090,10 +1099,11 @@ int lg_leaf_orientation(lg_handle h, const uint8_t* mask, int H, int W, float* o
     int rc = ensure_ws(h, 1, H, W, 20);
     if (rc) return rc;
     const int WW = (W + 63) / 64;
-    lg_launch_pack_bits(mask, h->bits, 1, H, W, WW, s);
+    LG_HIP(h, hipMemsetAsync(h->maxfix, 0, sizeof(uint32_t) * LG_MF, s));   // (the bounding box accumulates from zero)
+    lg_launch_pack_bits(mask, h->bits, 1, H, W, WW, s, h->maxfix);
     double o[5];
     if (h->orient) {   // the device analysis; a mask with more runs than its scratch holds falls through to the host code
-        lg_launch_bbox(h->bits, h->win, 1, H, W, WW, 0, nullptr, s);
+        lg_launch_window(h->maxfix, h->win, 1, H, W, 0, s);
         lg_launch_orient(h->orient, h->bits, h->win, h->fp_dev, 0, 1, H, W, WW, s);
         LG_HIP(h, hipMemcpyAsync(h->orient->h_out, h->orient->out, sizeof(double) * 5, hipMemcpyDeviceToHost, s));
         LG_HIP(h, hipMemcpyAsync(h->orient->h_status, h->orient->status, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1168,9 +1178,10 @@ int lg_detect_midrib(lg_handle h, const uint8_t* image, int C, const uint8_t* ma
     // estimate_leaf_orientation (:858) of every frame, as lg_leaf_orientation computes it
     {
         ProfScope ps(h, "midrib_orient", s);
-        lg_launch_pack_bits(mask, m->bits, B, H, W, WW, s);
+        if (m->orient) LG_HIP(h, hipMemsetAsync(m->box, 0, sizeof(uint32_t) * LG_MF * B, s));
+        lg_launch_pack_bits(mask, m->bits, B, H, W, WW, s, m->orient ? m->box : nullptr);
         if (m->orient) {
-            lg_launch_bbox(m->bits, m->win, B, H, W, WW, 0, nullptr, s);
+            lg_launch_window(m->box, m->win, B, H, W, 0, s);
             lg_launch_orient(m->orient, m->bits, m->win, m->fp, 0, B, H, W, WW, s);
             LG_HIP(h, hipMemcpyAsync(m->orient->h_out, m->orient->out, sizeof(double) * 5 * B, hipMemcpyDeviceToHost, s));
             LG_HIP(h, hipMemcpyAsync(m->orient->h_status, m->orient->status, sizeof(int) * B, hipMemcpyDeviceToHost, s));

@@ -15,12 +15,22 @@
 #define LG_INF 0x3FFFFFFFu    // "no path yet" inside the DT sweeps (never wins against a real distance)
 #define LG_NOSRC 0x20000000u  // values >= this after the backward sweep mean: image has no source pixel
 #define LG_HCAP 16383u        // run distance of a row without any zero pixel in the image (row search; W <= 8192)
-// lg_bbox_kernel, search_mode 2: a batch's d_in comes from the row search while sum over its frames of area^1.5 <= this *
+// lg_window_kernel, search_mode 2: a batch's d_in comes from the row search while sum over its frames of area^1.5 <= this *
 // (rows of its tallest bounding box)
 #ifndef LG_SEARCH_BUDGET
 #define LG_SEARCH_BUDGET 2.0e7f
 #endif
-struct LgDtBatch { unsigned long long cost; unsigned rows, done; };   // the sums behind that decision (device; lg_bbox_kernel resets them)
+// Words per frame of the `maxfix` array, zeroed by one memset in front of the bit-row pass:
+//   [0], [1]  max fixed-point d_in / d_out (atomicMax of the distance transform)
+//   [2 .. 6]  the mask's bounding box and area as the bit-row pass accumulates them (LG_BOX_*): every word is a maximum or a
+//             sum over the set bits, so all start from 0 -- the two minima are held as W - 1 - x0 and H - 1 - y0; a frame
+//             whose area stayed 0 has no set bit, whatever the other four say
+#define LG_MF 8
+#define LG_BOX_X0 2   // max of W - 1 - x
+#define LG_BOX_X1 3   // max of x
+#define LG_BOX_Y0 4   // max of H - 1 - y
+#define LG_BOX_Y1 5   // max of y
+#define LG_BOX_AREA 6 // number of set bits
 
 
 #define LG_MAX_GAUSS 15   // largest smoothing kernel lg_smooth_depth takes (the fused plane kernel: 1, 3, 5, 7)
@@ -33,7 +43,7 @@ struct LgGaussTaps { float k[LG_MAX_GAUSS]; };   // 1-D factor of ImageProcessor
                    // built with -DLG_TH=32: planes 2.60-2.71 vs 2.66-2.74 ms per 256 frames, top-k 0.33 vs 0.27 ms, dense launch the same
 #endif
 
-// Window of the distance-transform sweeps (per frame, written by lg_bbox_kernel).  The binary leaf mask covers a few
+// Window of the distance-transform sweeps (per frame, written by lg_window_kernel).  The binary leaf mask covers a few
 // per cent of a frame, so the sweeps run on the tile-aligned window around its bounding box only:
 //   d_in  (distance to the nearest zero pixel): every pixel outside the window is itself a zero pixel -> exactly 0, and
 //         enters the window as a 0-valued halo: the windowed two-pass recurrence is the full-frame one, bit for bit.
@@ -47,11 +57,55 @@ struct LgGaussTaps { float k[LG_MAX_GAUSS]; };   // 1-D factor of ImageProcessor
 struct LgWin {
     int wx0, nw, wy0, wy1;   // window: first column, active waves (64*E columns each), row range
     int bx0, bx1, by0, by1;  // bounding box of the mask (bx1 < bx0: empty mask -> window = whole frame)
-    int skip_out;            // 1: max d_out cannot lie inside the window (see lg_bbox_kernel): the d_out sweeps of this frame are skipped
+    int skip_out;            // 1: max d_out cannot lie inside the window (see lg_win_from_box): the d_out sweeps of this frame are skipped
     int search_in;           // 1: d_in of this frame comes from the row search (lg_hrun_kernel + lg_dtsearch_kernel), its d_in sweeps are skipped
     int area;                // set bits of the mask
     int pad_[1];
 };
+
+__host__ __device__ inline uint32_t lg_norm5(int dx, int dy) {   // closed-form norm of the (1, 1.4, 2.1969) chamfer mask
+    const uint32_t a = (uint32_t)(dx > dy ? dx : dy), b = (uint32_t)(dx > dy ? dy : dx);
+    return 2u * b <= a ? (a - 2u * b) * LG_A5 + b * LG_C5 : (a - b) * LG_C5 + (2u * b - a) * LG_B5;
+}
+// A frame's LgWin from the five words the bit-row pass accumulated (box = &maxfix[frame * LG_MF + LG_BOX_X0], see LG_MF).  wc,
+// nw_max: lg_dt_geometry(W).  search_in is the frame's own eligibility (search_mode != 0, a non-empty mask with at least one
+// zero pixel); lg_window_kernel clears it for the whole batch when the sweeps win (search_mode 2).  lg_window_kernel and the
+// host export lg_window_from_box run this code.
+__host__ __device__ inline LgWin lg_win_from_box(const uint32_t box[5], int H, int W, int wc, int nw_max, int search_mode) {
+    LgWin w;
+    w.area = (int)box[LG_BOX_AREA - LG_BOX_X0];
+    w.search_in = 0;
+    if (w.area == 0) {   // empty mask: no window (d_out has no source: the closed form of the whole frame applies)
+        w.bx0 = 0; w.bx1 = -1; w.by0 = 0; w.by1 = -1;
+        w.wx0 = 0; w.nw = nw_max; w.wy0 = 0; w.wy1 = H;
+        w.skip_out = 0;
+    } else {
+        w.bx0 = W - 1 - (int)box[LG_BOX_X0 - LG_BOX_X0]; w.bx1 = (int)box[LG_BOX_X1 - LG_BOX_X0];
+        w.by0 = H - 1 - (int)box[LG_BOX_Y0 - LG_BOX_X0]; w.by1 = (int)box[LG_BOX_Y1 - LG_BOX_X0];
+        // d_in by the row search (lg_dtsearch_kernel) needs a zero pixel in the image (a frame without one has OpenCV's
+        // border-initialised result, which only the sweeps produce)
+        w.search_in = (search_mode != 0 && (long long)w.area < (long long)H * W) ? 1 : 0;
+        w.wx0 = (w.bx0 / LG_TW) * LG_TW;
+        w.nw = (w.bx1 + 1 - w.wx0 + wc - 1) / wc;
+        w.wy0 = (w.by0 / LG_TH) * LG_TH;
+        const int wy1 = ((w.by1 + 1 + LG_TH - 1) / LG_TH) * LG_TH;
+        w.wy1 = wy1 < H ? wy1 : H;
+        // Only max d_out is consumed (grasp_point_selector.py:531-533).  Inside the window d_out(p) <= N(p - q) for any leaf
+        // pixel q, and both lie in the window: <= N(window width - 1, window height - 1).  At a frame corner every leaf pixel is
+        // at least the corner's gap to the bounding box away in x and in y: d_out(corner) >= N(gap_x, gap_y) (N is monotone in
+        // both).  When the best corner bound exceeds the window bound, the maximum is the frame-border maximum that
+        // lg_dout_border_kernel computes exactly, and the two d_out sweeps of this frame have nothing to add: they are skipped
+        // (the usual case: a leaf is a few hundred pixels across, the frame's far corner a thousand away).
+        const int wend = w.wx0 + w.nw * wc;
+        const int ww = (wend < W ? wend : W) - w.wx0, wh = w.wy1 - w.wy0;
+        const uint32_t ub_in = lg_norm5(ww - 1, wh - 1);
+        const int gx = w.bx0 > W - 1 - w.bx1 ? w.bx0 : W - 1 - w.bx1, gy = w.by0 > H - 1 - w.by1 ? w.by0 : H - 1 - w.by1;
+        // (strictly larger: the corner that achieves it then lies outside the window, on a border line lg_dout_border_kernel walks)
+        w.skip_out = lg_norm5(gx, gy) > ub_in ? 1 : 0;
+    }
+    w.pad_[0] = 0;
+    return w;
+}
 
 // Near tiles of a frame: the tiles of the fused score-plane kernel (LG_TW x LG_TH, stencil reach `halo` = Gaussian radius + 1)
 // whose bit-row test can meet the mask's bounding box [bx0, bx1] x [by0, by1].  The test reads columns tx0-8 .. tx0+LG_TW+7 and
@@ -148,10 +202,13 @@ struct LgFinalArgs {
 };
 
 // kernel launchers (lg_kernels.hip)
-void lg_launch_pack_bits(const uint8_t* mask, unsigned long long* bits, int B, int H, int W, int WW, hipStream_t s);
+// mf (null: bit rows only): the frames' maxfix words, zeroed by the caller: the pass adds every frame's bounding box and area
+// to mf[b * LG_MF + LG_BOX_X0 ..] (see LG_MF), at most five integer atomics per workgroup that saw a set bit
+void lg_launch_pack_bits(const uint8_t* mask, unsigned long long* bits, int B, int H, int W, int WW, hipStream_t s,
+                         uint32_t* mf = nullptr);
 // mask[b] = labels[b] == ids[b] (0 / 1 bytes) and its bit rows in one pass (ids: DEVICE, one per frame)
 void lg_launch_pack_labels(const int16_t* labels, const int32_t* ids_dev, uint8_t* mask, unsigned long long* bits, int B, int H,
-                           int W, int WW, hipStream_t s);
+                           int W, int WW, hipStream_t s, uint32_t* mf = nullptr);
 void lg_launch_export_rows(const unsigned long long* bits, const LgWin* wins, unsigned long long* dst_host_devptr, int B,
                            int H, int WW, hipStream_t s);
 void lg_launch_stem_bits(const unsigned long long* bits, unsigned long long* stem, int B, int H, int W, int WW,
@@ -160,8 +217,8 @@ void lg_launch_stem_bits(const unsigned long long* bits, unsigned long long* ste
 int lg_dt_geometry(int W, int* waves);
 // search_mode: 0 = d_in by the two sweeps for every frame, 1 = by the row search wherever it applies (a non-empty mask with
 // at least one zero pixel), 2 = the row search when the batch's estimated search work stays below the sweeps' latency
-void lg_launch_bbox(const unsigned long long* bits, LgWin* win, int B, int H, int W, int WW, int search_mode, LgDtBatch* batch,
-                    hipStream_t s);
+// mf: what lg_launch_pack_bits / lg_launch_pack_labels accumulated on the same stream
+void lg_launch_window(const uint32_t* mf, LgWin* win, int B, int H, int W, int search_mode, hipStream_t s);
 // d_in without the row-sequential sweeps (frames with LgWin::search_in): horizontal run distances of the bounding-box rows into
 // `tmp` (the d_in half of the sweep workspace, as uint16), then the bounded search over rows, which writes distance_map inside
 // the window and the maximum into maxfix[b][0]

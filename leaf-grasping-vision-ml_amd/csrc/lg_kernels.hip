@@ -113,38 +113,86 @@ __device__ __forceinline__ int lg_reflect(int v, int n) {  // torch 'reflect' in
 }
 
 // ============================================================================ mask -> bit rows
+// The pass also reduces every frame to its bounding box and area (LG_MF in lg_internal.h), from the words it holds in registers
+// anyway: grid (blocks per frame, B), so a workgroup stays inside one frame; a thread folds the set bits it packed into four
+// maxima and a count (nothing to do where it saw none -- a leaf covers a few per cent of a frame), lg_box_flush reduces them
+// over the workgroup and issues at most five integer atomics, from workgroups that saw a set bit only.
+struct LgBoxAcc {
+    uint32_t ex0 = 0, x1 = 0, ey0 = 0, y1 = 0, cnt = 0;   // max W - 1 - x, max x, max H - 1 - y, max y, set bits
+    // set bits `v` (< 2^nbits) of row y, bit j = pixel xb + j
+    __device__ __forceinline__ void add(unsigned long long v, int xb, int y, int H, int W) {
+        if (__ballot(v != 0) == 0) return;   // (most waves: nothing of this costs them more than the ballot)
+        if (v) {
+            ex0 = max(ex0, (uint32_t)(W - 1 - (xb + __builtin_ctzll(v))));
+            x1 = max(x1, (uint32_t)(xb + 63 - __builtin_clzll(v)));
+            ey0 = max(ey0, (uint32_t)(H - 1 - y));
+            y1 = max(y1, (uint32_t)y);
+            cnt += __popcll(v);
+        }
+    }
+};
+// every thread of the 256-thread workgroup calls this once, outside divergent code; s_box: 5 words of LDS
+__device__ __forceinline__ void lg_box_flush(const LgBoxAcc& a, uint32_t* s_box, uint32_t* __restrict__ mf_frame) {
+    const int t = threadIdx.x;
+    if (t < 5) s_box[t] = 0;
+    __syncthreads();
+    if (__ballot(a.cnt != 0)) {   // (wave-uniform)
+        const uint32_t ex0 = lg_wave_max_u32(a.ex0), x1 = lg_wave_max_u32(a.x1), ey0 = lg_wave_max_u32(a.ey0), y1 = lg_wave_max_u32(a.y1);
+        uint32_t c = a.cnt;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
+        if ((t & 63) == 0) {
+            atomicMax(&s_box[0], ex0); atomicMax(&s_box[1], x1); atomicMax(&s_box[2], ey0); atomicMax(&s_box[3], y1);
+            atomicAdd(&s_box[4], c);
+        }
+    }
+    __syncthreads();
+    if (t < 5 && s_box[4] != 0) {
+        if (t < 4) atomicMax(&mf_frame[LG_BOX_X0 + t], s_box[t]);
+        else atomicAdd(&mf_frame[LG_BOX_AREA], s_box[4]);
+    }
+}
+
 // bits[b][y][w] bit j = mask[b][y][64w + j] != 0.  One wave-ballot per 64 pixels.
 __global__ __launch_bounds__(256) void lg_pack_bits_kernel(const uint8_t* __restrict__ mask,
                                                            unsigned long long* __restrict__ bits, int H, int W, int WW,
-                                                           long long nwords_total) {
-    const int lane = threadIdx.x & 63;
-    long long wid = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;  // one 64-bit word per wave
-    const long long stride = ((long long)gridDim.x * 256) >> 6;
-    for (; wid < nwords_total; wid += stride) {
-        long long row = wid / WW;  // b*H + y
-        int w = (int)(wid - row * WW);
-        int x = w * 64 + lane;
-        uint8_t m = (x < W) ? mask[row * W + x] : (uint8_t)0;
+                                                           uint32_t* __restrict__ mf) {
+    __shared__ uint32_t s_box[5];
+    const int lane = threadIdx.x & 63, frame = blockIdx.y;
+    const int nwords = H * WW;                                   // of one frame
+    const uint8_t* fm = mask + (size_t)frame * H * W;
+    unsigned long long* fb = bits + (size_t)frame * nwords;
+    LgBoxAcc acc;
+    const int stride = (gridDim.x * 256) >> 6;
+    for (int wid = (blockIdx.x * 256 + threadIdx.x) >> 6; wid < nwords; wid += stride) {   // one 64-bit word per wave
+        const int row = wid / WW, w = wid - row * WW;
+        const int x = w * 64 + lane;
+        uint8_t m = (x < W) ? fm[(size_t)row * W + x] : (uint8_t)0;
         unsigned long long b = __ballot(m != 0);
-        if (lane == 0) bits[wid] = b;
+        if (lane == 0) { fb[wid] = b; if (mf) acc.add(b, w * 64, row, H, W); }
     }
+    if (mf) lg_box_flush(acc, s_box, mf + (size_t)frame * LG_MF);
 }
 
 // Vector variant (W % 16 == 0): each lane loads 16 mask bytes (1 KiB per wave instruction), four adjacent
 // lanes assemble one 64-bit word.  Slot s of a row covers pixels [16s, 16s+16); slots beyond W are empty.
 __global__ __launch_bounds__(256) void lg_pack_bits16_kernel(const uint8_t* __restrict__ mask,
-                                                             unsigned long long* __restrict__ bits, int W, int WW,
-                                                             long long nslots_total) {
-    const int slots_per_row = 4 * WW;
-    long long sid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long stride = (long long)gridDim.x * 256;  // multiple of 4: a word's four slots stay in adjacent lanes
-    for (; sid < nslots_total; sid += stride) {
-        const long long row = sid / slots_per_row;
-        const int slot = (int)(sid - row * slots_per_row);
+                                                             unsigned long long* __restrict__ bits, int H, int W, int WW,
+                                                             uint32_t* __restrict__ mf) {
+    __shared__ uint32_t s_box[5];
+    const int slots_per_row = 4 * WW, frame = blockIdx.y;
+    const int nslots = H * slots_per_row;                        // of one frame; a multiple of 4
+    const uint8_t* fm = mask + (size_t)frame * H * W;
+    unsigned long long* fb = bits + (size_t)frame * H * WW;
+    LgBoxAcc acc;
+    const int stride = gridDim.x * 256;  // multiple of 4: a word's four slots stay in adjacent lanes
+    for (int sid = blockIdx.x * 256 + threadIdx.x; sid < nslots; sid += stride) {
+        const int row = sid / slots_per_row;
+        const int slot = sid - row * slots_per_row;
         const int x = slot * 16;
         unsigned b16 = 0;
         if (x < W) {
-            const uint4 v = *reinterpret_cast<const uint4*>(mask + row * W + x);
+            const uint4 v = *reinterpret_cast<const uint4*>(fm + (size_t)row * W + x);
             const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int q = 0; q < 4; q++) {
@@ -154,31 +202,30 @@ __global__ __launch_bounds__(256) void lg_pack_bits16_kernel(const uint8_t* __re
                 b16 |= ((w4[q] & 0xff000000u) ? 8u : 0u) << (4 * q);
             }
         }
+        if (mf) acc.add(b16, x, row, H, W);   // (the lane's own 16 pixels: no wait for the shuffles)
         unsigned long long word = (unsigned long long)b16 << (16 * (slot & 3));
         word |= __shfl_xor(word, 1, 64);
         word |= __shfl_xor(word, 2, 64);
-        if ((slot & 3) == 0) bits[row * WW + (slot >> 2)] = word;
+        if ((slot & 3) == 0) fb[(size_t)row * WW + (slot >> 2)] = word;
     }
+    if (mf) lg_box_flush(acc, s_box, mf + (size_t)frame * LG_MF);
 }
 
-void lg_launch_pack_bits(const uint8_t* mask, unsigned long long* bits, int B, int H, int W, int WW, hipStream_t s) {
+// blocks per frame of a (blocks, B) grid of 256-thread workgroups over `units` threads' worth of work per frame: about `target`
+// workgroups in all, as the one-dimensional grids these kernels had
+static unsigned lg_pack_blocks(long long units, int B, long long target) {
+    const long long full = (units + 255) / 256;
+    return (unsigned)std::max<long long>(1, std::min<long long>(full, target / B));
+}
+
+void lg_launch_pack_bits(const uint8_t* mask, unsigned long long* bits, int B, int H, int W, int WW, hipStream_t s, uint32_t* mf) {
     if ((W & 15) == 0 && ((uintptr_t)mask & 15) == 0) {
-        long long nslots = (long long)B * H * WW * 4;
-        long long blocks = (nslots + 255) / 256;
-        if (blocks > 16384) blocks = 16384;
-        // all lanes of a wave must run the same number of iterations (shuffles): pad the slot space
-        long long per_iter = blocks * 256;
-        long long padded = ((nslots + per_iter - 1) / per_iter) * per_iter;
-        (void)padded;
-        hipLaunchKernelGGL(lg_pack_bits16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, mask, bits, W, WW, nslots);
+        hipLaunchKernelGGL(lg_pack_bits16_kernel, dim3(lg_pack_blocks((long long)H * WW * 4, B, 16384), B), dim3(256), 0, s, mask, bits,
+                           H, W, WW, mf);
         return;
     }
-    long long nwords = (long long)B * H * WW;
-    long long waves = nwords;
-    int blocks = (int)((waves + 3) / 4);
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(lg_pack_bits_kernel, dim3(blocks), dim3(256), 0, s, mask, bits, H, W, WW, nwords);
+    hipLaunchKernelGGL(lg_pack_bits_kernel, dim3(lg_pack_blocks((long long)H * WW * 64, B, 8192), B), dim3(256), 0, s, mask, bits, H, W,
+                       WW, mf);
 }
 
 // The node's `optimal_mask = mask_tensor == optimal_leaf_id` (leaf_grasp_node_v3.py:118) folded into the bit-row pass: labels
@@ -187,19 +234,24 @@ void lg_launch_pack_bits(const uint8_t* mask, unsigned long long* bits, int B, i
 // labels (two 16-byte loads), four adjacent lanes assemble a word; W % 16 == 0 (the launcher falls back otherwise).
 __global__ __launch_bounds__(256) void lg_pack_labels16_kernel(const int16_t* __restrict__ labels, const int32_t* __restrict__ ids,
                                                                uint8_t* __restrict__ mask, unsigned long long* __restrict__ bits,
-                                                               int H, int W, int WW, long long nslots_total) {
-    const int slots_per_row = 4 * WW;
-    long long sid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long stride = (long long)gridDim.x * 256;  // multiple of 4: a word's four slots stay in adjacent lanes
-    for (; sid < nslots_total; sid += stride) {
-        const long long row = sid / slots_per_row;
-        const int slot = (int)(sid - row * slots_per_row);
+                                                               int H, int W, int WW, uint32_t* __restrict__ mf) {
+    __shared__ uint32_t s_box[5];
+    const int slots_per_row = 4 * WW, frame = blockIdx.y;
+    const int nslots = H * slots_per_row;                        // of one frame; a multiple of 4
+    const int16_t* fl = labels + (size_t)frame * H * W;
+    uint8_t* fm = mask + (size_t)frame * H * W;
+    unsigned long long* fb = bits + (size_t)frame * H * WW;
+    const int id = ids[frame];
+    LgBoxAcc acc;
+    const int stride = gridDim.x * 256;  // multiple of 4: a word's four slots stay in adjacent lanes
+    for (int sid = blockIdx.x * 256 + threadIdx.x; sid < nslots; sid += stride) {
+        const int row = sid / slots_per_row;
+        const int slot = sid - row * slots_per_row;
         const int x = slot * 16;
         unsigned b16 = 0;
         if (x < W) {
-            const int id = ids[row / H];
-            const uint4 v0 = *reinterpret_cast<const uint4*>(labels + row * W + x);
-            const uint4 v1 = *reinterpret_cast<const uint4*>(labels + row * W + x + 8);
+            const uint4 v0 = *reinterpret_cast<const uint4*>(fl + (size_t)row * W + x);
+            const uint4 v1 = *reinterpret_cast<const uint4*>(fl + (size_t)row * W + x + 8);
             const uint32_t w8[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
             uint32_t mb[4];
 #pragma unroll
@@ -209,13 +261,15 @@ __global__ __launch_bounds__(256) void lg_pack_labels16_kernel(const int16_t* __
                 const uint32_t two = lo | (hi << 8);
                 if (q & 1) mb[q >> 1] |= two << 16; else mb[q >> 1] = two;
             }
-            *reinterpret_cast<uint4*>(mask + row * W + x) = make_uint4(mb[0], mb[1], mb[2], mb[3]);
+            *reinterpret_cast<uint4*>(fm + (size_t)row * W + x) = make_uint4(mb[0], mb[1], mb[2], mb[3]);
         }
+        if (mf) acc.add(b16, x, row, H, W);
         unsigned long long word = (unsigned long long)b16 << (16 * (slot & 3));
         word |= __shfl_xor(word, 1, 64);
         word |= __shfl_xor(word, 2, 64);
-        if ((slot & 3) == 0) bits[row * WW + (slot >> 2)] = word;
+        if ((slot & 3) == 0) fb[(size_t)row * WW + (slot >> 2)] = word;
     }
+    if (mf) lg_box_flush(acc, s_box, mf + (size_t)frame * LG_MF);
 }
 __global__ __launch_bounds__(256) void lg_labels_mask_kernel(const int16_t* __restrict__ labels, const int32_t* __restrict__ ids,
                                                              uint8_t* __restrict__ mask, long long px_per_frame, long long total) {
@@ -223,18 +277,16 @@ __global__ __launch_bounds__(256) void lg_labels_mask_kernel(const int16_t* __re
         mask[i] = (int)labels[i] == ids[i / px_per_frame] ? 1 : 0;
 }
 void lg_launch_pack_labels(const int16_t* labels, const int32_t* ids_dev, uint8_t* mask, unsigned long long* bits, int B, int H,
-                           int W, int WW, hipStream_t s) {
+                           int W, int WW, hipStream_t s, uint32_t* mf) {
     if ((W & 15) == 0 && ((uintptr_t)labels & 15) == 0 && ((uintptr_t)mask & 15) == 0) {
-        const long long nslots = (long long)B * H * WW * 4;
-        long long blocks = (nslots + 255) / 256;
-        if (blocks > 16384) blocks = 16384;
-        hipLaunchKernelGGL(lg_pack_labels16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, labels, ids_dev, mask, bits, H, W, WW, nslots);
+        hipLaunchKernelGGL(lg_pack_labels16_kernel, dim3(lg_pack_blocks((long long)H * WW * 4, B, 16384), B), dim3(256), 0, s, labels,
+                           ids_dev, mask, bits, H, W, WW, mf);
         return;
     }
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(lg_labels_mask_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 16384)), dim3(256), 0, s, labels,
                        ids_dev, mask, (long long)H * W, total);
-    lg_launch_pack_bits(mask, bits, B, H, W, WW, s);
+    lg_launch_pack_bits(mask, bits, B, H, W, WW, s, mf);
 }
 
 // Export of the bits the host needs -- the rows and 64-bit words of each frame's bounding box only (a leaf spans a third
@@ -328,113 +380,56 @@ void lg_launch_stem_bits(const unsigned long long* bits, unsigned long long* ste
 }
 
 // ============================================================================ sweep window (mask bounding box)
-__device__ __forceinline__ uint32_t lg_norm5(int dx, int dy) {   // closed-form norm of the (1, 1.4, 2.1969) chamfer mask
-    const uint32_t a = (uint32_t)max(dx, dy), b = (uint32_t)min(dx, dy);
-    return 2u * b <= a ? (a - 2u * b) * LG_A5 + b * LG_C5 : (a - b) * LG_C5 + (2u * b - a) * LG_B5;
-}
-// One workgroup per frame over the bit rows: bounding box of the set bits -> LgWin (see lg_internal.h).  1024 threads, four per
-// row (words q, q + 4, ...: the four read 32 adjacent bytes): a thread's loads are a dependent chain, and with one thread per
-// row and 256 threads the kernel took 44 us for ONE frame -- 6 % of a single-frame call.
+// One workgroup, thread = frame (frames t, t + 1024, ...): LgWin of every frame (lg_win_from_box, lg_internal.h) from the bounding
+// box and area the bit-row pass left in the frame's maxfix words.
 //
 // Search or sweeps is decided for the BATCH (search_mode 2): the search's time grows like the sum over the frames of area^1.5
 // (pixels x their depth), the sweeps' like the rows of the tallest window whatever the batch (one workgroup per frame, all at
 // once) -- and a batch of which one half is searched while the other half is swept takes as long as both together (measured:
 // 1.1 ms per 256 benchmark frames against 0.7 either way; the two forms do not run beside each other as their streams suggest).
-// Every workgroup adds its frame to the batch's sums; the last one to finish compares them and, if the sweeps win, clears
-// the flags of all frames (and resets the sums for the next launch).
-__global__ __launch_bounds__(1024) void lg_bbox_kernel(const unsigned long long* __restrict__ bits, LgWin* __restrict__ wins,
-                                                       int H, int W, int WW, int wc, int nw_max, int search_mode, float search_budget,
-                                                       LgDtBatch* __restrict__ bt) {
-    __shared__ int s_b[5];
-    __shared__ int s_last;
-    const int frame = blockIdx.x, t = threadIdx.x;
-    if (t == 0) { s_b[0] = INT_MAX; s_b[1] = -1; s_b[2] = INT_MAX; s_b[3] = -1; s_b[4] = 0; }
-    __syncthreads();
-    const unsigned long long* fb = bits + (size_t)frame * H * WW;
-    int x0 = INT_MAX, x1 = -1, y0 = INT_MAX, y1 = -1, cnt = 0;
-    for (int y = t >> 2; y < H; y += 256) {
-        const unsigned long long* row = fb + (size_t)y * WW;
-        int first = INT_MAX, last = -1;
-        for (int w = t & 3; w < WW; w += 4) {
-            const unsigned long long v = row[w];
-            if (v) {
-                first = min(first, 64 * w + __builtin_ctzll(v));
-                last = max(last, 64 * w + 63 - __builtin_clzll(v));
-                cnt += __popcll(v);
-            }
-        }
-        if (last >= 0) { x0 = min(x0, first); x1 = max(x1, last); y0 = min(y0, y); y1 = max(y1, y); }
-    }
-    if (x1 >= 0) {
-        atomicMin(&s_b[0], x0); atomicMax(&s_b[1], x1);
-        atomicMin(&s_b[2], y0); atomicMax(&s_b[3], y1);
-        atomicAdd(&s_b[4], cnt);
-    }
-    __syncthreads();
-    if (t == 0) {
-        LgWin w;
-        w.bx0 = s_b[0]; w.bx1 = s_b[1]; w.by0 = s_b[2]; w.by1 = s_b[3];
-        w.area = s_b[4];
-        w.search_in = 0;
-        if (w.bx1 < 0) {   // empty mask: no window (d_out has no source: the closed form of the whole frame applies)
-            w.bx0 = 0; w.bx1 = -1; w.by0 = 0; w.by1 = -1;
-            w.wx0 = 0; w.nw = nw_max; w.wy0 = 0; w.wy1 = H;
-            w.skip_out = 0;
-        } else {
-            // d_in by the row search (lg_dtsearch_kernel) needs a zero pixel in the image (a frame without one has OpenCV's
-            // border-initialised result, which only the sweeps produce); its work grows like area^1.5 (pixels x their depth)
-            // while the sweeps' time is set by the window's rows: `search_limit` is where the two meet for this batch.
-            w.search_in = (search_mode != 0 && (long long)w.area < (long long)H * W) ? 1 : 0;
-            if (search_mode == 2 && w.search_in) {
+// The per-frame costs are integers: the workgroup sums them (and takes the tallest box) through LDS, and every thread takes
+// the same decision before it writes its frames; if the sweeps win, no frame is searched.
+__global__ __launch_bounds__(1024) void lg_window_kernel(const uint32_t* __restrict__ mf, LgWin* __restrict__ wins, int B, int H, int W,
+                                                         int wc, int nw_max, int search_mode, float search_budget) {
+    __shared__ unsigned long long s_cost;
+    __shared__ unsigned s_rows;
+    const int t = threadIdx.x;
+    bool sweeps = false;
+    if (search_mode == 2) {
+        if (t == 0) { s_cost = 0; s_rows = 0; }
+        __syncthreads();
+        unsigned long long cost = 0;
+        unsigned rows = 0;
+        for (int f = t; f < B; f += 1024) {
+            const LgWin w = lg_win_from_box(mf + (size_t)f * LG_MF + LG_BOX_X0, H, W, wc, nw_max, search_mode);
+            if (w.search_in) {
+                // its work grows like area^1.5 (pixels x their depth) while the sweeps' time is set by the window's rows
                 const float a = (float)w.area;
-                atomicAdd(&bt->cost, (unsigned long long)(a * __builtin_sqrtf(a)));
-                atomicMax(&bt->rows, (unsigned)(w.by1 - w.by0 + 1));
+                cost += (unsigned long long)(a * __builtin_sqrtf(a));
+                rows = max(rows, (unsigned)(w.by1 - w.by0 + 1));
             }
-            w.wx0 = (w.bx0 / LG_TW) * LG_TW;
-            w.nw = (w.bx1 + 1 - w.wx0 + wc - 1) / wc;
-            w.wy0 = (w.by0 / LG_TH) * LG_TH;
-            w.wy1 = min(H, ((w.by1 + 1 + LG_TH - 1) / LG_TH) * LG_TH);
-            // Only max d_out is consumed (grasp_point_selector.py:531-533).  Inside the window d_out(p) <= N(p - q) for any leaf
-            // pixel q, and both lie in the window: <= N(window width - 1, window height - 1).  At a frame corner every leaf pixel is
-            // at least the corner's gap to the bounding box away in x and in y: d_out(corner) >= N(gap_x, gap_y) (N is monotone in
-            // both).  When the best corner bound exceeds the window bound, the maximum is the frame-border maximum that
-            // lg_dout_border_kernel computes exactly, and the two d_out sweeps of this frame have nothing to add: they are skipped
-            // (the usual case: a leaf is a few hundred pixels across, the frame's far corner a thousand away).
-            const int ww = min(W, w.wx0 + w.nw * wc) - w.wx0, wh = w.wy1 - w.wy0;
-            const uint32_t ub_in = lg_norm5(ww - 1, wh - 1);
-            const int gx = max(w.bx0, W - 1 - w.bx1), gy = max(w.by0, H - 1 - w.by1);
-            // (strictly larger: the corner that achieves it then lies outside the window, on a border line lg_dout_border_kernel walks)
-            w.skip_out = lg_norm5(gx, gy) > ub_in ? 1 : 0;
         }
-        w.pad_[0] = 0;
-        wins[frame] = w;
-        s_last = 0;
-        if (search_mode == 2) {
-            __threadfence();
-            s_last = atomicAdd(&bt->done, 1u) == gridDim.x - 1 ? 1 : 0;
-        }
+        if (cost) atomicAdd(&s_cost, cost);
+        if (rows) atomicMax(&s_rows, rows);
+        __syncthreads();
+        sweeps = (float)s_cost > search_budget * (float)s_rows;
     }
-    __syncthreads();
-    if (s_last) {   // (one workgroup of the launch; every other one has published its frame and its sums)
-        __threadfence();
-        const unsigned long long cost = atomicAdd(&bt->cost, 0ull);
-        const unsigned rows = atomicMax(&bt->rows, 0u);
-        if ((float)cost > search_budget * (float)rows)
-            for (int f = t; f < (int)gridDim.x; f += 1024) wins[f].search_in = 0;
-        if (t == 0) { bt->cost = 0; bt->rows = 0; bt->done = 0; }
+    for (int f = t; f < B; f += 1024) {
+        LgWin w = lg_win_from_box(mf + (size_t)f * LG_MF + LG_BOX_X0, H, W, wc, nw_max, search_mode);
+        if (sweeps) w.search_in = 0;
+        wins[f] = w;
     }
 }
 
-void lg_launch_bbox(const unsigned long long* bits, LgWin* win, int B, int H, int W, int WW, int search_mode, LgDtBatch* batch,
-                    hipStream_t s) {
+void lg_launch_window(const uint32_t* mf, LgWin* win, int B, int H, int W, int search_mode, hipStream_t s) {
     int nw = 0;
     const int wc = lg_dt_geometry(W, &nw);
     // mode 2: search while sum over the frames of area^1.5 <= LG_SEARCH_BUDGET * rows of the tallest window: 0.69 ms for 256
     // benchmark leaves of 100 k pixels in either form (anchors + bands; sweeps: ~1.6 us per row).  LG_DT_SEARCH_BUDGET=<x>
     // replaces the constant (experiments).
     static const float env_budget = getenv("LG_DT_SEARCH_BUDGET") ? (float)atof(getenv("LG_DT_SEARCH_BUDGET")) : 0.0f;
-    hipLaunchKernelGGL(lg_bbox_kernel, dim3(B), dim3(1024), 0, s, bits, win, H, W, WW, wc, nw, search_mode,
-                       env_budget > 0.0f ? env_budget : LG_SEARCH_BUDGET, batch);
+    hipLaunchKernelGGL(lg_window_kernel, dim3(1), dim3(1024), 0, s, mf, win, B, H, W, wc, nw, search_mode,
+                       env_budget > 0.0f ? env_budget : LG_SEARCH_BUDGET);
 }
 
 // ============================================================================ max d_out outside the sweep window
@@ -513,7 +508,7 @@ __global__ __launch_bounds__(256) void lg_dout_border_kernel(const unsigned long
         best = max(best, dmin);
     }
     best = lg_wave_max_u32(best);
-    if ((t & 63) == 0 && best) atomicMax(&maxfix[frame * 2 + 1], best);
+    if ((t & 63) == 0 && best) atomicMax(&maxfix[frame * LG_MF + 1], best);
 }
 
 void lg_launch_dout_border(const unsigned long long* bits, const LgWin* win, uint32_t* maxfix, int B, int H, int W, int WW,
@@ -547,7 +542,7 @@ __global__ __launch_bounds__(T) void lg_dt5_kernel(const uint8_t* __restrict__ m
     const LgWin win = wins[frame];
     const int nwa = win.nw;
     if (wave >= nwa) return;
-    if (which == 1 && win.skip_out) return;   // max d_out lies on the frame border (lg_bbox_kernel): whole workgroup, before any barrier
+    if (which == 1 && win.skip_out) return;   // max d_out lies on the frame border (lg_win_from_box): whole workgroup, before any barrier
     if (which == 0 && win.search_in) return;  // d_in of this frame comes from lg_dtsearch_kernel
     const int wx0 = win.wx0, wxe = wx0 + nwa * WC;   // window columns [wx0, wxe); columns >= W are outside the image
     const int wy0 = win.wy0, HW = win.wy1 - win.wy0; // window rows
@@ -767,7 +762,7 @@ __global__ __launch_bounds__(T) void lg_dt5_kernel(const uint8_t* __restrict__ m
     }
     if (BWD) {
         mx = lg_wave_max_u32(mx);
-        if (lane == 0) atomicMax(&maxfix[frame * 2 + which], mx);
+        if (lane == 0) atomicMax(&maxfix[frame * LG_MF + which], mx);
     }
 }
 
@@ -1032,7 +1027,7 @@ __global__ __launch_bounds__(256) void lg_dtsearch_kernel(const unsigned long lo
         }
     }
     mx = lg_wave_max_u32(mx);
-    if (lane == 0 && mx) atomicMax(&maxfix[frame * 2 + 0], mx);
+    if (lane == 0 && mx) atomicMax(&maxfix[frame * LG_MF + 0], mx);
 }
 
 // ---- the same search in two levels.  Along a column the minimising row is monotone in y: for two candidate rows r1 < r2,
@@ -1146,7 +1141,7 @@ __global__ __launch_bounds__(256) void lg_dtanchor_kernel(const unsigned long lo
         }
     }
     mx = lg_wave_max_u32(mx);
-    if (lane == 0 && mx) atomicMax(&maxfix[frame * 2 + 0], mx);
+    if (lane == 0 && mx) atomicMax(&maxfix[frame * LG_MF + 0], mx);
 }
 
 __device__ __forceinline__ int lg_wave_min_i32(int v) {
@@ -1314,7 +1309,7 @@ __global__ __launch_bounds__(256) void lg_dtlevel_kernel(const unsigned long lon
         }
     }
     mx = lg_wave_max_u32(mx);
-    if (lane == 0 && mx) atomicMax(&maxfix[frame * 2 + 0], mx);
+    if (lane == 0 && mx) atomicMax(&maxfix[frame * LG_MF + 0], mx);
 }
 
 static int lg_search_groups(int B, int per_batch, int lo, int hi) {
@@ -1834,7 +1829,7 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
 
     // ---- per-pixel planes
     const __attribute__((address_space(4))) LgFrameParams* fpp = (const __attribute__((address_space(4))) LgFrameParams*)(ap->fp + frame);
-    const __attribute__((address_space(4))) uint32_t* mfp = (const __attribute__((address_space(4))) uint32_t*)(ap->maxfix + frame * 2);
+    const __attribute__((address_space(4))) uint32_t* mfp = (const __attribute__((address_space(4))) uint32_t*)(ap->maxfix + frame * LG_MF);
     const LgPixFrame pf = lg_pix_frame(ap, fpp, mfp);
     unsigned long long best = 0;
 #pragma unroll
@@ -2325,11 +2320,18 @@ __global__ __launch_bounds__(256) void lg_tilekeys_kernel(const float* __restric
 //                  suppress every pixel within Chebyshev distance 2*min_dist of the pick }.
 // Equivalent to the reference's greedy walk over the descending argsort (a pixel is accepted iff its
 // (2d+1)^2 window meets no earlier window, i.e. iff it is > 2d away from every accepted point).
-// One 1024-thread workgroup per frame; per-tile maxima live in LDS and only the tiles touched by a new suppression
+// One LG_TOPK_T-thread workgroup per frame; per-tile maxima live in LDS and only the tiles touched by a new suppression
 // window (<= 8 of 64x16 pixels for the reference's 41x41 window; any number for larger min_distance) are recomputed.
 // tile_state (sparse planes): a tile with state 0 has no trad / valid written; its pixels are read as the constant tile's
 // (trad = w_flat * lg_const_flat(flat_scale), valid = 0) -- the same keys, tie rule included, as the written planes give.
-#define LG_TOPK_T 1024
+//
+// A round of the usual case (window on <= 8 tiles, W % 4 == 0) is two barriers around one round trip to L2:
+//   arg-max of the tile keys -> s_best[r & 1] | barrier 1 | pick; one WAVE per touched tile recomputes its key -> s_keys | barrier 2
+// The picks so far live in registers (lane q of every wave holds pick q), so the round reads no pick from LDS; s_cx / s_cy
+// are written for the general form and the tail only.
+#ifndef LG_TOPK_T
+#define LG_TOPK_T 512   // 8 waves = one per tile of a 41 x 41 window (measured against 256 and 1024: profiles/NOTES_topk_chain.md)
+#endif
 #define LG_MAX_TILES 8192
 #define LG_MAX_K 64
 __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restrict__ trad,
@@ -2342,13 +2344,16 @@ __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restr
                                                             int32_t* __restrict__ out_xy, int32_t* __restrict__ out_n,
                                                             float* __restrict__ out_info,
                                                             unsigned long long* __restrict__ keep, int mask_is_bool) {
+    static_assert(LG_TOPK_T % 64 == 0 && LG_TOPK_T >= 64 && (LG_TW * LG_TH) % LG_TOPK_T == 0, "whole waves; whole chunks per tile");
+    static_assert(LG_TW == 64 && LG_TH == 16, "fast path: a wave takes a tile as 16 rows x 4 lanes x 16 pixels");
+    constexpr int NW = LG_TOPK_T / 64;
     __shared__ unsigned long long s_keys[LG_MAX_TILES];
     __shared__ uint8_t s_state[LG_MAX_TILES];   // 1: the tile's planes were written (every tile when tile_state is null)
-    __shared__ unsigned long long s_best;
+    __shared__ unsigned long long s_best[2];    // the round's arg-max, by round parity
     __shared__ int s_cx[LG_MAX_K], s_cy[LG_MAX_K];
     const int frame = blockIdx.x;
     const int ntile = tiles_x * tiles_y;
-    const int t = threadIdx.x;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const size_t fo = (size_t)frame * H * W;
     const int sup = 2 * md;
     const float inv_w = __frcp_rn((float)W);
@@ -2357,16 +2362,18 @@ __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restr
         s_state[i] = tile_state ? tile_state[(size_t)frame * ntile + i] : 1;
     }
     const float trad1 = w_flat * lg_const_flat(flat_scale);   // traditional score of a constant tile
-    if (t == 0) s_best = 0;
+    if (t < 2) s_best[t] = 0;
     __syncthreads();
     int n = 0;
+    int pcx = 0, pcy = 0;   // lane q of every wave: pick q (q <= the current round; k <= 64)
     for (int r = 0; r < k; r++) {
+        const int par = r & 1;
         unsigned long long b = 0;
         for (int i = t; i < ntile; i += LG_TOPK_T) b = s_keys[i] > b ? s_keys[i] : b;
         b = lg_wave_max_u64(b);
-        if ((t & 63) == 0 && b) atomicMax(&s_best, b);
-        __syncthreads();
-        const unsigned long long bk = s_best;
+        if (lane == 0 && b) atomicMax(&s_best[par], b);
+        __syncthreads();   // barrier 1: s_best[par] complete; every read of s_keys of this round is done
+        const unsigned long long bk = s_best[par];
         if (bk == 0) break;  // every pixel is suppressed
         const int idx = (int)(uint32_t)(bk & 0xffffffffull);
         // idx < 2^24 (at most 8192 tiles of 1024 pixels): the float quotient is within 1 of idx / W
@@ -2378,80 +2385,94 @@ __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restr
             s_cx[r] = px; s_cy[r] = py;
             out_xy[((size_t)frame * k + r) * 2 + 0] = px;
             out_xy[((size_t)frame * k + r) * 2 + 1] = py;
+            // No barrier between the read of s_best above and its reset: the round's arg-max alternates between two words.
+            // s_best[par ^ 1] was last read behind barrier 1 of round r - 1, and every thread has since passed barrier 1 of this
+            // round; it is next written (atomicMax of round r + 1) behind the barrier that ends this round, which this thread
+            // reaches after the store.  s_best[par] itself is not written again before round r + 2's reset in round r + 1.
+            s_best[par ^ 1] = 0;
         }
+        if (lane == r) { pcx = px; pcy = py; }
         n = r + 1;
         // tiles touched by the new suppression window
         const int tx_lo = max(px - sup, 0) / LG_TW, tx_hi = min(px + sup, W - 1) / LG_TW;
         const int ty_lo = max(py - sup, 0) / LG_TH, ty_hi = min(py + sup, H - 1) / LG_TH;
         const int ntx = tx_hi - tx_lo + 1, nty = ty_hi - ty_lo + 1;
         const int naff = ntx * nty;
-        __syncthreads();  // s_cx/s_cy visible; everyone has read s_best
-        if (t == 0) s_best = 0;
-        for (int i = t; i < naff; i += LG_TOPK_T)   // any window size: a large min_distance touches > 1024 tiles
+        if (naff <= 8 && (W & 3) == 0) {
+            // The usual case (min_distance 10: a 41 x 41 window touches at most 2 x 4 tiles), kept short: the whole kernel runs on
+            // ONE CU per frame and every round is a dependent chain, so what counts is the instructions each SIMD issues per round.
+            // One wave per touched tile; lane: row lane >> 2 of the tile, 16 consecutive pixels: four 16-byte score loads + four
+            // 4-byte validity loads, all issued before anything is looked at.  The wave owns the tile's key: a plain store of the
+            // wave's arg-max replaces clear + barrier + atomicMax -- nobody else writes s_keys[tile] in this round, the reads of
+            // this round's arg-max lie in front of barrier 1, those of the next round behind barrier 2.
+            for (int ta = wave; ta < naff; ta += NW) {       // (wave-uniform)
+                int ry = 0, rx = ta;
+                while (rx >= ntx) { rx -= ntx; ry++; }       // (ntx <= 8: a few wave-uniform iterations instead of a division)
+                const int tile = (ty_lo + ry) * tiles_x + tx_lo + rx;
+                const int tx0 = (tx_lo + rx) * LG_TW, ty0 = (ty_lo + ry) * LG_TH;
+                const int y = ty0 + (lane >> 2), x0 = tx0 + (lane & 3) * 16;
+                const bool in = y < H && x0 < W;
+                const size_t o = in ? fo + (size_t)y * W + x0 : fo;
+                // W % 4 == 0: groups of four pixels are inside or outside as a whole; a group outside loads pixel 0 of the frame
+                uint32_t inm = 0;
+#pragma unroll
+                for (int g = 0; g < 4; g++) inm |= (in && x0 + 4 * g < W) ? 0xFu << (4 * g) : 0u;
+                float4 s4[4];
+                uint32_t v4[4];
+                if (s_state[tile] != 0) {                    // (uniform over the wave)
+#pragma unroll
+                    for (int g = 0; g < 4; g++) {
+                        const size_t og = (inm >> (4 * g)) & 1u ? o + 4 * g : fo;
+                        s4[g] = *reinterpret_cast<const float4*>(trad + og);
+                        v4[g] = *reinterpret_cast<const uint32_t*>(valid + og);
+                    }
+                } else {
+#pragma unroll
+                    for (int g = 0; g < 4; g++) { s4[g] = make_float4(trad1, trad1, trad1, trad1); v4[g] = 0u; }
+                }
+                // earlier picks (this round's included) whose window reaches this tile: one ballot over the lanes that hold them;
+                // each leaves one interval of this lane's 16 pixels dead
+                const unsigned long long rel = __ballot(lane <= r && pcx + sup >= tx0 && pcx - sup <= tx0 + LG_TW - 1 &&
+                                                        pcy + sup >= ty0 && pcy - sup <= ty0 + LG_TH - 1);
+                uint32_t dead = 0;
+                for (unsigned long long m = rel; m; m &= m - 1) {
+                    const int q = __builtin_ctzll(m);
+                    const int cxq = __builtin_amdgcn_readlane(pcx, q), cyq = __builtin_amdgcn_readlane(pcy, q);
+                    const int lo = max(cxq - sup - x0, 0), hi = min(cxq + sup - x0, 15);
+                    dead |= (lo <= hi && abs(y - cyq) <= sup) ? (2u << hi) - (1u << lo) : 0u;
+                }
+                const uint32_t alive = inm & ~dead;
+                const float sc[16] = {s4[0].x, s4[0].y, s4[0].z, s4[0].w, s4[1].x, s4[1].y, s4[1].z, s4[1].w,
+                                      s4[2].x, s4[2].y, s4[2].z, s4[2].w, s4[3].x, s4[3].y, s4[3].z, s4[3].w};
+                // the lane's arg-max: orderable(anything alive) >= 0x007fffff > 0, zero = suppressed / outside the image; the flat
+                // index grows with j, so `>=` gives a tie to the higher index
+                uint32_t bs = 0, bj = 0;
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    const uint32_t vb = (v4[j >> 2] >> (8 * (j & 3))) & 0xffu;
+                    const uint32_t v = (alive >> j) & 1u ? lg_orderable(lg_valid_score(sc[j], vb != 0)) : 0u;
+                    if (v >= bs) { bs = v; bj = j; }
+                }
+                // ... and the wave's: the flat index grows with the lane too (row-major, four lanes per row)
+                const unsigned long long best = lg_wave_argmax_lane_ordered(bs, (uint32_t)(y * W + x0) + bj);
+                if (lane == 0) s_keys[tile] = best;
+            }
+            __syncthreads();   // barrier 2: the touched tiles' keys are in place for the next round's arg-max
+            continue;
+        }
+        __syncthreads();  // s_cx/s_cy visible
+        for (int i = t; i < naff; i += LG_TOPK_T)   // any window size: a large min_distance touches more tiles than there are threads
             s_keys[(ty_lo + i / ntx) * tiles_x + tx_lo + i % ntx] = 0;
         __syncthreads();
         // earlier picks whose suppression window reaches the affected tiles at all (usually the new pick and a neighbour or
-        // two): the per-pixel test below walks these, not all r + 1 picks -- at the late rounds that test was most of the round
+        // two): the per-pixel test below walks these, not all r + 1 picks
         unsigned long long rel = 0;
         {
             const int xlo = tx_lo * LG_TW, xhi = tx_hi * LG_TW + LG_TW - 1, ylo = ty_lo * LG_TH, yhi = ty_hi * LG_TH + LG_TH - 1;
             for (int q = 0; q <= r; q++)
                 if (s_cx[q] + sup >= xlo && s_cx[q] - sup <= xhi && s_cy[q] + sup >= ylo && s_cy[q] - sup <= yhi) rel |= 1ull << q;
         }
-        constexpr int TPT = LG_TOPK_T / 8;                 // threads per tile on the fast path: 8 tiles x 128 threads x 8 pixels
-        static_assert(LG_TW * LG_TH == 8 * TPT, "one tile = 128 threads x 8 pixels");
-        if (naff <= 8 && (W & 3) == 0) {
-            // The usual case (min_distance 10: a 41 x 41 window touches at most 2 x 4 tiles), kept short: the whole kernel runs on
-            // ONE CU per frame, every round is a dependent chain, and the general form below spent ~2500 instructions per wave and
-            // round on per-chunk index arithmetic (runtime divisions) -- 15 us of instruction issue per round, 0.3 ms per call at
-            // any batch size.  Thread t: tile t >> 7 of the window, row (t & 127) >> 3, eight consecutive pixels: two 16-byte score
-            // loads + one 8-byte validity load, all issued before anything is looked at.
-            const int ta = t >> 7, u = t & 127;
-            if (ta < naff) {
-                int ry = 0, rx = ta;
-                while (rx >= ntx) { rx -= ntx; ry++; }       // (ntx <= 8: a few wave-uniform iterations instead of a division)
-                const int tile = (ty_lo + ry) * tiles_x + tx_lo + rx;
-                const int y = (ty_lo + ry) * LG_TH + (u >> 3), x0 = (tx_lo + rx) * LG_TW + (u & 7) * 8;
-                unsigned long long best = 0;
-                if (y < H && x0 < W) {
-                    const size_t o = fo + (size_t)y * W + x0;
-                    const bool two = x0 + 4 < W;             // W % 4 == 0: groups of four pixels are inside or outside as a whole
-                    const bool mat = s_state[tile] != 0;     // (uniform over the tile's two waves)
-                    float4 s0 = make_float4(trad1, trad1, trad1, trad1), s1 = s0;
-                    uint32_t v0 = 0u, v1 = 0u;
-                    if (mat) {
-                        s0 = *reinterpret_cast<const float4*>(trad + o);
-                        s1 = two ? *reinterpret_cast<const float4*>(trad + o + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                        v0 = *reinterpret_cast<const uint32_t*>(valid + o);
-                        v1 = two ? *reinterpret_cast<const uint32_t*>(valid + o + 4) : 0u;
-                    }
-                    const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-                    // rows: which of the relevant picks reach this row at all (the column test is then per pixel)
-                    unsigned long long rowrel = 0;
-                    for (unsigned long long m = rel; m; m &= m - 1) {
-                        const int q = __builtin_ctzll(m);
-                        if (abs(y - s_cy[q]) <= sup) rowrel |= 1ull << q;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; j++) {
-                        const int x = x0 + j;
-                        const bool inside = j < 4 || two;
-                        const uint32_t vb = ((j < 4 ? v0 : v1) >> (8 * (j & 3))) & 0xffu;
-                        bool dead = false;
-                        for (unsigned long long m = rowrel; m; m &= m - 1) dead |= abs(x - s_cx[__builtin_ctzll(m)]) <= sup;
-                        if (inside && !dead) {
-                            const unsigned long long key = ((unsigned long long)lg_orderable(lg_valid_score(sc[j], vb != 0)) << 32) | (uint32_t)(y * W + x);
-                            best = key > best ? key : best;
-                        }
-                    }
-                }
-                best = lg_wave_max_u64(best);
-                if ((t & 63) == 0 && best) atomicMax(&s_keys[tile], best);
-            }
-            __syncthreads();
-            continue;
-        }
-        // General form (any window size, any width): 1024-pixel chunks, one per tile; the loads of up to 12 chunks are issued
+        // General form (any window size, any width): chunks of LG_TOPK_T pixels of a tile; the loads of up to 12 chunks are issued
         // together (one round trip to L2 / HBM instead of one per chunk).
         constexpr int CPT = LG_TW * LG_TH / LG_TOPK_T;
         const int chunks = naff * CPT;
@@ -2498,7 +2519,7 @@ __global__ __launch_bounds__(LG_TOPK_T) void lg_topk_kernel(const float* __restr
                         }
                         if (!dead) score = lg_orderable(sc_[g]);
                     }
-                    // within a chunk the flat index grows with the lane (li = chunk * 1024 + t): the cheaper lane-ordered arg-max
+                    // within a wave of a chunk the flat index grows with the lane (li = chunk * LG_TOPK_T + t, one tile row per wave): the cheaper lane-ordered arg-max
                     const unsigned long long key = lg_wave_argmax_lane_ordered(score, (uint32_t)idx_[g]);
                     if ((t & 63) == 0 && key) atomicMax(&s_keys[tile_[g]], key);
                 }
@@ -2686,7 +2707,7 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
             }
             float o_sdf[4], o_app[4], o_iso[4], o_acc[4], o_stem[4], o_trad[4];
             bool o_valid[4];
-            const LgPixFrame pf = lg_pix_frame(&fa, fa.fp + frame, fa.maxfix + 2 * (size_t)frame);
+            const LgPixFrame pf = lg_pix_frame(&fa, fa.fp + frame, fa.maxfix + LG_MF * (size_t)frame);
             lg_pixels4<true>(&fa, pf, y, x0, H, W, mnib, snib, din, o_flat, fa.w_flat, o_sdf, o_app, o_iso, o_acc, o_stem, o_trad, o_valid);
 #pragma unroll
             for (int j = 0; j < 4; j++)

@@ -96,6 +96,7 @@ struct LgMidribWs {
     unsigned long long* bits_host = nullptr;            // pinned copy (host contour analysis)
     size_t bits_cap = 0;
     LgWin* win = nullptr;
+    uint32_t* box = nullptr;                            // [B][LG_MF] bounding boxes from the bit-row pass (lg_internal.h; zeroed per call)
     LgFrameParams* fp = nullptr;
     LgMidribGeom* geom = nullptr;  LgMidribGeom* geom_host = nullptr;   // [B]
     int32_t* res = nullptr;  int32_t* res_host = nullptr;               // [B][5]: x0, y0, x1, y1, status

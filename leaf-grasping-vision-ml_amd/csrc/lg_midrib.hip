@@ -279,7 +279,7 @@ void lg_midrib_free(LgMidribWs*& w) {
     if (!w) return;
     auto F = [](void* p) { if (p) hipFree(p); };
     auto HF = [](void* p) { if (p) hipHostFree(p); };
-    F(w->hist); F(w->lut); F(w->bits); F(w->win); F(w->fp); F(w->geom); F(w->res);
+    F(w->hist); F(w->lut); F(w->bits); F(w->win); F(w->box); F(w->fp); F(w->geom); F(w->res);
     HF(w->bits_host); HF(w->geom_host); HF(w->res_host);
     lg_orient_free(w->orient);
     delete w;
@@ -315,9 +315,9 @@ int lg_midrib_ensure(LgMidribWs*& w, int B, int H, int W, int ntiles, bool frame
         hipDeviceSynchronize();
         auto F = [](void* p) { if (p) hipFree(p); };
         auto HF = [](void* p) { if (p) hipHostFree(p); };
-        F(w->win); F(w->fp); F(w->geom); F(w->res); HF(w->geom_host); HF(w->res_host);
-        w->win = nullptr; w->fp = nullptr; w->geom = w->geom_host = nullptr; w->res = w->res_host = nullptr; w->capB = 0;
-        A(dalloc(&w->win, B)); A(dalloc(&w->fp, B)); A(dalloc(&w->geom, B)); A(dalloc(&w->res, (size_t)B * 5));
+        F(w->win); F(w->box); F(w->fp); F(w->geom); F(w->res); HF(w->geom_host); HF(w->res_host);
+        w->win = nullptr; w->box = nullptr; w->fp = nullptr; w->geom = w->geom_host = nullptr; w->res = w->res_host = nullptr; w->capB = 0;
+        A(dalloc(&w->win, B)); A(dalloc(&w->box, (size_t)B * LG_MF)); A(dalloc(&w->fp, B)); A(dalloc(&w->geom, B)); A(dalloc(&w->res, (size_t)B * 5));
         A(hipHostMalloc((void**)&w->geom_host, sizeof(LgMidribGeom) * B));
         A(hipHostMalloc((void**)&w->res_host, sizeof(int32_t) * 5 * B));
         if (rc != hipSuccess) { if (err) *err = std::string("midrib frame buffers: ") + hipGetErrorString(rc); return LG_ERR_NOMEM; }
