@@ -32,6 +32,9 @@
  *   lg_clahe / lg_detect_midrib / lg_midrib_walk   GraspPointSelector.detect_midrib
  *                      (scripts/utils/grasp_point_selector.py:829-922), which LeafVisualizer calls
  *                      (scripts/utils/visualizer.py:141)
+ *   lg_cnn_load_from_trainer / lg_cnn_evaluate / lg_eval_logits   the validation pass of train_grasp_model
+ *                      (scripts/train_model.py:280-311: model.eval(), per-batch criterion, accuracy, analyze_predictions
+ *                      :64-99) on the weights the training step has just written, without a trip through the host
  */
 #ifndef LEAFGRASP_H
 #define LEAFGRASP_H
@@ -450,6 +453,65 @@ int lg_train_sync(lg_trainer* t);
    stay per rank, as with torch's DistributedDataParallel without SyncBatchNorm. */
 int lg_train_grad_buffer(lg_trainer* t, float** dev_ptr, int64_t* n);
 int lg_train_apply(lg_trainer* t, const lg_train_hparams* hp, float* grad_norm_host);
+
+/* ---- trainer -> inference hand-off and validation on the device (scripts/train_model.py:280-311)
+   lg_cnn_load_from_trainer   what lg_cnn_load does, computed on the device from the trainer's flat parameter and buffer
+                     vectors: BatchNorm folding, the direct, F(2x2) and F(4x4) Winograd weight layouts, the transposed
+                     classifier.  Every float equals what lg_cnn_load writes for trainer.state_dict (the same IEEE double
+                     operations in the same order, rounded once).  Whether the inference kernels take the model is decided
+                     before anything is touched -- lg_cnn_load's conditions and messages, and the classifier sizes a forward
+                     would refuse: on LG_ERR_UNSUPPORTED / LG_ERR_INVALID (a null trainer, a trainer on another device) the
+                     model loaded before stays loaded and usable.  Same geometry as the loaded model (encoder_filters,
+                     attention_type): the weight buffers are rewritten in place, nothing is freed or allocated and the
+                     activation workspace stays; otherwise as lg_cnn_load.  LG_CNN_F23 / LG_CNN_DIRECT / LG_CNN_WINO_MASK
+                     are read as lg_cnn_load reads them.
+                     Ordering: the fold runs on the legacy default stream behind an event recorded on the trainer's own
+                     stream(s) -- no lg_train_sync is needed after lg_train_step -- and that stream is synchronised before
+                     the call returns: a forward enqueued on any stream afterwards reads the new weights.  A forward still
+                     in flight on a NON-BLOCKING stream is the caller's to synchronise first (blocking streams, torch's
+                     default stream among them, are ordered by the legacy default stream itself).
+   lg_eval_logits    validation loss and confusion counts of N labelled logits (DEVICE, float32), walked in chunks of
+                     `chunk` samples as DataLoader(batch_size=chunk, shuffle=False) would (:280-298): chunk c covers
+                     [c chunk, min(N, (c + 1) chunk)).  Per sample, in double from the float logit z and label y:
+                     (1 - y) z + (1 + (pos_weight - 1) y) (max(-z, 0) + log1p(exp(-|z|))), BCEWithLogitsLoss(pos_weight).
+                     A chunk's mean = its terms added in index order / its length; loss = the chunk means added in chunk
+                     order / n_chunks (:306).  The order is fixed (it does not depend on the grid; no float atomics): two
+                     calls give the same bits.  Counts as analyze_predictions (:64-99): pred = z > threshold compared in
+                     float (the reference thresholds the LOGIT), tp = pred & y == 1, tn = !pred & y == 0, fp = #(y == 0) -
+                     tn, fn = #(y == 1) - tp.  correct counts (z > 0) == (y == 1): the reference's sigmoid(z) > 0.5 (:285-287)
+                     everywhere except for 0 < z < ~6e-8, where the float sigmoid rounds to exactly 0.5 and the reference
+                     predicts 0.  A NaN logit follows IEEE: not predicted positive, loss NaN.  N < 1, chunk < 1 or a null
+                     pointer: LG_ERR_INVALID.  Synchronises `stream`; the result is a HOST struct.
+   lg_eval_logits_host   the same code on the host (logits, labels HOST; no device, no handle): the per-sample term and the
+                     chunk walk are shared with the kernels; device and host differ in the ulps of exp / log1p only.
+   lg_cnn_evaluate   lg_cnn_forward on patches [N][9][32][32] (same plan, same slices: the same logits bit for bit), then
+                     lg_eval_logits on them, on one stream.  labels [N] DEVICE; logits_out: DEVICE, N floats, or NULL.
+                     Synchronises `stream`.
+   lg_debug_cnn_weights   plain read-back of one weight buffer of the loaded model into out (HOST, cap floats): which =
+                     LG_CNNW_*, layer = encoder layer (BCONV .. UWINO4) or classifier layer (FCW, FCB), ignored otherwise.
+                     *n = its floats, 0 when the model has no such buffer (WCONV past layer 0 of a non-standard encoder,
+                     UWINO of layer 0, attention tensors of another attention type).  cap = 0: size query.  LG_CNNW_SCALARS:
+                     n_layers, F, Fp, npix, act_per_patch, standard, att_type, att_b (0 without spatial attention), then
+                     cin, cout, cinp, coutp, wi, pool of every layer, as floats.  LG_CNNW_ALLOCS: copies nothing; *n = the
+                     weight buffers lg_cnn_load_from_trainer has allocated on this handle so far (an in-place refresh adds
+                     none: the buffers sit where they sat).  Synchronises the device. */
+enum { LG_CNNW_BCONV = 0, LG_CNNW_WCONV = 1, LG_CNNW_UWINO = 2, LG_CNNW_UWINO4 = 3, LG_CNNW_FCW = 4, LG_CNNW_FCB = 5,
+       LG_CNNW_ATT_W = 6, LG_CNNW_CA_W1 = 7, LG_CNNW_CA_B1 = 8, LG_CNNW_CA_W2 = 9, LG_CNNW_CA_B2 = 10, LG_CNNW_ZEROS = 11,
+       LG_CNNW_SCALARS = 12, LG_CNNW_ALLOCS = 13 };
+typedef struct lg_eval_result {      /* HOST, 64 bytes */
+    double  loss;                    /* mean over the chunks of each chunk's mean      train_model.py:280-298 */
+    int64_t n, n_chunks;
+    int64_t correct;                 /* (logit > 0) == (label == 1)                     :285-287 */
+    int64_t tp, fp, fn, tn;          /* analyze_predictions, threshold on the LOGIT     :64-99 */
+} lg_eval_result;
+int lg_cnn_load_from_trainer(lg_handle h, lg_trainer* t);
+int lg_eval_logits(lg_handle h, const float* logits, const float* labels, int N, int chunk, double pos_weight, float threshold,
+                   lg_eval_result* out, void* stream);
+int lg_eval_logits_host(const float* logits, const float* labels, int N, int chunk, double pos_weight, float threshold,
+                        lg_eval_result* out);
+int lg_cnn_evaluate(lg_handle h, const float* patches, const float* labels, int N, int chunk, double pos_weight, float threshold,
+                    float* logits_out, lg_eval_result* out, void* stream);
+int lg_debug_cnn_weights(lg_handle h, int which, int layer, float* out, int64_t cap, int64_t* n);
 
 #ifdef __cplusplus
 }

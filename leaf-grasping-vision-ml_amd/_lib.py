@@ -62,6 +62,17 @@ class LgLeafStat(C.Structure):
                 ("median_depth", C.c_float), ("pad2_", C.c_float)]
 
 
+class LgEvalResult(C.Structure):
+    """lg_eval_result: validation loss and confusion counts of lg_eval_logits / lg_cnn_evaluate (64 bytes)."""
+    _fields_ = [("loss", C.c_double), ("n", C.c_int64), ("n_chunks", C.c_int64), ("correct", C.c_int64),
+                ("tp", C.c_int64), ("fp", C.c_int64), ("fn", C.c_int64), ("tn", C.c_int64)]
+
+
+# lg_debug_cnn_weights: the buffers of the loaded CNN (include/leafgrasp.h LG_CNNW_*)
+CNNW = {"bconv": 0, "wconv": 1, "uwino": 2, "uwino4": 3, "fcw": 4, "fcb": 5, "att_w": 6, "ca_w1": 7, "ca_b1": 8, "ca_w2": 9,
+        "ca_b2": 10, "zeros": 11, "scalars": 12, "allocs": 13}
+
+
 # every symbol include/leafgrasp.h declares: (restype, argtypes)
 _VP = C.c_void_p
 SYMBOLS = {
@@ -134,6 +145,11 @@ SYMBOLS = {
     "lg_clahe": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _VP, _VP]),
     "lg_detect_midrib": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), _VP]),
+    "lg_cnn_load_from_trainer": (C.c_int, [_VP, _VP]),
+    "lg_eval_logits": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_double, C.c_float, C.POINTER(LgEvalResult), _VP]),
+    "lg_eval_logits_host": (C.c_int, [_FP, _FP, C.c_int, C.c_int, C.c_double, C.c_float, C.POINTER(LgEvalResult)]),
+    "lg_cnn_evaluate": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_double, C.c_float, _VP, C.POINTER(LgEvalResult), _VP]),
+    "lg_debug_cnn_weights": (C.c_int, [_VP, C.c_int, C.c_int, _FP, C.c_int64, C.POINTER(C.c_int64)]),
     "lg_midrib_walk": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "lg_cnn.h"
+#include "lg_eval.h"
 #include "lg_leaf.h"
 #include "lg_internal.h"
 #include "lg_midrib.h"
@@ -129,6 +130,8 @@ struct lg_ctx {
     hipEvent_t ev_cnn0 = nullptr, ev_cnn1 = nullptr;   // batch's memory-bound kernels beside it, bench.py --inflight)
     bool opt_host_orient = false;  // LG_HOST_ORIENT: contour analysis of every frame on the host threads (the round-1 path)
     LgMidribWs* midrib = nullptr;  // lg_clahe / lg_detect_midrib scratch (lg_midrib.hip)
+    void* eval_ws = nullptr;       // lg_eval_logits / lg_cnn_evaluate: result, chunk rows and (evaluate without logits_out) the logits
+    size_t eval_cap = 0;
 };
 
 namespace {
@@ -446,6 +449,7 @@ int lg_destroy(lg_handle h) {
     if (h->cand_rows_dev) hipFree(h->cand_rows_dev);
     if (h->cand_rows_host) hipHostFree(h->cand_rows_host);
     lg_cnn_free(&h->cnn);
+    if (h->eval_ws) hipFree(h->eval_ws);
     lg_leaf_free(h->leaf);
     lg_leaf_prof_free(h->leaf_prof);
     lg_orient_free(h->orient);
@@ -1324,6 +1328,125 @@ int lg_cnn_forward(lg_handle h, const float* patches, int N, float* logits, void
     int rc = lg_cnn_run(&h->cnn, patches, false, N, logits, s, &err);
     if (rc) return fail(h, rc, err.c_str());
     LG_HIP(h, hipGetLastError());
+    return LG_OK;
+}
+
+// The trainer's weights into this handle's inference CNN without leaving the device (lg_cnn.hip: the fold and transform kernels).
+// The fold runs on the legacy default stream -- ordered after every blocking stream's earlier work, a forward on torch's default
+// stream included -- behind an event recorded on each of the trainer's (non-blocking) streams.
+int lg_cnn_load_from_trainer(lg_handle h, lg_trainer* t) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    LgTrainView v;
+    if (!t || !lg_train_view(t, &v)) return fail(h, LG_ERR_INVALID, "lg_cnn_load_from_trainer: null trainer");
+    if (v.device != h->device) return fail(h, LG_ERR_INVALID, "lg_cnn_load_from_trainer: the trainer lives on another device than the handle");
+    LG_HIP(h, hipSetDevice(h->device));
+    hipStream_t s = nullptr;
+    hipEvent_t ev = nullptr;
+    LG_HIP(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    for (hipStream_t q : v.stream) {
+        if (!q) continue;
+        hipError_t e = hipEventRecord(ev, q);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, ev, 0);
+        if (e != hipSuccess) { hipEventDestroy(ev); return fail(h, LG_ERR_HIP, "lg_cnn_load_from_trainer: event", e); }
+    }
+    std::string err;
+    const int rc = lg_cnn_upload_from_trainer(&h->cnn, &v, s, &err);   // synchronises s
+    hipEventDestroy(ev);
+    if (rc) return fail(h, rc, err.c_str());
+    return LG_OK;
+}
+
+int lg_debug_cnn_weights(lg_handle h, int which, int layer, float* out, int64_t cap, int64_t* n) {
+    if (!h || !n || cap < 0 || (cap > 0 && !out)) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    *n = 0;
+    const LgCnn& c = h->cnn;
+    if (which == LG_CNNW_ALLOCS) { *n = (int64_t)c.handoff_allocs; return LG_OK; }
+    if (!c.loaded) return fail(h, LG_ERR_NO_MODEL, "lg_debug_cnn_weights: no model loaded");
+    if (which == LG_CNNW_SCALARS) {
+        std::vector<float> sc = {(float)c.n_layers, (float)c.F, (float)c.Fp, (float)c.npix, (float)c.act_per_patch, c.standard ? 1.f : 0.f,
+                                 (float)c.att_type, c.att_type == LG_ATT_SPATIAL || c.att_type == LG_ATT_HYBRID ? c.att_b : 0.f};
+        for (int L = 0; L < c.n_layers; L++) {
+            const RtLayer& l = c.layers[L];
+            for (int x : {l.cin, l.cout, l.cinp, l.coutp, l.wi, l.pool ? 1 : 0}) sc.push_back((float)x);
+        }
+        *n = (int64_t)sc.size();
+        if (cap == 0) return LG_OK;
+        if (cap < *n) return fail(h, LG_ERR_INVALID, "lg_debug_cnn_weights: cap too small");
+        memcpy(out, sc.data(), sc.size() * sizeof(float));
+        return LG_OK;
+    }
+    const float* p = nullptr;
+    size_t cnt = 0;
+    if (!lg_cnn_weight_buffer(&c, which, layer, &p, &cnt)) return LG_OK;   // no such buffer for this model: *n = 0
+    *n = (int64_t)cnt;
+    if (cap == 0) return LG_OK;   // size query
+    if ((size_t)cap < cnt) return fail(h, LG_ERR_INVALID, "lg_debug_cnn_weights: cap too small");
+    hipSetDevice(h->device);
+    hipDeviceSynchronize();
+    if (hipMemcpy(out, p, cnt * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(h, LG_ERR_HIP, "lg_debug_cnn_weights: copy failed");
+    return LG_OK;
+}
+
+// scratch of the metrics kernels (+ extra bytes behind it), grown when a call needs more
+static int eval_scratch(lg_handle h, size_t bytes, hipStream_t s) {
+    if (bytes <= h->eval_cap) return LG_OK;
+    LG_HIP(h, hipStreamSynchronize(s));
+    if (h->eval_ws) { hipFree(h->eval_ws); h->eval_ws = nullptr; h->eval_cap = 0; }
+    if (hipMalloc(&h->eval_ws, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(h, LG_ERR_NOMEM, "lg_eval_logits: scratch allocation failed"); }
+    h->eval_cap = bytes;
+    return LG_OK;
+}
+
+static int eval_run(lg_handle h, const float* logits, const float* labels, int N, int chunk, double pos_weight, float threshold,
+                    lg_eval_result* out, hipStream_t s) {
+    lg_eval_enqueue(logits, labels, N, chunk, pos_weight, threshold, h->eval_ws, s);
+    LG_HIP(h, hipGetLastError());
+    lg_eval_result r;
+    LG_HIP(h, hipMemcpyAsync(&r, h->eval_ws, sizeof(r), hipMemcpyDeviceToHost, s));
+    LG_HIP(h, hipStreamSynchronize(s));
+    *out = r;
+    return LG_OK;
+}
+
+int lg_eval_logits(lg_handle h, const float* logits, const float* labels, int N, int chunk, double pos_weight, float threshold,
+                   lg_eval_result* out, void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (!logits || !labels || !out || N < 1 || chunk < 1) return fail(h, LG_ERR_INVALID, "lg_eval_logits: bad argument");
+    hipStream_t s = (hipStream_t)stream_;
+    LG_HIP(h, hipSetDevice(h->device));
+    int rc = eval_scratch(h, lg_eval_scratch_bytes(N, chunk), s);
+    if (rc) return rc;
+    return eval_run(h, logits, labels, N, chunk, pos_weight, threshold, out, s);
+}
+
+// lg_cnn_forward's call of lg_cnn_run (same plan, same slices: the same logits) and the metrics behind it on the same stream
+int lg_cnn_evaluate(lg_handle h, const float* patches, const float* labels, int N, int chunk, double pos_weight, float threshold,
+                    float* logits_out, lg_eval_result* out, void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (!patches || !labels || !out || N < 1 || chunk < 1) return fail(h, LG_ERR_INVALID, "lg_cnn_evaluate: bad argument");
+    if (!h->cnn.loaded) return fail(h, LG_ERR_NO_MODEL, "lg_cnn_evaluate: no model loaded (reference: ml_predictor is None)");
+    hipStream_t s = (hipStream_t)stream_;
+    LG_HIP(h, hipSetDevice(h->device));
+    const size_t sb = (lg_eval_scratch_bytes(N, chunk) + 255) / 256 * 256;
+    int rc = eval_scratch(h, sb + (logits_out ? 0 : (size_t)N * sizeof(float)), s);
+    if (rc) return rc;
+    float* logits = logits_out ? logits_out : (float*)((char*)h->eval_ws + sb);
+    std::string err;
+    if (lg_cnn_take_error(&h->cnn)) return fail(h, LG_ERR_HIP, "lg_cnn_evaluate: a split item of the previous forward did not receive its parts");
+    {
+        ProfScope ps(h, "cnn", s);
+        rc = lg_cnn_run(&h->cnn, patches, false, N, logits, s, &err);
+    }
+    if (rc) return fail(h, rc, err.c_str());
+    LG_HIP(h, hipGetLastError());
+    rc = eval_run(h, logits, labels, N, chunk, pos_weight, threshold, out, s);
+    if (rc) return rc;
+    if (lg_cnn_take_error(&h->cnn)) return fail(h, LG_ERR_HIP, "lg_cnn_evaluate: a split CNN item did not receive its parts");
     return LG_OK;
 }
 

@@ -42,6 +42,7 @@ struct LgCnn {
     unsigned* kerr_dev = nullptr;
     int wino_mask = 0x3f;         // bit L = layer L on Winograd (LG_CNN_DIRECT / LG_CNN_WINO_MASK at load time; bits 1..5: standard encoder only)
     int capN = 0;
+    long long handoff_allocs = 0; // weight buffers lg_cnn_upload_from_trainer has allocated on this handle (0 more on an in-place refresh)
 };
 
 int lg_cnn_upload(LgCnn* c, const lg_cnn_weights* w, std::string* err);
@@ -57,3 +58,28 @@ bool lg_cnn_counts_on_device(const LgCnn* c);
 size_t lg_cnn_halo_patch_floats(void);
 // after a synchronisation of the stream a forward ran on: true (once) if a split item of it gave up waiting for its parts
 bool lg_cnn_take_error(LgCnn* c);
+
+// ---- trainer -> inference hand-off on the device (lg_cnn_load_from_trainer)
+// What the fold kernels need of an lg_trainer (lg_train.hip): the flat parameter / buffer vectors and the offsets of every tensor
+// in them, in the order of lg_cnn_weights.
+struct LgTrainView {
+    int device = 0, n_blocks = 0, att = 0, F = 0, hid = 0;
+    int filters[4] = {0, 0, 0, 0};
+    float bn_eps = 1e-5f;                        // the eps of the training step's BatchNorms
+    const float* P = nullptr;                    // flat parameters (DEVICE)
+    const float* B = nullptr;                    // flat BatchNorm buffers (DEVICE)
+    size_t conv_w[8] = {0}, conv_b[8] = {0}, bn_g[8] = {0}, bn_b[8] = {0};   // offsets into P
+    size_t bn_m[8] = {0}, bn_v[8] = {0};                                       // offsets into B
+    size_t att_w = 0, att_b = 0, ca_w1 = 0, ca_b1 = 0, ca_w2 = 0, ca_b2 = 0;   // P
+    size_t fc_w[4] = {0}, fc_b[4] = {0}, fbn_g[3] = {0}, fbn_b[3] = {0};       // P
+    size_t fbn_m[3] = {0}, fbn_v[3] = {0};                                     // B
+    hipStream_t stream[2] = {nullptr, nullptr};  // the streams the trainer's steps run on
+};
+bool lg_train_view(lg_trainer* t, LgTrainView* v);
+// lg_cnn_upload computed on the device from the trainer's vectors, on stream s (the caller orders s after the trainer's
+// streams); synchronises s before it returns (the spatial attention's bias comes back as one 4-byte copy).  Every float written
+// equals what lg_cnn_upload writes for the same state.  Support is decided before anything is touched; same geometry as loaded
+// (n_layers, layers[], att_type): the weight buffers are rewritten in place, nothing is freed or allocated.
+int lg_cnn_upload_from_trainer(LgCnn* c, const LgTrainView* v, hipStream_t s, std::string* err);
+// the weight buffer `which` (LG_CNNW_*) of layer `layer`: its device pointer and floats; false: no such buffer for this model
+bool lg_cnn_weight_buffer(const LgCnn* c, int which, int layer, const float** p, size_t* n);

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/leafgrasp.h"
+#include "lg_cnn.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -1498,3 +1499,25 @@ int lg_train_sync(lg_trainer* tr) {
 }
 
 }  // extern "C"
+
+// The trainer as lg_cnn_upload_from_trainer reads it: where every tensor of lg_cnn_weights lies in the flat vectors.
+bool lg_train_view(lg_trainer* tr, LgTrainView* v) {
+    if (!tr || !v || !tr->P_ || !tr->B || tr->layers.size() != (size_t)2 * tr->n_blocks || tr->layers.size() > 8) return false;
+    *v = LgTrainView();
+    v->device = tr->device; v->n_blocks = tr->n_blocks; v->att = tr->att; v->F = tr->F; v->hid = tr->hid;
+    for (int b = 0; b < 4; b++) v->filters[b] = b < tr->n_blocks ? tr->filters[b] : 0;
+    v->bn_eps = 1e-5f;   // enqueue_step's eps
+    v->P = tr->P_; v->B = tr->B;
+    for (size_t L = 0; L < tr->layers.size(); L++) {
+        const TrainLayer& l = tr->layers[L];
+        v->conv_w[L] = l.w; v->conv_b[L] = l.b; v->bn_g[L] = l.g; v->bn_b[L] = l.be; v->bn_m[L] = l.rm; v->bn_v[L] = l.rv;
+    }
+    v->att_w = tr->att_w; v->att_b = tr->att_b;
+    v->ca_w1 = tr->ca_w1; v->ca_b1 = tr->ca_b1; v->ca_w2 = tr->ca_w2; v->ca_b2 = tr->ca_b2;
+    for (int k = 0; k < 4; k++) {
+        v->fc_w[k] = tr->fc[k].w; v->fc_b[k] = tr->fc[k].b;
+        if (k < 3) { v->fbn_g[k] = tr->fc[k].g; v->fbn_b[k] = tr->fc[k].be; v->fbn_m[k] = tr->fc[k].rm; v->fbn_v[k] = tr->fc[k].rv; }
+    }
+    v->stream[0] = tr->stream; v->stream[1] = tr->stream_w;
+    return true;
+}

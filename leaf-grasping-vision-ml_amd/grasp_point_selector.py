@@ -99,6 +99,66 @@ class GraspPointSelector:
         self._keep = keep
         self.ml_predictor = "lg_cnn"
 
+    def load_from_trainer(self, trainer):
+        """Install the weights a GraspTrainer holds right now, on the device (lg_cnn_load_from_trainer): the same floats as
+        set_cnn_state_dict(trainer.state_dict()), without the state dict.  The call orders itself after the trainer's steps;
+        a model of the same geometry is refreshed in place.  A model the inference kernels do not take (LgError, status
+        LG_ERR_UNSUPPORTED) leaves the loaded one as it is."""
+        th = getattr(trainer, "_h", None)
+        with torch.cuda.device(self.device):
+            check(self._h, lib.lg_cnn_load_from_trainer(self._h, th if th else None), "lg_cnn_load_from_trainer")
+        self._keep = None
+        self.ml_predictor = "lg_cnn"
+
+    def cnn_weights(self, which, layer=0):
+        """Inspection: one weight buffer of the loaded CNN as the kernels read it (lg_debug_cnn_weights; `which`: a key of
+        _lib.CNNW), float32 numpy array, empty when the model has no such buffer.  'allocs': the number of weight buffers
+        load_from_trainer has allocated on this selector so far (an int; an in-place refresh adds none)."""
+        n = C.c_int64()
+        code = _lib.CNNW[which]
+        check(self._h, lib.lg_debug_cnn_weights(self._h, code, int(layer), None, 0, C.byref(n)), "lg_debug_cnn_weights")
+        if which == "allocs":
+            return int(n.value)
+        out = np.empty(n.value, np.float32)
+        if n.value:
+            check(self._h, lib.lg_debug_cnn_weights(self._h, code, int(layer), out.ctypes.data_as(C.POINTER(C.c_float)), out.size,
+                                                    C.byref(n)), "lg_debug_cnn_weights")
+        return out
+
+    def eval_logits(self, logits, labels, batch_size=16, pos_weight=2.0, threshold=0.5):
+        """Validation loss and counts of device logits (lg_eval_logits) -> _lib.LgEvalResult."""
+        z = torch.as_tensor(logits).to(self.device, torch.float32).contiguous().reshape(-1)
+        y = torch.as_tensor(labels).to(self.device, torch.float32).contiguous().reshape(-1)
+        if z.shape != y.shape:
+            raise ValueError("logits and labels must have the same length")
+        r = _lib.LgEvalResult()
+        with torch.cuda.device(self.device):
+            check(self._h, lib.lg_eval_logits(self._h, z.data_ptr(), y.data_ptr(), int(z.shape[0]), int(batch_size),
+                                              float(pos_weight), float(threshold), C.byref(r), self._stream()), "lg_eval_logits")
+        return r
+
+    def evaluate(self, features, labels, batch_size=16, pos_weight=2.0, threshold=0.5, return_logits=False):
+        """The validation pass of train_model.py:280-311 on the loaded CNN in one call (lg_cnn_evaluate): forward, per-batch
+        BCEWithLogitsLoss(pos_weight) averaged over the batches, accuracy and analyze_predictions' metrics (threshold on the
+        logit).  features [N,9,32,32], labels [N].  Returns {"val_loss", "accuracy" (percent), "n", "metrics"[, "logits"]}."""
+        from .trainer import metrics_from_counts
+        x = torch.as_tensor(features).to(self.device, torch.float32).contiguous()
+        y = torch.as_tensor(labels).to(self.device, torch.float32).contiguous().reshape(-1)
+        N = int(x.shape[0])
+        if tuple(x.shape) != (N, 9, 32, 32) or tuple(y.shape) != (N,):
+            raise ValueError("features must be [N,9,32,32] and labels [N]")
+        logits = torch.empty((N,), dtype=torch.float32, device=self.device) if return_logits else None
+        r = _lib.LgEvalResult()
+        with torch.cuda.device(self.device):
+            check(self._h, lib.lg_cnn_evaluate(self._h, x.data_ptr(), y.data_ptr(), N, int(batch_size), float(pos_weight),
+                                               float(threshold), logits.data_ptr() if return_logits else None, C.byref(r),
+                                               self._stream()), "lg_cnn_evaluate")
+        out = {"val_loss": float(r.loss), "accuracy": 100.0 * r.correct / r.n, "n": int(r.n),
+               "metrics": metrics_from_counts(int(r.tp), int(r.fp), int(r.fn), int(r.tn))}
+        if return_logits:
+            out["logits"] = logits
+        return out
+
     def clear_cnn(self):
         lib.lg_cnn_unload(self._h)
         self.ml_predictor = None

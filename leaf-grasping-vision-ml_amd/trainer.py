@@ -114,6 +114,19 @@ def analyze_predictions(outputs, labels, threshold=0.5):
             "confusion_matrix": {"true_positive": tp, "false_positive": fp, "false_negative": fn, "true_negative": tn}}
 
 
+def metrics_from_counts(tp, fp, fn, tn):
+    """analyze_predictions' dict (train_model.py:64-99: same keys, same zero-denominator rules, percentages) from the four
+    confusion counts -- what lg_eval_logits / lg_cnn_evaluate bring back instead of the logits."""
+    total_pos, total_neg = tp + fn, tn + fp
+    precision = tp / (tp + fp) if tp + fp > 0 else 0
+    recall = tp / (tp + fn) if tp + fn > 0 else 0
+    f1 = 2 * precision * recall / (precision + recall) if precision + recall > 0 else 0
+    return {"positive_accuracy": (tp / total_pos if total_pos else 0) * 100,
+            "negative_accuracy": (tn / total_neg if total_neg else 0) * 100,
+            "precision": precision * 100, "recall": recall * 100, "f1_score": f1 * 100,
+            "confusion_matrix": {"true_positive": tp, "false_positive": fp, "false_negative": fn, "true_negative": tn}}
+
+
 def parameter_layout(filters, attention_type="spatial", in_channels=9):
     """[(state_dict key, shape)] in model.parameters() order, and the same for the BatchNorm buffers
     (running_mean, running_var per BatchNorm in module order) -- the flat vectors of lg_train_set_state."""
@@ -381,6 +394,16 @@ class GraspTrainer:
         x = torch.as_tensor(features).to(self.device, torch.float32)
         return torch.cat([sel.cnn_forward(x[i:i + batch]) for i in range(0, x.shape[0], batch)])
 
+    def evaluate(self, features, labels, selector=None, batch_size=16, return_logits=False):
+        """The validation pass (train_model.py:280-311) without leaving the device: the current weights go into the
+        selector's inference CNN (GraspPointSelector.load_from_trainer), which scores the set in one call
+        (lg_cnn_evaluate) with this trainer's pos_weight.  Returns {"val_loss", "accuracy", "n", "metrics"[, "logits"]}."""
+        from .grasp_point_selector import GraspPointSelector
+        sel = selector or GraspPointSelector(self.device, load_model=False)
+        sel.load_from_trainer(self)
+        return sel.evaluate(features, labels, batch_size=batch_size, pos_weight=float(self.hp.pos_weight),
+                            return_logits=return_logits)
+
     def bce_with_logits(self, logits, labels):
         """nn.BCEWithLogitsLoss(pos_weight) mean (validation loss, train_model.py:285)."""
         pw = torch.tensor([self.hp.pos_weight], device=logits.device)
@@ -388,11 +411,14 @@ class GraspTrainer:
 
     # ------------------------------------------------------------------ epoch loop (train_model.py:155-356)
     def fit(self, features, labels, num_epochs=150, batch_size=16, val_fraction=0.2, save_dir=None, patience=15,
-            min_delta=0.001, sched_factor=0.5, sched_patience=5, min_lr=1e-6, normalization_stats=None, log=print):
+            min_delta=0.001, sched_factor=0.5, sched_patience=5, min_lr=1e-6, normalization_stats=None, log=print,
+            device_eval=False):
         """80/20 split, weighted sampling with replacement, ReduceLROnPlateau(min, 0.5, 5, min_lr 1e-6),
         EarlyStopping(15, 0.001, restore best weights), best_model.pth with the reference's checkpoint keys.
         The last incomplete batch of an epoch is used when it has at least 2 samples (a batch of 1 raises in the
-        reference: BatchNorm1d in train mode)."""
+        reference: BatchNorm1d in train mode).  device_eval=True: the epoch's validation is one evaluate() call (weights
+        handed to the inference CNN on the device, loss and counts reduced there) instead of state_dict() + reload + a
+        loss per batch; the loss is then summed in double, so it agrees with the float32 loop to ~1e-6 relative."""
         gen = torch.Generator().manual_seed(self.seed)
         feats = torch.as_tensor(features, dtype=torch.float32).to(self.device)
         labs = torch.as_tensor(labels, dtype=torch.float32).to(self.device)
@@ -421,13 +447,17 @@ class GraspTrainer:
                 tot, nb = tot + loss, nb + 1
                 correct += ((torch.sigmoid(logits) > 0.5).float() == tr_y[bi]).sum().item()
             train_losses.append(tot / max(nb, 1))
-            vl = self.predict_logits(va_x, selector=sel)
-            # the reference averages per-batch means over len(val_loader) (:306)
-            vb = [self.bce_with_logits(vl[s:s + batch_size], va_y[s:s + batch_size]).item()
-                  for s in range(0, va_y.shape[0], batch_size)]
-            val_loss = float(np.mean(vb)) if vb else float("nan")
+            if device_eval:
+                ev = self.evaluate(va_x, va_y, selector=sel, batch_size=batch_size)
+                val_loss, metrics = ev["val_loss"], ev["metrics"]
+            else:
+                vl = self.predict_logits(va_x, selector=sel)
+                # the reference averages per-batch means over len(val_loader) (:306)
+                vb = [self.bce_with_logits(vl[s:s + batch_size], va_y[s:s + batch_size]).item()
+                      for s in range(0, va_y.shape[0], batch_size)]
+                val_loss = float(np.mean(vb)) if vb else float("nan")
+                metrics = analyze_predictions(vl, va_y)
             val_losses.append(val_loss)
-            metrics = analyze_predictions(vl, va_y)
             metrics_history.append(metrics)
             scheduler.step(val_loss)
             if log:
@@ -451,7 +481,8 @@ class GraspTrainer:
                 "best_val_loss": best_val, "best_epoch": early_stopping.best_epoch}
 
 
-def train_grasp_model(data_path=None, save_dir=None, device="cuda:0", num_epochs=150, log=print, **trainer_kwargs):
+def train_grasp_model(data_path=None, save_dir=None, device="cuda:0", num_epochs=150, log=print, device_eval=False,
+                      **trainer_kwargs):
     """scripts/train_model.py::train_grasp_model (:155-395) on this path: torch.manual_seed(42), load
     ~/leaf_grasp_output/ml_training_data/training_data.pt (EnhancedGraspDataCollector's file; loaded with weights_only=True),
     normalise, 80/20 split, weighted sampling, Adam / ReduceLROnPlateau / EarlyStopping, best_model.pth + final_model.pth in
@@ -466,7 +497,8 @@ def train_grasp_model(data_path=None, save_dir=None, device="cuda:0", num_epochs
     if log:
         log(f"Combined features shape: {tuple(features.shape)}")
     trainer = GraspTrainer(torch.device(device), **trainer_kwargs)
-    hist = trainer.fit(features, labels, num_epochs=num_epochs, save_dir=save_dir, normalization_stats=stats, log=log)
+    hist = trainer.fit(features, labels, num_epochs=num_epochs, save_dir=save_dir, normalization_stats=stats, log=log,
+                       device_eval=device_eval)
     torch.save({"epoch": len(hist["val_losses"]) - 1, "model_state_dict": trainer.state_dict(),
                 "optimizer_state_dict": trainer.torch_optimizer_state_dict(),
                 "val_loss": hist["val_losses"][-1] if hist["val_losses"] else None,
