@@ -384,6 +384,12 @@ int lg_debug_near_tiles(lg_handle h, int32_t* off, int cap);
 /* *patches = how many patches the last lg_select_grasp* call on this handle put through the CNN (0 without a model;
    B * top_k where every candidate is scored: lg_select_grasp_candidates*, LG_CNN_PRUNE=0).  Synchronises the device. */
 int lg_debug_cnn_scored(lg_handle h, int64_t* patches);
+/* The clutter arg-max of the last lg_leaf_stats / lg_leaf_stats_batch / lg_leaf_select_batch call on this handle: *n_frames =
+   its batch size (0: no such call yet, or the call was refused before the pass), flags[b] = 1 for a frame whose survivor
+   list of the branch-and-bound pass overflowed, *n_flagged = how many did.  *n_flagged > 0 means the full-transform pass
+   (column scan + per-row lower envelope) ran for the whole batch and every frame's arg-max comes from it.  flags: HOST, cap
+   >= the batch size (LG_ERR_INVALID otherwise).  Read-only, launches nothing. */
+int lg_debug_leaf_fallback(lg_handle h, int32_t* flags, int cap, int32_t* n_frames, int32_t* n_flagged);
 /* The CNN pass of the last lg_select_grasp* call on this handle, patch by patch.  The call's B frames run as *n_sub
    sub-batches of *sub_frames frames (one sub-batch of B frames unless LG_SUBBATCH was set at lg_create); sub-batch k owns
    the entries [k * *sub_frames * top_k, ...) of list, slot and logits, one per candidate slot of its frames, and every index

@@ -538,6 +538,14 @@ int lg_debug_cnn_scored(lg_handle h, int64_t* patches) {
     return LG_OK;
 }
 
+int lg_debug_leaf_fallback(lg_handle h, int32_t* flags, int cap, int32_t* n_frames, int32_t* n_flagged) {
+    if (!h || !n_frames || !n_flagged || cap < 0 || (cap > 0 && !flags)) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (lg_leaf_last_fallback(h->leaf, flags, cap, n_frames, n_flagged))
+        return fail(h, LG_ERR_INVALID, "lg_debug_leaf_fallback: cap is smaller than the last call's batch");
+    return LG_OK;
+}
+
 int lg_debug_cnn_survivors(lg_handle h, int32_t* sub_frames, int32_t* n_sub, int32_t* counts, int32_t counts_cap,
                            int32_t* list, int32_t* slot, float* logits, int64_t cap, int64_t* n_slots) {
     if (!h || !sub_frames || !n_sub || !n_slots) return LG_ERR_INVALID;

@@ -31,4 +31,7 @@ int lg_leaf_select_host(const lg_leaf_stat* st, int n, const int32_t ext[4], int
 int lg_leaf_select_batch_run(LgLeafWs*& w, const int16_t* labels, const float* depth, int B, int H, int W, double cx, double cy,
                              double f, int32_t* ids, int32_t* n_tall, int32_t* tall, int tall_cap, hipStream_t s, hipStream_t side,
                              std::string* err, LgLeafProf* prof = nullptr);
+// lg_debug_leaf_fallback: which frames of the last lg_leaf_run* call on this workspace overflowed a survivor list of the
+// branch-and-bound pass (the whole batch then took the full-transform pass); w may be NULL (no call yet: 0 frames)
+int lg_leaf_last_fallback(const LgLeafWs* w, int32_t* flags, int cap, int32_t* n_frames, int32_t* n_flagged);
 void lg_leaf_free(LgLeafWs*& w);

@@ -581,13 +581,16 @@ __global__ __launch_bounds__(LGL_BB_T) void k_edt_bb(const unsigned long long* _
     qa += (size_t)fr * LGL_QCAP; qb += (size_t)fr * LGL_QCAP;
     if (t == 0) { s_lb2 = 0; s_na = 0; s_nb = 0; s_any = 0; s_ovf = 0; s_res = 0; }
     __syncthreads();
-    {   // any leaf pixel at all?
-        unsigned any = 0;
-        for (long long i = t; i < (long long)H * WW; i += LGL_BB_T) any |= bits[i] != 0ull;
-        if (any) s_any = 1;
+    {   // any leaf pixel at all?  any background pixel?  (bits past W are 0: a frame is all leaf iff H * W bits are set)
+        unsigned cnt = 0;
+        for (long long i = t; i < (long long)H * WW; i += LGL_BB_T) cnt += (unsigned)__popcll(bits[i]);
+        if (cnt) atomicAdd(&s_any, cnt);
     }
     __syncthreads();
-    if (!s_any) { if (t == 0) { out[fr] = 0; flag[fr] = 0; } return; }
+    // no leaf pixel, or no background pixel: the field is constant.  (Without the second test every cell of an all-leaf frame
+    // survives every filter -- centre value 0 against a best value of 0 -- and a frame of more than 65536 pixels overflowed
+    // the list and sent its whole batch through the fallback for an answer that is known here.)
+    if (!s_any || s_any == (unsigned)H * (unsigned)W) { if (t == 0) { out[fr] = 0; flag[fr] = 0; } return; }
     // entry: d2 (32) | y0 (16) | x0 (16) of a cell; level 0: cells of S x S pixels
     int S = 64;
     while (((H + S - 1) / S) * ((W + S - 1) / S) > 8192) S *= 2;
@@ -768,9 +771,13 @@ __global__ __launch_bounds__(256) void k_pack(const unsigned long long* __restri
         o.sum_y = (double)acc[slot].sum_y;
         o.sum_depth = acc[slot].sum_depth;
         o.sum_ray = acc[slot].sum_ray;
-        // np.median: odd n -> middle element; even n -> float32 mean of the two middle elements
+        // np.median: odd n -> middle element; even n -> float32 mean of the two middle elements; NaN when the leaf holds a
+        // NaN (np.median sorts them last and checks the last element).  f2key puts a positive NaN above the key of +inf and
+        // a negative one below the key of -inf, so the leaf's key range (k_accumulate) already says whether there is one.
         const float lo_v = key2f(st[slot].key);
-        if (acc[slot].area % 2 == 1) {
+        if (acc[slot].kmax > 0xFF800000u || ~acc[slot].nkmin < 0x007FFFFFu) {
+            o.median_depth = __uint_as_float(0x7FC00000u);
+        } else if (acc[slot].area % 2 == 1) {
             o.median_depth = lo_v;
         } else {
             const float hi_v = (st[slot].n_le > 0) ? lo_v : key2f(succ[slot]);   // duplicates of the key cover the upper index
@@ -1010,8 +1017,19 @@ struct LgLeafWs {   // every array holds capB frames back to back
     int out_cap;
     size_t px_cap, bits_cap, g_cap, rb_cap;   // pixels (comp list), 64-bit words of the bit rows, pixels, rows
     int capB;
+    int32_t* last_flag;        // [capB] HOST: frames of the last call whose survivor list overflowed (lg_leaf_last_fallback)
+    int last_B;                // frames of the last call that got as far as the clutter extrema (0: none)
     hipEvent_t ev_in, ev_side; // fences of the side chain (the side stream belongs to the handle)
 };
+
+int lg_leaf_last_fallback(const LgLeafWs* w, int32_t* flags, int cap, int32_t* n_frames, int32_t* n_flagged) {
+    const int B = w ? w->last_B : 0;
+    if (cap < B) return LG_ERR_INVALID;
+    int n = 0;
+    for (int b = 0; b < B; b++) { flags[b] = w->last_flag[b]; n += w->last_flag[b]; }
+    *n_frames = B; *n_flagged = n;
+    return LG_OK;
+}
 
 void lg_leaf_free(LgLeafWs*& w) {
     if (!w) return;
@@ -1021,6 +1039,7 @@ void lg_leaf_free(LgLeafWs*& w) {
         if (p) hipFree(p);
     if (w->h_out) hipHostFree(w->h_out);
     if (w->h_hdr) hipHostFree(w->h_hdr);
+    free(w->last_flag);
     if (w->ev_in) hipEventDestroy(w->ev_in);
     if (w->ev_side) hipEventDestroy(w->ev_side);
     delete w;
@@ -1041,7 +1060,8 @@ static int leaf_ws(LgLeafWs*& w, int B, int H, int W) {
             hipMalloc((void**)&w->best, nb * 8) || hipMalloc((void**)&w->bbflag, nb * 4) || hipMalloc((void**)&w->comp_n, nb * 4 * 256) ||
             hipMalloc((void**)&w->qa, nb * 8 * LGL_QCAP) || hipMalloc((void**)&w->qb, nb * 8 * LGL_QCAP) ||
             hipMemset(w->hist, 0, nb * 4 * LGL_MAXL * 256) || hipMalloc((void**)&w->d_hdr, nb * sizeof(LeafHdr)) ||
-            hipHostMalloc((void**)&w->h_hdr, nb * sizeof(LeafHdr)))
+            hipHostMalloc((void**)&w->h_hdr, nb * sizeof(LeafHdr)) ||
+            !(w->last_flag = (int32_t*)calloc(nb, sizeof(int32_t))))
             return LG_ERR_NOMEM;
         if (hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming) || hipEventCreateWithFlags(&w->ev_side, hipEventDisableTiming))
             return LG_ERR_HIP;
@@ -1106,6 +1126,7 @@ int lg_leaf_run_batch(LgLeafWs*& w, const int16_t* labels, const float* depth, i
                       hipStream_t s, hipStream_t side, std::string* err, LgLeafProf* prof) {
     int rc = leaf_ws(w, B, H, W);
     if (rc) { *err = "lg_leaf_stats: workspace allocation failed"; return rc; }
+    w->last_B = 0;
     if (W > 4096 || H > 65535) { *err = "lg_leaf_stats: width > 4096 unsupported"; return LG_ERR_UNSUPPORTED; }
     const size_t nb = (size_t)B;
     const int WW = (W + 63) / 64;
@@ -1182,7 +1203,11 @@ int lg_leaf_run_batch(LgLeafWs*& w, const int16_t* labels, const float* depth, i
     }
     if (prof && prof->on) leaf_prof_flush(prof);
     bool any_flag = false;
-    for (int b = 0; b < B; b++) any_flag |= w->h_hdr[b].bbflag != 0;
+    for (int b = 0; b < B; b++) {
+        w->last_flag[b] = w->h_hdr[b].bbflag != 0;   // (kept for lg_leaf_last_fallback: the re-pack below clears the headers' flags)
+        any_flag |= w->h_hdr[b].bbflag != 0;
+    }
+    w->last_B = B;
     if (any_flag) {   // a survivor list overflowed somewhere: the full-transform pass for the batch, then the headers once more
         rc = leaf_edt_fallback(w, labels, B, H, W, s);
         if (rc) { *err = "lg_leaf_stats: workspace allocation failed"; return rc; }

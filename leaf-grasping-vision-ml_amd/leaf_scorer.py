@@ -160,6 +160,24 @@ class OptimalLeafSelector:
             out.append((fs, ((e[0], e[1]), (e[2], e[3])), (H, W)))
         return out
 
+    def edt_fallback_frames(self):
+        """Inspection: one bool per frame of the last leaf_statistics / leaf_statistics_batch / select_optimal_leaves_batch call
+        on this selector -- True where the branch-and-bound pass of the clutter arg-max overflowed its survivor list
+        (lg_debug_leaf_fallback).  Any True means the full distance transform answered for the whole batch; [] before the
+        first call and after a refused one."""
+        cap = 64
+        while True:
+            flags = (C.c_int32 * cap)()
+            n, nf = C.c_int32(0), C.c_int32(0)
+            rc = lib.lg_debug_leaf_fallback(self._h, flags, cap, C.byref(n), C.byref(nf))
+            if rc == LG_ERR_INVALID and cap < 65536:
+                cap *= 4
+                continue
+            check(self._h, rc, "lg_debug_leaf_fallback")
+            out = [bool(flags[b]) for b in range(n.value)]
+            assert sum(out) == nf.value
+            return out
+
     def select_optimal_leaves_batch(self, mask_tensors, depth_tensors):
         """select_optimal_leaf for B frames in ONE library call (lg_leaf_select_batch: the device passes, then tall-leaf split,
         scores, Pareto filter and weighted pick on the host inside the library -- the same arithmetic as

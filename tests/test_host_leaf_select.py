@@ -67,6 +67,43 @@ def test_native_selection_equals_python_mirror(seed):
     assert n_pick > 300
 
 
+@pytest.mark.parametrize("odd", [np.nan, np.inf, -np.inf, "inf_and_minus_inf"])
+def test_native_selection_with_non_finite_medians(odd):
+    """A small leaf (below the 10 000 px floor) whose median depth is NaN or +-inf, as the leaf stage reports it for a leaf with a
+    NaN pixel or mostly infinite depths, among ordinary rows: the float32 mean of the medians is NaN or +-inf, and the tall list
+    follows from it (none; every finite leaf; none) as np.mean and `<` give it in the Python mirror."""
+    rng = np.random.default_rng(11)
+    H, W = 1080, 1920
+    cx, cy, f = 707.87, 494.07, 1750.68
+    ols = _selector(cx, cy, f)
+    n_pick, n_tall = 0, 0
+    for _ in range(200):
+        rows, ext = _random_frame(rng, H, W)
+        if not rows:
+            continue
+        vals = [np.inf, -np.inf] if isinstance(odd, str) else [odd]
+        if len(rows) < len(vals):
+            continue
+        small = [r for r in rows if r["area"] < 10000]
+        for r in rows:
+            if len(small) < len(vals) and r["area"] >= 10000:
+                r["area"] = 25
+                small.append(r)
+        for r, v in zip(small, vals):
+            r["median_depth"] = np.float32(v)
+        with np.errstate(all="ignore"):
+            want = ols._select_from_statistics([dict(r) for r in rows], ext, (H, W))
+        got, tall = _native(rows, ext, H, W, cx, cy, f)
+        assert got == (want if want is not None else -1), (rows, ext)
+        if want is not None:
+            n_pick += 1
+            assert tall == ols.get_tall_leaves()
+            n_tall += len(tall)
+            if not (isinstance(odd, float) and odd == np.inf):
+                assert tall == []
+    assert n_pick > 80 and (n_tall > 0) == (isinstance(odd, float) and odd == np.inf)
+
+
 def test_native_selection_edge_cases():
     H, W = 540, 720
     ols = _selector(360.0, 270.0, 600.0)
