@@ -104,7 +104,9 @@ struct lg_ctx {
     LgOrientWs* orient = nullptr;   // device-side orientation scratch (lg_orient.hip)
     hipEvent_t ev_orient = nullptr, ev_side = nullptr, ev_search = nullptr;
     int opt_dt_algo = 0;            // LG_DT_SEARCH_ALGO=1: one-level row search at every batch size; 2: anchors + bands (3 / 4: with four / one
-                                    // anchor rows per lane); 0: by batch size
+                                    // anchor rows per lane); 5: seed row pairs + stencil bands; 0: by batch size
+    int opt_dt_band_p = 16, opt_dt_band_e = 4;   // LG_DT_BAND_P=12 | 16 | 24 | 32: rows from one seed pair of form 5 to the next;
+                                    // LG_DT_BAND_E=2 | 4: columns per lane of its band kernel (experiments, tests)
     int opt_dt_search = 2;          // LG_DT_SEARCH=0: d_in by the two sweeps for every frame; 1: by the row search wherever it applies;
                                     // 2 (default): per frame, the search while the batch's estimated search work stays below the sweeps' latency
     int prof_on = 0;  // 0 off, 1 every kernel (event pairs on the stream), 2 only launches that stamp their own events
@@ -411,7 +413,9 @@ int lg_create(int device, lg_handle* out) {
     if (const char* e = getenv("LG_CNN_PRUNE")) h->opt_cnn_prune = atoi(e) != 0;
     if (const char* e = getenv("LG_DEFER_PLANES")) h->opt_defer_planes = atoi(e) != 0;
     if (const char* e = getenv("LG_DT_SEARCH")) h->opt_dt_search = std::max(0, std::min(2, atoi(e)));
-    if (const char* e = getenv("LG_DT_SEARCH_ALGO")) h->opt_dt_algo = std::max(0, std::min(4, atoi(e)));
+    if (const char* e = getenv("LG_DT_SEARCH_ALGO")) h->opt_dt_algo = std::max(0, std::min(5, atoi(e)));
+    if (const char* e = getenv("LG_DT_BAND_P")) { const int p = atoi(e); if (p == 12 || p == 16 || p == 24 || p == 32) h->opt_dt_band_p = p; }
+    if (const char* e = getenv("LG_DT_BAND_E")) { const int v = atoi(e); if (v == 2 || v == 4) h->opt_dt_band_e = v; }
     if (const char* e = getenv("LG_SIDE_TAIL")) h->opt_side_tail = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("LG_CNN_CUS")) {
         const int n = atoi(e);
@@ -684,10 +688,13 @@ struct Plan {  // one call's geometry, parameters and plane pointers (absolute, 
 
 
 // which form of the row search a batch of n frames takes (LG_DT_SEARCH_ALGO forces one): one level up to 64 frames of 1080p (one
-// launch, the device is not full: 32 of 1080p 0.14 vs 0.18 ms), anchors + bands above (fewer evaluations: 64 of 4K 1.08 vs 1.54 ms)
+// launch, the device is not full: 32 of 1080p 0.14 vs 0.18 ms); above, two levels: seed row pairs + stencil bands (form 5; 256 of
+// 1080p 0.24 + 0.18 ms against 0.28 + 0.36 for form 2's anchors + searched bands, which took this place before)
 int dt_algo(const lg_ctx* h, int n, int H, int W) {
+    if (h->opt_dt_algo == 5 && (H < 16 || W < 16)) return 1;   // (form 5's seed rows need the room of sixteen rows and columns)
     if (h->opt_dt_algo) return h->opt_dt_algo;
-    return (long long)n * H * W <= 64ll * 1080 * 1920 ? 1 : 2;
+    if ((long long)n * H * W <= 64ll * 1080 * 1920) return 1;
+    return (H < 16 || W < 16) ? 2 : 5;   // seed pairs + stencil bands instead of anchors + searched bands (profiles/NOTES_dt_bands.md)
 }
 
 // frame-border maxima of d_out + stem bits: both read only the bit rows, neither is needed before the plane kernel
@@ -752,7 +759,8 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
     }
     if (h->opt_side_tail) {   // beside the sweeps (latency bound, two workgroups per CU), not behind them: 0.3 ms per 256 frames;
         // LG_SIDE_TAIL=2 puts them on a third stream whatever the batch, so that orientation -> border -> stem is not one chain as
-        // long as the sweeps themselves -- measured slower at 256 frames (9.76-9.94 vs 9.56-9.77 ms per step, three alternating runs)
+        // long as the sweeps themselves -- measured slower at 256 frames (9.76-9.94 vs 9.56-9.77 ms per step, three alternating runs;
+        // again with form 5 of the search, whose chain is the shorter one: 2.196, 2.199 vs 2.135, 2.162 ms, NOTES_dt_bands)
         // Small batches are a chain of latencies, not of throughput: orientation (0.13 ms for one frame), border maxima (0.08) and
         // stem bits (0.01) one behind the other on the side stream were the longest chain between the bit rows and the plane
         // kernel of a single-frame call (0.22 ms; the row search beside them takes 0.08).  Up to 32 frames the border maxima and
@@ -801,7 +809,8 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
         const int algo = dt_algo(h, n, pl.H, pl.W);
         auto launch = [&](int phase) {
             return lg_launch_dtsearch(phase, algo, h->bits + off * words, h->tmp + 2 * off * px, pl.maps[LG_MAP_DISTANCE] + off * px,
-                                      h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, pl.WW, ss);
+                                      h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, pl.WW, ss, h->opt_dt_band_p,
+                                      h->opt_dt_band_e);
         };
         {
             ProfScope ps(h, "dt_search", ss);   // the one-level search, or the anchor rows

@@ -223,9 +223,10 @@ void lg_launch_window(const uint32_t* mf, LgWin* win, int B, int H, int W, int s
 // `tmp` (the d_in half of the sweep workspace, as uint16), then the bounded search over rows, which writes distance_map inside
 // the window and the maximum into maxfix[b][0]
 void lg_launch_hrun(const unsigned long long* bits, uint32_t* tmp, const LgWin* win, int B, int H, int W, int WW, hipStream_t s);
-// algo 1: one-level search (phase 0 only); algo 2: phase 0 = anchor rows (every 8th), phase 1 = the rows between them
+// algo 1: one-level search (phase 0 only); algo 2: phase 0 = anchor rows (every 8th), phase 1 = the rows between them;
+// algo 5 (H, W >= 16): phase 0 = pairs of adjacent rows every band_p rows, phase 1 = the rows between them by stencil sweeps
 int lg_launch_dtsearch(int phase, int algo, const unsigned long long* bits, uint32_t* tmp, float* dist_out, uint32_t* maxfix,
-                       const LgWin* win, int B, int H, int W, int WW, hipStream_t s);
+                       const LgWin* win, int B, int H, int W, int WW, hipStream_t s, int band_p = 16, int band_e = 4);
 int lg_launch_dt(bool bwd, const uint8_t* mask, uint32_t* tmp, float* dist_out, uint32_t* maxfix, const LgWin* win, int B,
                  int H, int W, uint32_t init0, hipStream_t s);   // init0: lg_params.chamfer_init_dist0 (frames without a zero pixel)
 // max d_out outside the sweep windows (closed-form chamfer norm on the frame border) -> atomicMax into maxfix[b][1]

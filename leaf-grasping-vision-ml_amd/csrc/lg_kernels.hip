@@ -1039,7 +1039,14 @@ __global__ __launch_bounds__(256) void lg_dtsearch_kernel(const unsigned long lo
 //                       [anchor above's row, anchor below's row] -- a dozen rows where the nearest edge stays on one side,
 //                       the leaf's whole thickness where the band crosses its medial axis (once per column).
 // ~5x fewer candidate evaluations than the one-level search at the benchmark's leaf size; same integers.
-template <int NP, int ST>   // NP anchor rows per lane, ST (= 8) rows apart: NP = 4 shares every candidate row's load among four
+// PAIR (the seed rows of lg_dtband_kernel): the lane's NP rows are NP / 2 pairs of adjacent rows, ya0 + ST i and ya0 + ST i + 1; no
+// minimising rows are recorded, the 16.16 integers go to the seed rows instead (lg_dt_seed_rows), row pair i of the window in rows
+// 2 i and 2 i + 1 -- distance_map's float is not exact above 2^24 and cannot seed.
+__device__ __forceinline__ uint32_t* lg_dt_seed_rows(uint32_t* tmp, int frame, int H, int W) {
+    // the half of the frame's d_in workspace behind the run distances ([H][W] uint16), 16-byte aligned
+    return tmp + (size_t)frame * 2 * H * W + ((((size_t)H * W + 1) / 2 + 3) & ~(size_t)3);
+}
+template <int NP, int ST, bool PAIR = false>   // NP anchor rows per lane, ST (= 8) rows apart: NP = 4 shares every candidate row's load among four
                             // pixels (large batches); 1 gives four times the waves and a quarter of the work per wave (small
                             // batches: latency)
 __global__ __launch_bounds__(256) void lg_dtanchor_kernel(const unsigned long long* __restrict__ bits,
@@ -1052,27 +1059,31 @@ __global__ __launch_bounds__(256) void lg_dtanchor_kernel(const unsigned long lo
     if (!w.search_in) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int wxe = min(W, w.wx0 + w.nw * wc);
-    constexpr int ROWS = 4 * NP * ST;   // rows per workgroup tile: four waves x NP anchors x ST
+    static_assert(!PAIR || (NP % 2 == 0 && ST >= 4), "pairs of adjacent rows, ST apart");
+    constexpr int NG = PAIR ? NP / 2 : NP;   // rows (pairs) per lane that lie ST apart
+    constexpr int ROWS = 4 * NG * ST;   // rows per workgroup tile: four waves x NG anchors (pairs) x ST
+    auto roff = [](int i) { return PAIR ? ST * (i >> 1) + (i & 1) : ST * i; };   // the lane's i-th row, from ya0
     const int ntx = (wxe - w.wx0 + 63) >> 6, nty = (w.wy1 - w.wy0 + ROWS - 1) / ROWS;
     const int lo = max(w.by0 - 1, 0), hi = min(w.by1 + 1, H - 1);   // candidate rows
     const unsigned long long* fb = bits + (size_t)frame * H * WW;
     const uint16_t* hd = reinterpret_cast<const uint16_t*>(tmp + (size_t)frame * 2 * H * W);
     uint16_t* argb = reinterpret_cast<uint16_t*>(tmp + (size_t)frame * 2 * H * W) + (size_t)H * W;   // [H][W] minimising rows
+    uint32_t* seed = lg_dt_seed_rows(tmp, frame, H, W);   // PAIR: [seed row][W] instead
     float* dout = dist_out + (size_t)frame * H * W;
     uint32_t mx = 0;
-    constexpr int SPAN = ST * (NP - 1) / 2;   // the anchors lie within SPAN rows of the scan's centre
+    constexpr int SPAN = (PAIR ? ST * (NP / 2 - 1) + 1 : ST * (NP - 1)) / 2;   // the anchors lie within SPAN rows of the scan's centre
     const int ntile = __builtin_amdgcn_readfirstlane(ntx * nty);
     for (int tile = j; tile < ntile; tile += G) {
         const int tyi = __builtin_amdgcn_readfirstlane(tile / ntx), txi = tile - tyi * ntx;
         const int wi = (w.wx0 >> 6) + txi;
-        const int x = 64 * wi + lane, ya0 = w.wy0 + ROWS * tyi + ST * NP * wave;
+        const int x = 64 * wi + lane, ya0 = w.wy0 + ROWS * tyi + ST * NG * wave;
         if (ya0 >= w.wy1) continue;   // (wave-uniform)
         const bool xin = x < W;
         const unsigned xc = (unsigned)min(x, W - 1);
         unsigned long long rb[NP];
 #pragma unroll
         for (int i = 0; i < NP; i++) {
-            const int y = ya0 + ST * i;
+            const int y = ya0 + roff(i);
             rb[i] = fb[(unsigned)(min(y, H - 1) * WW + wi)];
             rb[i] = y < w.wy1 ? lg_readlane_u64(rb[i], 0) : 0ull;
         }
@@ -1084,7 +1095,7 @@ __global__ __launch_bounds__(256) void lg_dtanchor_kernel(const unsigned long lo
 #pragma unroll
         for (int i = 0; i < NP; i++) {
             best[i] = (xin && ((rb[i] >> lane) & 1ull)) ? 0xFFFFFFFFu : 0u;
-            arow[i] = ya0 + ST * i;   // an off-leaf pixel is its own nearest zero pixel
+            arow[i] = ya0 + roff(i);   // an off-leaf pixel is its own nearest zero pixel
         }
         if (anyb) {
             const int c = ya0 + SPAN;   // scan outwards from here: rows c - k and c + 1 + k
@@ -1111,7 +1122,7 @@ __global__ __launch_bounds__(256) void lg_dtanchor_kernel(const unsigned long lo
                         const LgH4 hh = lg_h4(hu[q]);
 #pragma unroll
                         for (int i = 0; i < NP; i++) {
-                            const int dy = ya0 + ST * i - yu;
+                            const int dy = ya0 + roff(i) - yu;
                             const uint32_t v = lg_norm5_h(hh, (uint32_t)(dy < 0 ? -dy : dy));
                             arow[i] = v < best[i] ? yu : arow[i];
                             best[i] = min(best[i], v);
@@ -1121,7 +1132,7 @@ __global__ __launch_bounds__(256) void lg_dtanchor_kernel(const unsigned long lo
                         const LgH4 hh = lg_h4(hv[q]);
 #pragma unroll
                         for (int i = 0; i < NP; i++) {
-                            const int dy = ya0 + ST * i - yd;
+                            const int dy = ya0 + roff(i) - yd;
                             const uint32_t v = lg_norm5_h(hh, (uint32_t)(dy < 0 ? -dy : dy));
                             arow[i] = v < best[i] ? yd : arow[i];
                             best[i] = min(best[i], v);
@@ -1132,11 +1143,12 @@ __global__ __launch_bounds__(256) void lg_dtanchor_kernel(const unsigned long lo
         }
 #pragma unroll
         for (int i = 0; i < NP; i++) {
-            const int y = ya0 + ST * i;
+            const int y = ya0 + roff(i);
             mx = max(mx, best[i]);
             if (xin && y < w.wy1) {
                 dout[(unsigned)(y * W) + xc] = (float)best[i] * (1.0f / 65536.0f);
-                argb[(unsigned)(y * W) + xc] = (uint16_t)arow[i];
+                if (PAIR) seed[(size_t)(2 * ((ya0 - w.wy0) / ST + (i >> 1)) + (i & 1)) * W + xc] = best[i];
+                else argb[(unsigned)(y * W) + xc] = (uint16_t)arow[i];
             }
         }
     }
@@ -1312,9 +1324,200 @@ __global__ __launch_bounds__(256) void lg_dtlevel_kernel(const unsigned long lon
     if (lane == 0 && mx) atomicMax(&maxfix[frame * LG_MF + 0], mx);
 }
 
+// ---- the rows between two seed pairs by the 5 x 5 stencil itself (tests/test_dt_band_math.py).  With h the run distance of a
+// pixel's own row,  U(y, x) = min(A h[y][x], U(y-1, x) + A, min U(y-1, x+-1) + B, min(U(y-1, x+-2), U(y-2, x+-1)) + C)  is the
+// distance to the nearest zero pixel at or above row y: an optimal chamfer path uses at most two adjacent generators in any
+// order, so its horizontal steps can all be taken along the source's own row (A h) and nothing is left to scan within the row.
+// Started from the TRUE d on the pair above a band and run downwards, and mirrored from the pair below and run upwards, the
+// minimum of the two is the true d on every row between: a seed is an upper bound the triangle inequality keeps valid, every
+// path from outside the band crosses a pair (a knight's move skips at most one row), sources inside enter through A h.
+// Wave = the P - 2 rows between the pairs at window rows P k and P (k + 1), times 64 E columns, lane = E columns, everything in
+// registers: no LDS, no barrier, nothing waits for another wave.  A stencil step reaches two columns sideways, so what a wave
+// computes is exact 2 (P - 2) columns inside its ends: neighbouring waves overlap by that much on either side and store only
+// their centre.  Rows and columns outside the window are off the leaf (d = h = 0) inside the image and "no path" outside it.
+template <int P, int E, bool VEC>   // VEC: W % E == 0, a lane's E columns are one aligned load / store
+__global__ __launch_bounds__(256) void lg_dtband_kernel(const unsigned long long* __restrict__ bits,
+                                                        const LgWin* __restrict__ wins, uint32_t* __restrict__ tmp,
+                                                        float* __restrict__ dist_out, uint32_t* __restrict__ maxfix, int H, int W,
+                                                        int WW, int wc, int G, int B) {
+    constexpr int N = P - 2, HALO = 2 * N, WCOL = 64 * E, S = WCOL - 2 * HALO, EH = E / 2;
+    static_assert((E == 2 || E == 4) && S > 0 && HALO % E == 0, "whole lanes of halo on either side of a centre");
+    constexpr uint32_t HOUT = LG_HCAP;   // h outside the image: like a row without a zero pixel, an upper bound that beats nothing
+    int frame, j;
+    if (!lg_frame_of_block(G, B, &frame, &j)) return;
+    const LgWin w = wins[frame];
+    if (!w.search_in) return;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wxe = min(W, w.wx0 + w.nw * wc);
+    const int ntx = (wxe - w.wx0 + S - 1) / S, nby = (w.wy1 - w.wy0 - 2 + P - 1) / P;   // band k: rows wy0 + P k + 2 ... < wy1
+    const int r0 = max(w.by0 - 1, 0), r1 = min(w.by1 + 1, H - 1);                  // rows and
+    const int hx0 = (w.bx0 >> 6) << 6, hx1 = min(W, ((w.bx1 >> 6) + 1) << 6);     // columns lg_hrun_kernel wrote
+    const uint16_t* hd = reinterpret_cast<const uint16_t*>(tmp + (size_t)frame * 2 * H * W);
+    const uint32_t* seed = lg_dt_seed_rows(tmp, frame, H, W);
+    float* dout = dist_out + (size_t)frame * H * W;
+    const bool centre = lane * E >= HALO && lane * E < WCOL - HALO;
+    uint32_t mx = 0;
+    const int nunit = __builtin_amdgcn_readfirstlane(ntx * nby);
+    for (int u = 4 * j + wave; u < nunit; u += 4 * G) {
+        const int byi = __builtin_amdgcn_readfirstlane(u / ntx), txi = u - byi * ntx;
+        const int s = w.wy0 + P * byi + 2;               // first row of the band
+        const int xl = w.wx0 + S * txi - HALO + E * lane;   // the lane's first column
+        const bool lane_in = xl >= 0 && xl + E <= W;     // (VEC: a lane lies in the image or outside it)
+        auto col_in = [&](int k) { return VEC ? lane_in : (xl + k >= 0 && xl + k < W); };
+        auto store_row = [&](int y, const uint32_t* v) {   // the centre's columns inside the window; y < wy1
+            float* dst = dout + (size_t)y * W + xl;
+            if (VEC) {
+                if (centre && xl + E <= wxe) {
+                    if (E == 4) *reinterpret_cast<float4*>(dst) = make_float4((float)v[0] * (1.0f / 65536.0f), (float)v[1] * (1.0f / 65536.0f),
+                                                                               (float)v[2] * (1.0f / 65536.0f), (float)v[E - 1] * (1.0f / 65536.0f));
+                    else *reinterpret_cast<float2*>(dst) = make_float2((float)v[0] * (1.0f / 65536.0f), (float)v[1] * (1.0f / 65536.0f));
+#pragma unroll
+                    for (int k = 0; k < E; k++) mx = max(mx, v[k]);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < E; k++)
+                    if (centre && xl + k < wxe) {
+                        dst[k] = (float)v[k] * (1.0f / 65536.0f);
+                        mx = max(mx, v[k]);
+                    }
+            }
+        };
+        const uint32_t zero[E] = {};
+        // a band or a centre beside the bounding box holds no leaf pixel
+        const int xc0 = w.wx0 + S * txi;
+        bool leaf = s <= w.by1 && s + N > w.by0 && xc0 <= w.bx1 && xc0 + S > w.bx0;
+        // ---- A h of the band's rows, two columns per register (uint16 as lg_hrun_kernel wrote them)
+        uint32_t hp[N][EH];
+        if (leaf) {
+            uint32_t any = 0;
+#pragma unroll
+            for (int i = 0; i < N; i++) {
+                const int y = s + i;
+                const bool yin = y < H, hrow = y >= r0 && y <= r1;   // (y >= wy0 + 2)
+                const uint16_t* row = hd + (size_t)(hrow ? y : r0) * W;
+                if (VEC) {
+                    const bool ld = hrow && lane_in && xl >= hx0 && xl < hx1;
+                    const uint16_t* src = row + (ld ? xl : 0);
+                    uint32_t raw[EH];
+                    if (E == 4) { const uint2 v = *reinterpret_cast<const uint2*>(src); raw[0] = v.x; raw[EH - 1] = v.y; }
+                    else raw[0] = *reinterpret_cast<const uint32_t*>(src);
+#pragma unroll
+                    for (int q = 0; q < EH; q++) hp[i][q] = ld ? raw[q] : ((yin && lane_in) ? 0u : (HOUT | (HOUT << 16)));
+                } else {
+                    uint32_t hv[E];
+#pragma unroll
+                    for (int k = 0; k < E; k++) {
+                        const int c = xl + k;
+                        const bool ld = hrow && c >= hx0 && c < hx1;   // (inside the image)
+                        const uint32_t v = row[ld ? c : 0];
+                        hv[k] = ld ? v : ((yin && col_in(k)) ? 0u : HOUT);
+                    }
+#pragma unroll
+                    for (int q = 0; q < EH; q++) hp[i][q] = hv[2 * q] | (hv[2 * q + 1] << 16);
+                }
+                if (y < w.wy1) {
+#pragma unroll
+                    for (int q = 0; q < EH; q++) any |= hp[i][q];
+                }
+            }
+            // h > 0 is a leaf pixel (the centre's columns of rows < wy1 lie in the image unless they are past the window's end)
+            leaf = __any(centre && xl < wxe && any != 0u);
+        }
+        if (!leaf) {
+#pragma unroll
+            for (int i = 0; i < N; i++)
+                if (s + i < w.wy1) store_row(s + i, zero);
+            continue;
+        }
+        // ---- a seed row (any row index: true d where it was searched, else off the leaf / outside the image)
+        auto load_seed = [&](int y, uint32_t* dst) {
+            const bool yin = y >= 0 && y < H;
+            if (y < w.wy0 || y >= w.wy1) {   // (wave-uniform)
+#pragma unroll
+                for (int k = 0; k < E; k++) dst[k] = (yin && col_in(k)) ? 0u : LG_INF;
+                return;
+            }
+            const int rel = y - w.wy0;
+            const uint32_t* row = seed + (size_t)(2 * (rel / P) + rel % P) * W;
+            if (VEC) {
+                const bool ld = lane_in && xl >= w.wx0 && xl < wxe;
+                const uint32_t* src = row + (ld ? xl : 0);
+                uint32_t raw[E];
+                if (E == 4) { const uint4 v = *reinterpret_cast<const uint4*>(src); raw[0] = v.x; raw[1] = v.y; raw[E - 2] = v.z; raw[E - 1] = v.w; }
+                else { const uint2 v = *reinterpret_cast<const uint2*>(src); raw[0] = v.x; raw[1] = v.y; }
+#pragma unroll
+                for (int k = 0; k < E; k++) dst[k] = ld ? raw[k] : (lane_in ? 0u : LG_INF);
+            } else {
+#pragma unroll
+                for (int k = 0; k < E; k++) {
+                    const int c = xl + k;
+                    const bool ld = c >= w.wx0 && c < wxe;
+                    const uint32_t v = row[ld ? c : 0];
+                    dst[k] = ld ? v : (col_in(k) ? 0u : LG_INF);
+                }
+            }
+        };
+        uint32_t p1[E + 4], p2[E + 2];   // the row one step back (columns -2 .. E + 1 of the lane) and the one before (-1 .. E)
+        auto set_p1 = [&](const uint32_t* v) {
+            p1[0] = (uint32_t)lg_wave_shr1((int)LG_INF, (int)v[E - 2]);
+            p1[1] = (uint32_t)lg_wave_shr1((int)LG_INF, (int)v[E - 1]);
+#pragma unroll
+            for (int k = 0; k < E; k++) p1[2 + k] = v[k];
+            p1[E + 2] = (uint32_t)lg_wave_shl1((int)LG_INF, (int)v[0]);
+            p1[E + 3] = (uint32_t)lg_wave_shl1((int)LG_INF, (int)v[1]);
+        };
+        auto start = [&](int y2, int y1) {   // p2 / p1 from the seed rows two steps / one step back
+            uint32_t v[E];
+            load_seed(y2, v);
+            p2[0] = (uint32_t)lg_wave_shr1((int)LG_INF, (int)v[E - 1]);
+#pragma unroll
+            for (int k = 0; k < E; k++) p2[1 + k] = v[k];
+            p2[E + 1] = (uint32_t)lg_wave_shl1((int)LG_INF, (int)v[0]);
+            load_seed(y1, v);
+            set_p1(v);
+        };
+        auto step = [&](const uint32_t* hpi, uint32_t* v) {   // one row of the recurrence, then the row registers move on
+#pragma unroll
+            for (int k = 0; k < E; k++) {
+                const uint32_t ah = (k & 1) ? (hpi[k >> 1] & 0xFFFF0000u) : (hpi[k >> 1] << 16);
+                // equal weights are grouped before they are added: min(x + w, y + w) == min(x, y) + w (values < 2^31)
+                const uint32_t mc = min(min(p2[k], p2[k + 2]), min(p1[k], p1[k + 4])) + LG_C5;
+                const uint32_t mb = min(p1[k + 1], p1[k + 3]) + LG_B5;
+                const uint32_t ma = p1[k + 2] + LG_A5;
+                v[k] = min(min(mc, mb), min(ma, ah));
+            }
+#pragma unroll
+            for (int q = 0; q < E + 2; q++) p2[q] = p1[q + 1];
+            set_p1(v);
+        };
+        uint32_t res[N][E];
+        start(s - 2, s - 1);
+#pragma unroll
+        for (int i = 0; i < N; i++) step(hp[i], res[i]);
+        start(s + N + 1, s + N);
+#pragma unroll
+        for (int i = N - 1; i >= 0; i--) {
+            uint32_t v[E];
+            step(hp[i], v);
+#pragma unroll
+            for (int k = 0; k < E; k++) v[k] = min(v[k], res[i][k]);
+            if (s + i < w.wy1) store_row(s + i, v);
+        }
+    }
+    mx = lg_wave_max_u32(mx);
+    if (lane == 0 && mx) atomicMax(&maxfix[frame * LG_MF + 0], mx);
+}
+
 static int lg_search_groups(int B, int per_batch, int lo, int hi) {
     const int bpad = 8 * ((B + 7) / 8);
     return std::max(lo, std::min(hi, per_batch / bpad));
+}
+// workgroups per frame of lg_dtband_kernel: four waves, each one band x one overlapping column tile at a time
+static int lg_band_groups(int B, int H, int W, int P, int E) {
+    const int S = 64 * E - 4 * (P - 2);
+    const int units = ((W + S - 1) / S + 1) * ((H + P - 1) / P);
+    return std::min((units + 3) / 4, lg_search_groups(B, 16384, 8, 512));
 }
 void lg_launch_hrun(const unsigned long long* bits, uint32_t* tmp, const LgWin* win, int B, int H, int W, int WW, hipStream_t s) {
     const int G = lg_search_groups(B, 2048, 2, 64);
@@ -1328,8 +1531,11 @@ void lg_launch_hrun(const unsigned long long* bits, uint32_t* tmp, const LgWin* 
 // 16 rows.  All exact, up to ten times fewer evaluations, all slower: a level's wave pays its fixed cost -- bit rows, the two
 // solved rows' minimisers, window, stores: three dependent round trips -- for one or three rows of work instead of seven, and
 // the anchors' cost does not halve with their number.  profiles/NOTES_r04.md.)
+// algo 5: pairs of adjacent rows every band_p rows (12, 16, 24 or 32) by the bounded search (phase 0), then the rows between two
+// pairs by the chamfer stencil run down and up in registers, band_e (2 or 4) columns per lane (phase 1: lg_dtband_kernel).
+// Needs H, W >= 16 (the seed rows share the run distances' workspace).
 int lg_launch_dtsearch(int phase, int algo, const unsigned long long* bits, uint32_t* tmp, float* dist_out, uint32_t* maxfix,
-                       const LgWin* win, int B, int H, int W, int WW, hipStream_t s) {
+                       const LgWin* win, int B, int H, int W, int WW, hipStream_t s, int band_p, int band_e) {
     static const int g_env = getenv("LG_DT_SEARCH_G") ? atoi(getenv("LG_DT_SEARCH_G")) : 0;
     const int wc = lg_dt_geometry(W, nullptr);
     const unsigned nb8 = 8u * (unsigned)((B + 7) / 8);
@@ -1339,6 +1545,29 @@ int lg_launch_dtsearch(int phase, int algo, const unsigned long long* bits, uint
         if (phase) return 0;
         const int G = g_env > 0 ? g_env : lg_search_groups(B, 8192, 8, 256);
         LG_LAUNCH_SEARCH(lg_dtsearch_kernel, G);
+        return 1;
+    }
+    if (algo == 5) {   // seed pairs every band_p rows by the bounded search, then the rows between them by stencil sweeps
+        if (phase > 1) return 0;
+        const bool vec = W % band_e == 0;
+#define LG_LAUNCH_BANDS(P_)                                                                                                     \
+    if (phase == 0) {                                                                                                           \
+        const int Gs = g_env > 0 ? g_env : std::min(tx * ((H + 8 * P_ - 1) / (8 * P_)), lg_search_groups(B, 16384, 8, 512));      \
+        LG_LAUNCH_SEARCH((lg_dtanchor_kernel<4, P_, true>), Gs);                                                                \
+    } else if (band_e == 2) {                                                                                                   \
+        const int Gb = g_env > 0 ? g_env : lg_band_groups(B, H, W, P_, 2);                                                      \
+        if (vec) LG_LAUNCH_SEARCH((lg_dtband_kernel<P_, 2, true>), Gb);                                                         \
+        else LG_LAUNCH_SEARCH((lg_dtband_kernel<P_, 2, false>), Gb);                                                            \
+    } else {                                                                                                                    \
+        const int Gb = g_env > 0 ? g_env : lg_band_groups(B, H, W, P_, 4);                                                      \
+        if (vec) LG_LAUNCH_SEARCH((lg_dtband_kernel<P_, 4, true>), Gb);                                                         \
+        else LG_LAUNCH_SEARCH((lg_dtband_kernel<P_, 4, false>), Gb);                                                            \
+    }
+        if (band_p == 12) { LG_LAUNCH_BANDS(12) }
+        else if (band_p == 24) { LG_LAUNCH_BANDS(24) }
+        else if (band_p == 32) { LG_LAUNCH_BANDS(32) }
+        else { LG_LAUNCH_BANDS(16) }
+#undef LG_LAUNCH_BANDS
         return 1;
     }
     if (phase == 0) {
