@@ -376,6 +376,12 @@ int lg_near_tile_rect(int bx0, int bx1, int by0, int by1, int H, int W, int halo
    pixel -- a batch may still take the sweeps), area, columns per sweep wave}.  LG_ERR_INVALID for a bad argument or a width
    the sweeps do not take (W > 8192). */
 int lg_window_from_box(const uint32_t box[5], int H, int W, int search_mode, int32_t out[12]);
+/* Max d_out along one frame border line on the host (no device, no handle), the pruned search the device runs.  prof[i], i in
+   [0, n): distance from the line of the nearest leaf pixel in line position lo + i, -1 where there is none; the line has `len`
+   positions, 0 <= lo, lo + n <= len, 1 <= n, every entry <= 16384.  *out = max over p in {lo .. lo + n - 1, 0, len - 1} of the
+   min over the entries >= 0 of the 5 x 5 chamfer norm of (|p - (lo + i)|, prof[i]) in 16.16 fixed point; 0xFFFFFFFF when no
+   entry is >= 0.  LG_ERR_INVALID for a bad argument. */
+int lg_border_line_max(const int32_t* prof, int n, int lo, int len, uint32_t* out);
 /* off[0 .. B] = first entry of every frame's near tiles in the list the last lg_select_grasp* call on this handle launched its
    plane kernel on (off[0] = 0, off[B] = the list's length; frame b has off[b + 1] - off[b] near tiles).  cap >= B + 1.
    LG_ERR_INVALID when that call did not take the near launch (planes or validity taken back, LG_FINAL_NEAR=0, LG_SUBBATCH,

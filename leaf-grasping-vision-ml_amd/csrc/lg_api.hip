@@ -640,6 +640,14 @@ int lg_window_from_box(const uint32_t box[5], int H, int W, int search_mode, int
     return LG_OK;
 }
 
+int lg_border_line_max(const int32_t* prof, int n, int lo, int len, uint32_t* out) {
+    if (!prof || !out || n < 1 || lo < 0 || len > 16384 || lo > len - n) return LG_ERR_INVALID;
+    for (int i = 0; i < n; i++)
+        if (prof[i] < -1 || prof[i] > 16384) return LG_ERR_INVALID;   // (the norm of two such lengths stays below 2^32)
+    lg_border_search(prof, n, lo, len, out);
+    return LG_OK;
+}
+
 int lg_debug_near_tiles(lg_handle h, int32_t* off, int cap) {
     if (!h || !off) return LG_ERR_INVALID;
     LG_ENTER(h);
@@ -760,11 +768,14 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
     if (h->opt_side_tail) {   // beside the sweeps (latency bound, two workgroups per CU), not behind them: 0.3 ms per 256 frames;
         // LG_SIDE_TAIL=2 puts them on a third stream whatever the batch, so that orientation -> border -> stem is not one chain as
         // long as the sweeps themselves -- measured slower at 256 frames (9.76-9.94 vs 9.56-9.77 ms per step, three alternating runs;
-        // again with form 5 of the search, whose chain is the shorter one: 2.196, 2.199 vs 2.135, 2.162 ms, NOTES_dt_bands)
-        // Small batches are a chain of latencies, not of throughput: orientation (0.13 ms for one frame), border maxima (0.08) and
-        // stem bits (0.01) one behind the other on the side stream were the longest chain between the bit rows and the plane
-        // kernel of a single-frame call (0.22 ms; the row search beside them takes 0.08).  Up to 32 frames the border maxima and
-        // the stem bits go to a stream of their own (s_dt[0]; the search uses s_dt[1]).
+        // again with form 5 of the search, whose chain is the shorter one: 2.196, 2.199 vs 2.135, 2.162 ms, NOTES_dt_bands; and
+        // with the pruned border search and the two-level hull test, which make the side chain the shorter one again, 0.34 against
+        // 0.45 ms: 2.074, 2.093 vs 2.044 .. 2.061 ms, NOTES_side_chain)
+        // Small batches are a chain of latencies, not of throughput: orientation (0.13 ms for one frame; 0.10 since the two-level
+        // hull test), border maxima (0.08; 0.035 since the pruned search) and stem bits (0.01) one behind the other on the side
+        // stream were the longest chain between the bit rows and the plane kernel of a single-frame call (0.22 ms; the row search
+        // beside them takes 0.10).  Up to 32 frames the border maxima and the stem bits go to a stream of their own (s_dt[0]; the
+        // search uses s_dt[1]).
         const bool own_tail = h->opt_subbatch == 0 && (h->opt_side_tail == 2 || n <= 32);
         hipStream_t ts = own_tail ? h->s_dt[0] : h->copy_stream;
         if (ts != h->copy_stream) LG_HIP(h, hipStreamWaitEvent(ts, ev_prep, 0));

@@ -67,6 +67,52 @@ __host__ __device__ inline uint32_t lg_norm5(int dx, int dy) {   // closed-form 
     const uint32_t a = (uint32_t)(dx > dy ? dx : dy), b = (uint32_t)(dx > dy ? dy : dx);
     return 2u * b <= a ? (a - 2u * b) * LG_A5 + b * LG_C5 : (a - b) * LG_C5 + (2u * b - a) * LG_B5;
 }
+// ---- max d_out along one frame border line (lg_dout_border_kernel; host export lg_border_line_max)
+// prof[i], i in [0, n): distance from the border line of the nearest leaf pixel in line position lo + i (-1: none).  A candidate
+// p on the line has d_out(p) = min over the entries i with prof[i] >= 0 of lg_norm5(|p - (lo + i)|, prof[i]); the line's maximum
+// lies among p in {lo .. lo + n - 1, 0, len - 1} (see the kernel).  lg_norm5 is monotone in both arguments, which gives an exact
+// pruned search: the two ends are evaluated in full (lg_border_end_part) and seed `best`; a span candidate visits the entries
+// outwards from its own position, i = c - k and c + k for k = 0, 1, ..., and stops
+//   (a) once its running minimum dmin <= best: dmin only falls, the candidate cannot raise the maximum;
+//   (b) once lg_norm5(k, m) >= dmin, m = the smallest entry >= 0: no entry at distance >= k can lower dmin;
+//   (c) when both directions have left the profile.
+// (b) and (c) leave dmin exact, (a) drops only candidates bounded by a value already attained: the maximum keeps its bits.
+__host__ __device__ inline uint32_t lg_border_cand_min(const int32_t* prof, int n, int c, int m, uint32_t best) {
+    uint32_t dmin = 0xFFFFFFFFu;
+    for (int k = 0; k < n; k++) {
+        const int il = c - k, ir = c + k;
+        if (il < 0 && ir >= n) break;                                   // (c)
+        if (lg_norm5(k, m) >= dmin) break;                              // (b)
+        if (il >= 0) { const int d = prof[il]; if (d >= 0) { const uint32_t v = lg_norm5(k, d); dmin = v < dmin ? v : dmin; } }
+        if (ir < n && k) { const int d = prof[ir]; if (d >= 0) { const uint32_t v = lg_norm5(k, d); dmin = v < dmin ? v : dmin; } }
+        if (dmin <= best) break;                                        // (a)
+    }
+    return dmin;
+}
+// entries t, t + nt, ... of the profile against line position p: their minimum (0xFFFFFFFF: none of them holds a leaf pixel)
+__host__ __device__ inline uint32_t lg_border_end_part(const int32_t* prof, int n, int lo, int p, int t, int nt) {
+    uint32_t dmin = 0xFFFFFFFFu;
+    for (int i = t; i < n; i += nt) {
+        const int d = prof[i], dx = p - (lo + i);
+        if (d >= 0) { const uint32_t v = lg_norm5(dx < 0 ? -dx : dx, d); dmin = v < dmin ? v : dmin; }
+    }
+    return dmin;
+}
+// The whole search by one thread, as the kernel's 256 threads compose it (ends, then the span against the running maximum).
+// *out = 0xFFFFFFFF when no entry holds a leaf pixel (every candidate's minimum is over nothing).
+__host__ __device__ inline void lg_border_search(const int32_t* prof, int n, int lo, int len, uint32_t* out) {
+    int m = 0x7fffffff;
+    for (int i = 0; i < n; i++) if (prof[i] >= 0 && prof[i] < m) m = prof[i];
+    if (m == 0x7fffffff) { *out = 0xFFFFFFFFu; return; }
+    const uint32_t e0 = lg_border_end_part(prof, n, lo, 0, 0, 1), e1 = lg_border_end_part(prof, n, lo, len - 1, 0, 1);
+    uint32_t best = e0 > e1 ? e0 : e1;
+    for (int c = 0; c < n; c++) {
+        const uint32_t d = lg_border_cand_min(prof, n, c, m, best);
+        best = d > best ? d : best;
+    }
+    *out = best;
+}
+
 // A frame's LgWin from the five words the bit-row pass accumulated (box = &maxfix[frame * LG_MF + LG_BOX_X0], see LG_MF).  wc,
 // nw_max: lg_dt_geometry(W).  search_in is the frame's own eligibility (search_mode != 0, a non-empty mask with at least one
 // zero pixel); lg_window_kernel clears it for the whole batch when the sweeps win (search_mode 2).  lg_window_kernel and the

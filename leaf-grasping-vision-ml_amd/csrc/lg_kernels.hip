@@ -438,6 +438,7 @@ void lg_launch_window(const uint32_t* mf, LgWin* win, int B, int H, int W, int s
 // the maximum over the outside region sits on the frame border, and beyond the bounding box's span at a frame corner.
 // grid (4, B): side 0 = top row, 1 = bottom row, 2 = left column, 3 = right column.  For a candidate on the top row
 // only the topmost leaf pixel of each column can be the nearest one of that column (same dx, smallest dy), etc.
+__device__ __forceinline__ uint32_t lg_wave_min_u32(uint32_t v);   // (with the row search below)
 __global__ __launch_bounds__(256) void lg_dout_border_kernel(const unsigned long long* __restrict__ bits,
                                                              const LgWin* __restrict__ wins, uint32_t* __restrict__ maxfix,
                                                              int H, int W, int WW, int wc) {
@@ -451,20 +452,23 @@ __global__ __launch_bounds__(256) void lg_dout_border_kernel(const unsigned long
     const unsigned long long* fb = bits + (size_t)frame * H * WW;
     const bool horiz = side < 2;                     // candidates along x, profile indexed by column
     const int lo = horiz ? w.bx0 : w.by0, hi = horiz ? w.bx1 : w.by1, n = hi - lo + 1;
+    __shared__ uint32_t s_red[4];                    // minima of the two ends and of the profile; the running maximum
+    if (t == 0) { s_red[0] = 0xFFFFFFFFu; s_red[1] = 0xFFFFFFFFu; s_red[2] = 0x7FFFFFFFu; s_red[3] = 0; }
     if (horiz) {
-        // thread q owns one 64-column word of the bounding box and walks the rows from the border inwards, 8 rows per
-        // round trip; a column's profile entry is the row at which its bit is first seen
-        for (int i = t; i < n; i += 256) s_prof[i] = -1;
+        // item = (64-column word of the bounding box) x (chunk of its rows): a thread walks its chunk from the border inwards, 8
+        // rows per round trip; a column's profile entry is the smallest distance at which any chunk saw its bit (atomicMin)
+        for (int i = t; i < n; i += 256) s_prof[i] = 0x7FFFFFFF;
         __syncthreads();
-        const int q = (w.bx0 >> 6) + t;
-        if (q <= (w.bx1 >> 6)) {
+        const int q0 = w.bx0 >> 6, nq = (w.bx1 >> 6) - q0 + 1, rows = w.by1 - w.by0 + 1;
+        const int nch = max(1, min(256 / nq, (rows + 7) / 8)), rc = (rows + nch - 1) / nch;
+        for (int it = t; it < nq * nch; it += 256) {
+            const int q = q0 + it % nq, ra = (it / nq) * rc, rb = min(rows, ra + rc);
             unsigned long long seen = 0;
-            const int rows = w.by1 - w.by0 + 1;
-            for (int r0 = 0; r0 < rows; r0 += 8) {
+            for (int r0 = ra; r0 < rb; r0 += 8) {
                 unsigned long long v[8];
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
-                    const int r = min(r0 + j, rows - 1);
+                    const int r = min(r0 + j, rb - 1);
                     const int y = side == 0 ? w.by0 + r : w.by1 - r;
                     v[j] = fb[(size_t)y * WW + q];
                 }
@@ -472,16 +476,18 @@ __global__ __launch_bounds__(256) void lg_dout_border_kernel(const unsigned long
                 for (int j = 0; j < 8; j++) {
                     unsigned long long nb = v[j] & ~seen;
                     seen |= v[j];
-                    const int r = min(r0 + j, rows - 1);
+                    const int r = min(r0 + j, rb - 1);
                     const int dist = side == 0 ? w.by0 + r : H - 1 - (w.by1 - r);
                     while (nb) {
                         const int c = 64 * q + __builtin_ctzll(nb);
                         nb &= nb - 1;
-                        s_prof[c - lo] = dist;
+                        atomicMin(&s_prof[c - lo], dist);
                     }
                 }
             }
         }
+        __syncthreads();
+        for (int i = t; i < n; i += 256) if (s_prof[i] == 0x7FFFFFFF) s_prof[i] = -1;   // (the entries this thread reads below)
     } else {
         for (int i = t; i < n; i += 256) {
             int d = -1;
@@ -493,19 +499,27 @@ __global__ __launch_bounds__(256) void lg_dout_border_kernel(const unsigned long
             }
             s_prof[i] = d;
         }
+        __syncthreads();                                 // (s_red)
+    }
+    // the two ends of the line in full, and the smallest entry: every thread its share of the profile (the entries it wrote)
+    const int len = horiz ? W : H;
+    {
+        uint32_t m = 0x7FFFFFFFu;
+        for (int i = t; i < n; i += 256) { const int d = s_prof[i]; if (d >= 0) m = min(m, (uint32_t)d); }
+        const uint32_t e0 = lg_wave_min_u32(lg_border_end_part(s_prof, n, lo, 0, t, 256));
+        const uint32_t e1 = lg_wave_min_u32(lg_border_end_part(s_prof, n, lo, len - 1, t, 256));
+        m = lg_wave_min_u32(m);
+        if ((t & 63) == 0) { atomicMin(&s_red[0], e0); atomicMin(&s_red[1], e1); atomicMin(&s_red[2], m); }
     }
     __syncthreads();
-    // candidates: the span of the bounding box plus the two ends of the line
-    const int len = horiz ? W : H;
-    uint32_t best = 0;
-    for (int ci = t; ci < n + 2; ci += 256) {
-        const int p = ci < n ? lo + ci : (ci == n ? 0 : len - 1);
-        uint32_t dmin = 0xFFFFFFFFu;
-        for (int i = 0; i < n; i++) {
-            const int d = s_prof[i];
-            if (d >= 0) dmin = min(dmin, lg_norm5(abs(p - (lo + i)), d));
-        }
-        best = max(best, dmin);
+    // span candidates, one per lane and round, against the running maximum (lg_border_cand_min).  s_red[3] shares what the
+    // other lanes found: a stale, lower value only prunes less, and a maximum does not depend on the order
+    const int m = (int)s_red[2];
+    uint32_t best = max(s_red[0], s_red[1]);
+    for (int c = t; c < n; c += 256) {
+        best = max(best, __hip_atomic_load(&s_red[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        const uint32_t d = lg_border_cand_min(s_prof, n, c, m, best);
+        if (d > best) { best = d; atomicMax(&s_red[3], d); }
     }
     best = lg_wave_max_u32(best);
     if ((t & 63) == 0 && best) atomicMax(&maxfix[frame * LG_MF + 1], best);

@@ -9,8 +9,9 @@
 //   C  more than one component: outer-border following per component (one lane each, Suzuki-Abe like the host), shoelace
 //      sum in int64 (exact: the host's double sum never rounds either); largest area wins, first in raster order on ties
 //   D  leftmost / rightmost pixel of the chosen component per row: only these can be hull vertices
-//   E  strict vertices of the left (convex) and right (concave) chains by exact integer slope comparisons, compacted in the
-//      order Andrew's monotone chain produces (counter-clockwise from the lexicographically smallest point)
+//   E  strict vertices of the left (convex) and right (concave) chains by exact integer slope comparisons (in two levels: every
+//      row against its block of 16 rows, then the blocks' vertices against each other), compacted in the order Andrew's
+//      monotone chain produces (counter-clockwise from the lexicographically smallest point)
 //   F  min-area rectangle over the hull edges in float64, no fused multiply-add (the host code has none): first minimum in
 //      edge order, then atan2 / fmod, sin and cos for the score-plane kernel
 // A frame with more runs than the scratch holds (or more hull vertices than LDS holds) gets status 1: the caller analyses
@@ -135,6 +136,39 @@ struct FrameScratch {
     int* comp;              // [4][cap] per component (indexed by its root run): interior pixels, min x, max x, last row
 };
 
+// -DLG_ORIENT_PHASES (off in the shipped build; LG_VARIANT_SRC=lg_orient.hip tools/build_variants.sh "phases:-DLG_ORIENT_PHASES"):
+// thread 0 of the first OPH_FRAMES frames of a launch stamps wall_clock64() (100 MHz) at the kernel's start, behind the steps A, B,
+// C, D, E, behind the compaction and at the end; lg_debug_orient_phases reads the stamps (tools/orient_phases.py prints them)
+#ifdef LG_ORIENT_PHASES
+constexpr int OPH_FRAMES = 256, OPH_N = 8;
+__device__ unsigned long long lg_orient_phase_clk[OPH_FRAMES * OPH_N];
+#define OPHASE(k) do { if (tid == 0 && b < OPH_FRAMES) lg_orient_phase_clk[b * OPH_N + (k)] = wall_clock64(); } while (0)
+#else
+#define OPHASE(k) do { } while (0)
+#endif
+
+constexpr int OBLK = 16;   // rows per block of step E's first level (a power of two, at most 64)
+
+// Step E's vertex test on the rows row(ja) < ... < row(jb - 1): is row(j) a strict vertex of their left chain (LEFT: lower
+// convex envelope of X over the rows -- the steepest slope arriving from above is smaller than the flattest slope leaving
+// downwards) or of their right chain (mirrored)?  The first and the last row always are.  Exact integer comparisons.
+template <bool LEFT, class RowOf>
+__device__ __forceinline__ bool hull_vertex(const short* X, RowOf row, int ja, int j, int jb) {
+    if (j == ja || j == jb - 1) return true;
+    const int i = row(j), xi = X[i], ra = row(ja), rb = row(j + 1);
+    int p = xi - X[ra], q = i - ra;                      // arriving slopes (x_i - x_a) / (i - a): max (left), min (right)
+    for (int a = ja + 1; a < j; a++) {
+        const int r = row(a), qq = i - r, pp = xi - X[r];
+        if (LEFT ? pp * q > p * qq : pp * q < p * qq) { p = pp; q = qq; }
+    }
+    int p2 = X[rb] - xi, q2 = rb - i;                    // leaving slopes (x_b - x_i) / (b - i): min (left), max (right)
+    for (int c = j + 2; c < jb; c++) {
+        const int r = row(c), qq = r - i, pp = X[r] - xi;
+        if (LEFT ? pp * q2 < p2 * qq : pp * q2 > p2 * qq) { p2 = pp; q2 = qq; }
+    }
+    return LEFT ? p * q2 < p2 * q : p * q2 > p2 * q;
+}
+
 __device__ void write_none(LgFrameParams* fp, double* out, int* status, int b, int st) {
     LgFrameParams f;
     f.sin_t = 0.f; f.cos_t = 0.f; f.has_angle = 0; f.theta = __builtin_nanf("");
@@ -148,7 +182,8 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
                                                        int* row_start_, short* rowL_, short* rowR_, unsigned char* vflag_,
                                                        int* comp_, LgFrameParams* fp, double* out, int* status) {
 #pragma clang fp contract(off)
-    extern __shared__ __align__(16) unsigned char s_dyn[];   // parent[cap] | L[n], R[n] shorts | hull x[OHULL], y[OHULL] doubles
+    // parent[cap] | L[n], R[n] shorts, survivor lists [n], [n], ballots | hull x[OHULL], y[OHULL] doubles
+    extern __shared__ __align__(16) unsigned char s_dyn[];
     __shared__ int s_scan[OT];
     __shared__ int s_nroots, s_ybot, s_rank, s_lb, s_ncand, s_cand;
     __shared__ u64 s_key, s_p0;
@@ -167,6 +202,7 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
     Band bd;
     bd.rows = bits + ((size_t)b * H + w.by0) * WW; bd.hy = hyb; bd.W = W; bd.WW = WW; bd.w0 = w.bx0 >> 6; bd.w1 = w.bx1 >> 6;
     if (tid == 0) { s_nroots = 0; s_ybot = 0; s_key = 0; s_p0 = ~0ull; s_rank = 0x7fffffff; s_lb = 0; s_ncand = 0; s_cand = 0; }
+    OPHASE(0);
     // ---- A: runs.  Thread t owns the rows [r0, r1)
     const int chunk = (hyb + OT - 1) / OT, r0 = min(tid * chunk, hyb), r1 = min(r0 + chunk, hyb);
     int sum = 0;
@@ -220,6 +256,7 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
     }
     if (tid == 0) fs.row_start[hyb] = R;
     __syncthreads();
+    OPHASE(1);
     // ---- B: union runs that touch the previous row (8-connectivity: overlap after growing by one pixel)
     for (int i = tid; i < R; i += OT) {
         const int r = fs.run_y[i];
@@ -250,6 +287,7 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
     for (int i = tid; i < R; i += OT) parent[i] = uf_find(parent, i);   // (a root stays a root: concurrent reads still end there)
     const int nroots = s_nroots;
     __syncthreads();
+    OPHASE(2);
     // ---- C: the component with the largest outer contour
     int best;
     if (nroots == 1) {
@@ -307,6 +345,7 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
         __syncthreads();
         best = 0xfffff - (int)(s_key & 0xfffffull);
     }
+    OPHASE(3);
     // ---- D: per row, leftmost / rightmost pixel of that component
     for (int r = r0; r < r1; r++) {
         int L = -1, Rr = -1;
@@ -325,32 +364,56 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
     short* Rs = Ls + n;
     for (int i = tid; i < n; i += OT) { Ls[i] = fs.rowL[ytop + i]; Rs[i] = fs.rowR[ytop + i]; }
     __syncthreads();
+    OPHASE(4);
     // ---- E: strict hull vertices.  Left chain = lower convex envelope of L over the rows: row i is a vertex iff the
     // steepest slope arriving from above is smaller than the flattest slope leaving downwards; right chain mirrored.
-    for (int i = tid; i < n; i += OT) {
-        bool vl = true, vr = true;
-        if (i > 0 && i < n - 1) {
-            const int li = Ls[i], ri = Rs[i];
-            int lp = li - Ls[0], lq = i, rp = ri - Rs[0], rq = i;              // arriving slopes (x_i - x_a) / (i - a)
-            for (int a = 1; a < i; a++) {
-                const int q = i - a, pl = li - Ls[a], pr = ri - Rs[a];
-                if (pl * lq > lp * q) { lp = pl; lq = q; }                         // max for the left chain
-                if (pr * rq < rp * q) { rp = pr; rq = q; }                         // min for the right chain
-            }
-            int lp2 = Ls[i + 1] - li, lq2 = 1, rp2 = Rs[i + 1] - ri, rq2 = 1;  // leaving slopes (x_b - x_i) / (b - i)
-            for (int c = i + 2; c < n; c++) {
-                const int q = c - i, pl = Ls[c] - li, pr = Rs[c] - ri;
-                if (pl * lq2 < lp2 * q) { lp2 = pl; lq2 = q; }                     // min
-                if (pr * rq2 > rp2 * q) { rp2 = pr; rq2 = q; }                     // max
-            }
-            vl = lp * lq2 < lp2 * lq;
-            vr = rp * rq2 > rp2 * rq;
+    // In two levels: a strict vertex of the hull of all rows is a strict vertex of the hull of any subset that holds it, and the
+    // hull of all rows is the hull of the subsets' vertices.  Level 1 tests every row against the rows of its own block of
+    // OBLK; level 2 tests the survivors of a chain against each other -- the same integer comparisons on fewer rows.
+    uint16_t* listL = (uint16_t*)(Rs + n);                // level-1 survivors of the two chains, ascending rows
+    uint16_t* listR = listL + n;
+    u64* mskL = (u64*)(s_dyn + 8 * (size_t)n);            // their ballots per 64 rows
+    const int nseg = (n + 63) >> 6;
+    u64* mskR = mskL + nseg;
+    const auto same = [](int j) { return j; };
+    for (int base = 0; base < n; base += OT) {            // (every lane of a wave takes part in the ballots)
+        const int i = base + tid;
+        bool vl = false, vr = false;
+        if (i < n) {
+            const int b0 = i & ~(OBLK - 1), b1 = min(b0 + OBLK, n);
+            vl = hull_vertex<true>(Ls, same, b0, i, b1);
+            vr = hull_vertex<false>(Rs, same, b0, i, b1);
+            if (!vl) fs.vflag[i] = 0;
+            if (!vr) fs.vflag[H + i] = 0;
         }
-        // the chains meet at the top and bottom rows: a shared end point is listed once (with the left chain)
-        if ((i == 0 || i == n - 1) && Ls[i] == Rs[i]) vr = false;
-        fs.vflag[i] = vl; fs.vflag[H + i] = vr;
+        const u64 ml = __ballot(vl), mr = __ballot(vr);
+        if ((tid & 63) == 0 && i < n) { mskL[i >> 6] = ml; mskR[i >> 6] = mr; }
     }
     __syncthreads();
+    int SL = 0, SR = 0, sdone = 0;                        // survivors in the 64-row segments [0, sdone)
+    for (int base = 0; base < n; base += OT) {
+        const int i = base + tid, seg = i >> 6, lane = tid & 63;
+        if (seg >= nseg) break;
+        for (; sdone < seg; sdone++) { SL += __popcll(mskL[sdone]); SR += __popcll(mskR[sdone]); }
+        const u64 ml = mskL[seg], mr = mskR[seg], below = (1ull << lane) - 1ull;
+        if ((ml >> lane) & 1ull) listL[SL + __popcll(ml & below)] = (uint16_t)i;
+        if ((mr >> lane) & 1ull) listR[SR + __popcll(mr & below)] = (uint16_t)i;
+    }
+    for (; sdone < nseg; sdone++) { SL += __popcll(mskL[sdone]); SR += __popcll(mskR[sdone]); }
+    __syncthreads();
+    for (int it = tid; it < SL + SR; it += OT) {
+        if (it < SL) {
+            fs.vflag[listL[it]] = hull_vertex<true>(Ls, [listL](int j) { return (int)listL[j]; }, 0, it, SL);
+        } else {
+            const int k = it - SL, i = listR[k];
+            bool vr = hull_vertex<false>(Rs, [listR](int j) { return (int)listR[j]; }, 0, k, SR);
+            // the chains meet at the top and bottom rows: a shared end point is listed once (with the left chain)
+            if ((i == 0 || i == n - 1) && Ls[i] == Rs[i]) vr = false;
+            fs.vflag[H + i] = vr;
+        }
+    }
+    __syncthreads();
+    OPHASE(5);
     // order: left chain bottom -> top, then right chain top -> bottom (Andrew's monotone chain on (x, y) walks the hull
     // this way round); the start at the lexicographically smallest point is applied as a rotation below
     const int chn = (n + OT - 1) / OT, i0 = min(tid * chn, n), i1 = min(i0 + chn, n);
@@ -394,6 +457,7 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
         }
         return;
     }
+    OPHASE(6);
     // ---- F: min-area rectangle, one hull edge per thread (edge e starts at hull vertex e counted from the smallest point)
     const int pos0 = (int)(s_p0 & 0xffffull);
     double m_area = 1e300, m_ux = 0, m_uy = 0, m_w = 0, m_h = 0, m_sc = 0, m_tc = 0;
@@ -446,12 +510,22 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
         o[3] = m_sc * m_ux - m_tc * m_uy; o[4] = m_sc * m_uy + m_tc * m_ux;
         status[b] = 0;
     }
+    OPHASE(7);
 }
 
 template <typename T>
 hipError_t dalloc(T** p, size_t n) { return hipMalloc((void**)p, n * sizeof(T)); }
 
 }  // namespace
+
+#ifdef LG_ORIENT_PHASES
+// out[frame][8]: the stamps of the last launch's first `frames` frames (synchronise the launch's stream first)
+extern "C" int lg_debug_orient_phases(unsigned long long* out, int frames) {
+    if (!out || frames < 1 || frames > OPH_FRAMES) return LG_ERR_INVALID;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(lg_orient_phase_clk), sizeof(unsigned long long) * OPH_N * frames) == hipSuccess
+               ? LG_OK : LG_ERR_HIP;
+}
+#endif
 
 void lg_orient_free(LgOrientWs*& w) {
     if (!w) return;
@@ -485,8 +559,9 @@ int lg_orient_ensure(LgOrientWs*& w, int B, int H, std::string* err) {
         return LG_ERR_NOMEM;
     }
     w->capB = nB; w->H = H;
-    // LDS: parent[cap] ints, later two short rows [H] and the hull (2 * OHULL doubles)
-    w->lds = std::max(std::max((size_t)w->cap * 4, (size_t)H * 4), (size_t)OHULL * 16);
+    // LDS: parent[cap] ints; later step E's two short rows [H], two survivor lists [H] and two ballots per 64 rows; then the
+    // hull (2 * OHULL doubles)
+    w->lds = std::max(std::max((size_t)w->cap * 4, (size_t)H * 8 + ((size_t)H / 64 + 1) * 16), (size_t)OHULL * 16);
     rc = hipFuncSetAttribute((const void*)lg_orient_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w->lds);
     if (rc != hipSuccess) {
         if (err) *err = std::string("orientation kernel LDS: ") + hipGetErrorString(rc);
