@@ -361,6 +361,10 @@ int lg_debug_dt_max(lg_handle h, int frame, uint32_t out[2], int32_t win[4]);
 /* form[0] = 1: d_in of that frame came from the row search (0: from the two sweeps); form[1] = 1: its d_out sweeps were
    skipped (the maximum provably lies on the frame border).  Which form a batch takes is decided on the device. */
 int lg_debug_dt_form(lg_handle h, int frame, int32_t form[2]);
+/* *algo = the form of the row search the last call queued for its searched frames (LG_DT_SEARCH_ALGO's numbering: 1 one level,
+   2 anchors + searched bands, 3 / 4 the same with four / one anchor rows per lane when forced, 5 seed pairs + stencil bands,
+   6 one register sweep per frame); 0: the handle queues no search. */
+int lg_debug_dt_search_form(lg_handle h, int32_t* algo);
 /* The near tiles of a frame on the host (no device, no handle), the code the device runs: the tiles (64 x 16 pixels) of the
    score-plane kernel whose look at the mask can meet the mask's bounding box [bx0, bx1] x [by0, by1] (bx1 < bx0: empty) in an
    H x W frame, halo = gaussian_size / 2 + 1.  They form a rectangle of the tile grid: rect = {tx_lo, tx_hi, ty_lo, ty_hi},

@@ -104,7 +104,9 @@ struct lg_ctx {
     LgOrientWs* orient = nullptr;   // device-side orientation scratch (lg_orient.hip)
     hipEvent_t ev_orient = nullptr, ev_side = nullptr, ev_search = nullptr;
     int opt_dt_algo = 0;            // LG_DT_SEARCH_ALGO=1: one-level row search at every batch size; 2: anchors + bands (3 / 4: with four / one
-                                    // anchor rows per lane); 5: seed row pairs + stencil bands; 0: by batch size
+                                    // anchor rows per lane); 5: seed row pairs + stencil bands; 6: one two-wave register sweep per frame;
+                                    // 0: by batch size
+    int last_dt_algo = 0;           // lg_debug_dt_search_form: the form the row search of the last call took (0: no search was queued)
     int opt_dt_band_p = 16, opt_dt_band_e = 4;   // LG_DT_BAND_P=12 | 16 | 24 | 32: rows from one seed pair of form 5 to the next;
                                     // LG_DT_BAND_E=2 | 4: columns per lane of its band kernel (experiments, tests)
     int opt_dt_search = 2;          // LG_DT_SEARCH=0: d_in by the two sweeps for every frame; 1: by the row search wherever it applies;
@@ -413,7 +415,7 @@ int lg_create(int device, lg_handle* out) {
     if (const char* e = getenv("LG_CNN_PRUNE")) h->opt_cnn_prune = atoi(e) != 0;
     if (const char* e = getenv("LG_DEFER_PLANES")) h->opt_defer_planes = atoi(e) != 0;
     if (const char* e = getenv("LG_DT_SEARCH")) h->opt_dt_search = std::max(0, std::min(2, atoi(e)));
-    if (const char* e = getenv("LG_DT_SEARCH_ALGO")) h->opt_dt_algo = std::max(0, std::min(5, atoi(e)));
+    if (const char* e = getenv("LG_DT_SEARCH_ALGO")) h->opt_dt_algo = std::max(0, std::min(6, atoi(e)));
     if (const char* e = getenv("LG_DT_BAND_P")) { const int p = atoi(e); if (p == 12 || p == 16 || p == 24 || p == 32) h->opt_dt_band_p = p; }
     if (const char* e = getenv("LG_DT_BAND_E")) { const int v = atoi(e); if (v == 2 || v == 4) h->opt_dt_band_e = v; }
     if (const char* e = getenv("LG_SIDE_TAIL")) h->opt_side_tail = std::max(0, std::min(2, atoi(e)));
@@ -670,6 +672,13 @@ int lg_debug_dt_form(lg_handle h, int frame, int32_t form[2]) {
     return LG_OK;
 }
 
+int lg_debug_dt_search_form(lg_handle h, int32_t* algo) {
+    if (!h || !algo) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    *algo = h->last_dt_algo;
+    return LG_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -698,10 +707,17 @@ struct Plan {  // one call's geometry, parameters and plane pointers (absolute, 
 // which form of the row search a batch of n frames takes (LG_DT_SEARCH_ALGO forces one): one level up to 64 frames of 1080p (one
 // launch, the device is not full: 32 of 1080p 0.14 vs 0.18 ms); above, two levels: seed row pairs + stencil bands (form 5; 256 of
 // 1080p 0.24 + 0.18 ms against 0.28 + 0.36 for form 2's anchors + searched bands, which took this place before)
+// Form 6 (one two-wave register sweep per frame) replaces form 5 there when a bounding box's span fits 64 lanes x 32 columns,
+// W <= 2048 (H, W >= 16 like form 5): 256 of 1080p 0.229 ms against 0.235 + 0.140 for seed pairs + bands, and one workgroup per CU
+// instead of 32 k workgroups beside the side chain (profiles/NOTES_dt_sweep.md).  4K keeps form 5.
 int dt_algo(const lg_ctx* h, int n, int H, int W) {
-    if (h->opt_dt_algo == 5 && (H < 16 || W < 16)) return 1;   // (form 5's seed rows need the room of sixteen rows and columns)
+    const bool sweep_ok = W <= 2048 && H >= 16 && W >= 16;
+    if (h->opt_dt_algo == 6 && sweep_ok) return 6;
+    if (h->opt_dt_algo >= 5 && (H < 16 || W < 16)) return 1;   // (form 5's seed rows need the room of sixteen rows and columns)
+    if (h->opt_dt_algo == 6) return 5;   // (wider than 2048 columns)
     if (h->opt_dt_algo) return h->opt_dt_algo;
     if ((long long)n * H * W <= 64ll * 1080 * 1920) return 1;
+    if (sweep_ok) return 6;   // (profiles/NOTES_dt_sweep.md)
     return (H < 16 || W < 16) ? 2 : 5;   // seed pairs + stencil bands instead of anchors + searched bands (profiles/NOTES_dt_bands.md)
 }
 
@@ -770,7 +786,9 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
         // long as the sweeps themselves -- measured slower at 256 frames (9.76-9.94 vs 9.56-9.77 ms per step, three alternating runs;
         // again with form 5 of the search, whose chain is the shorter one: 2.196, 2.199 vs 2.135, 2.162 ms, NOTES_dt_bands; and
         // with the pruned border search and the two-level hull test, which make the side chain the shorter one again, 0.34 against
-        // 0.45 ms: 2.074, 2.093 vs 2.044 .. 2.061 ms, NOTES_side_chain)
+        // 0.45 ms: 2.074, 2.093 vs 2.044 .. 2.061 ms, NOTES_side_chain; and with form 6 of the search, one workgroup per CU: 2.070,
+        // 2.047, 2.018 vs 2.004, 2.026, 2.011 ms -- the stem bits' dilation and the sweep share the vector ALUs, both take longer,
+        // NOTES_dt_sweep)
         // Small batches are a chain of latencies, not of throughput: orientation (0.13 ms for one frame; 0.10 since the two-level
         // hull test), border maxima (0.08; 0.035 since the pruned search) and stem bits (0.01) one behind the other on the side
         // stream were the longest chain between the bit rows and the plane kernel of a single-frame call (0.22 ms; the row search
@@ -811,6 +829,7 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
     // the other frames (and the d_out sweeps of the few frames that need them): throughput-bound work on every CU next to
     // latency-bound work on one workgroup per frame.  Inside the sub-batch pipeline (whose stages own the side streams): in line.
     hipStream_t ss = (s == h->s_dt[0] || s == h->s_dt[1]) ? s : h->s_dt[1];
+    h->last_dt_algo = 0;
     if (h->opt_dt_search) {
         if (ss != s) LG_HIP(h, hipStreamWaitEvent(ss, h->ev_prep, 0));
         {
@@ -818,16 +837,17 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
             lg_launch_hrun(h->bits + off * words, h->tmp + 2 * off * px, h->win + off, n, pl.H, pl.W, pl.WW, ss);
         }
         const int algo = dt_algo(h, n, pl.H, pl.W);
+        h->last_dt_algo = algo;
         auto launch = [&](int phase) {
             return lg_launch_dtsearch(phase, algo, h->bits + off * words, h->tmp + 2 * off * px, pl.maps[LG_MAP_DISTANCE] + off * px,
                                       h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, pl.WW, ss, h->opt_dt_band_p,
                                       h->opt_dt_band_e);
         };
         {
-            ProfScope ps(h, "dt_search", ss);   // the one-level search, or the anchor rows
+            ProfScope ps(h, "dt_search", ss);   // the one-level search, the anchor rows, or the whole box by the register sweep
             launch(0);
         }
-        if (algo != 1) {
+        if (algo != 1 && algo != 6) {
             ProfScope ps(h, "dt_band", ss);     // the rows between the anchors
             for (int phase = 1; launch(phase) > 0; phase++) {}
         }

@@ -1349,6 +1349,43 @@ __global__ __launch_bounds__(256) void lg_dtlevel_kernel(const unsigned long lon
 // registers: no LDS, no barrier, nothing waits for another wave.  A stencil step reaches two columns sideways, so what a wave
 // computes is exact 2 (P - 2) columns inside its ends: neighbouring waves overlap by that much on either side and store only
 // their centre.  Rows and columns outside the window are off the leaf (d = h = 0) inside the image and "no path" outside it.
+// The row step itself, lane = E consecutive columns (lg_dtband_kernel, lg_dtsweep_kernel): p1 = the row one step back (columns
+// -2 .. E + 1 of the lane), p2 = the one before (-1 .. E); the halo comes from the neighbouring lanes by wave shifts.  fl: what
+// lane 0 sees in the columns left of its own, fr0 / fr1: what lane 63 sees in the two columns right of its own.
+template <int E>
+struct LgRowStep {
+    uint32_t p1[E + 4], p2[E + 2];
+    __device__ __forceinline__ void set_p1(const uint32_t* v, uint32_t fl, uint32_t fr0, uint32_t fr1) {
+        p1[0] = (uint32_t)lg_wave_shr1((int)fl, (int)v[E - 2]);
+        p1[1] = (uint32_t)lg_wave_shr1((int)fl, (int)v[E - 1]);
+#pragma unroll
+        for (int k = 0; k < E; k++) p1[2 + k] = v[k];
+        p1[E + 2] = (uint32_t)lg_wave_shl1((int)fr0, (int)v[0]);
+        p1[E + 3] = (uint32_t)lg_wave_shl1((int)fr1, (int)v[1]);
+    }
+    __device__ __forceinline__ void set_p2(const uint32_t* v, uint32_t fl, uint32_t fr0) {
+        p2[0] = (uint32_t)lg_wave_shr1((int)fl, (int)v[E - 1]);
+#pragma unroll
+        for (int k = 0; k < E; k++) p2[1 + k] = v[k];
+        p2[E + 1] = (uint32_t)lg_wave_shl1((int)fr0, (int)v[0]);
+    }
+    // one row of the recurrence from A h of the row (two columns per register, uint16), then the row registers move on
+    __device__ __forceinline__ void step(const uint32_t* hpi, uint32_t* v, uint32_t fl, uint32_t fr0, uint32_t fr1) {
+#pragma unroll
+        for (int k = 0; k < E; k++) {
+            const uint32_t ah = (k & 1) ? (hpi[k >> 1] & 0xFFFF0000u) : (hpi[k >> 1] << 16);
+            // equal weights are grouped before they are added: min(x + w, y + w) == min(x, y) + w (values < 2^31)
+            const uint32_t mc = min(min(p2[k], p2[k + 2]), min(p1[k], p1[k + 4])) + LG_C5;
+            const uint32_t mb = min(p1[k + 1], p1[k + 3]) + LG_B5;
+            const uint32_t ma = p1[k + 2] + LG_A5;
+            v[k] = min(min(mc, mb), min(ma, ah));
+        }
+#pragma unroll
+        for (int q = 0; q < E + 2; q++) p2[q] = p1[q + 1];
+        set_p1(v, fl, fr0, fr1);
+    }
+};
+
 template <int P, int E, bool VEC>   // VEC: W % E == 0, a lane's E columns are one aligned load / store
 __global__ __launch_bounds__(256) void lg_dtband_kernel(const unsigned long long* __restrict__ bits,
                                                         const LgWin* __restrict__ wins, uint32_t* __restrict__ tmp,
@@ -1472,39 +1509,15 @@ __global__ __launch_bounds__(256) void lg_dtband_kernel(const unsigned long long
                 }
             }
         };
-        uint32_t p1[E + 4], p2[E + 2];   // the row one step back (columns -2 .. E + 1 of the lane) and the one before (-1 .. E)
-        auto set_p1 = [&](const uint32_t* v) {
-            p1[0] = (uint32_t)lg_wave_shr1((int)LG_INF, (int)v[E - 2]);
-            p1[1] = (uint32_t)lg_wave_shr1((int)LG_INF, (int)v[E - 1]);
-#pragma unroll
-            for (int k = 0; k < E; k++) p1[2 + k] = v[k];
-            p1[E + 2] = (uint32_t)lg_wave_shl1((int)LG_INF, (int)v[0]);
-            p1[E + 3] = (uint32_t)lg_wave_shl1((int)LG_INF, (int)v[1]);
-        };
+        LgRowStep<E> rs;   // (beyond the wave's ends: "no path" -- the halo absorbs it)
         auto start = [&](int y2, int y1) {   // p2 / p1 from the seed rows two steps / one step back
             uint32_t v[E];
             load_seed(y2, v);
-            p2[0] = (uint32_t)lg_wave_shr1((int)LG_INF, (int)v[E - 1]);
-#pragma unroll
-            for (int k = 0; k < E; k++) p2[1 + k] = v[k];
-            p2[E + 1] = (uint32_t)lg_wave_shl1((int)LG_INF, (int)v[0]);
+            rs.set_p2(v, LG_INF, LG_INF);
             load_seed(y1, v);
-            set_p1(v);
+            rs.set_p1(v, LG_INF, LG_INF, LG_INF);
         };
-        auto step = [&](const uint32_t* hpi, uint32_t* v) {   // one row of the recurrence, then the row registers move on
-#pragma unroll
-            for (int k = 0; k < E; k++) {
-                const uint32_t ah = (k & 1) ? (hpi[k >> 1] & 0xFFFF0000u) : (hpi[k >> 1] << 16);
-                // equal weights are grouped before they are added: min(x + w, y + w) == min(x, y) + w (values < 2^31)
-                const uint32_t mc = min(min(p2[k], p2[k + 2]), min(p1[k], p1[k + 4])) + LG_C5;
-                const uint32_t mb = min(p1[k + 1], p1[k + 3]) + LG_B5;
-                const uint32_t ma = p1[k + 2] + LG_A5;
-                v[k] = min(min(mc, mb), min(ma, ah));
-            }
-#pragma unroll
-            for (int q = 0; q < E + 2; q++) p2[q] = p1[q + 1];
-            set_p1(v);
-        };
+        auto step = [&](const uint32_t* hpi, uint32_t* v) { rs.step(hpi, v, LG_INF, LG_INF, LG_INF); };
         uint32_t res[N][E];
         start(s - 2, s - 1);
 #pragma unroll
@@ -1521,6 +1534,187 @@ __global__ __launch_bounds__(256) void lg_dtband_kernel(const unsigned long long
     }
     mx = lg_wave_max_u32(mx);
     if (lane == 0 && mx) atomicMax(&maxfix[frame * LG_MF + 0], mx);
+}
+
+// ---- form 6: the same row step over the whole bounding box, one workgroup per frame and no seed rows at all.  Wave 0 runs U
+// downwards from the box's first row, wave 1 runs D upwards from its last row, both over the span of 64 E columns that holds the
+// box (E = 4, 8, 16 or 32: W <= 2048), lane = E columns in registers.  Rows above / below the box and columns beside the span
+// are off the leaf: 0 inside the image, "no path" outside it.  The waves meet at mid-height: up to there each stores its own
+// exact 16.16 row, one workgroup barrier follows, and past it each takes the minimum with the row the other stored and writes
+// the float.  The rows are parked in distance_map itself, in the very words the final floats replace (every word is read and
+// then rewritten by the same lane): the seed-row area of `tmp` holds H / 2 rows and a box may be as high as the frame.  Waves
+// 2 and 3 meanwhile write the 0 of the window's cells outside the box's rows and the span.  h rows do not depend on each other:
+// PF rows of loads stay in flight (their out-of-range columns are replaced when a row is used, not when it is loaded).
+template <int E, bool VEC>   // VEC: W % 4 == 0, four columns are one aligned load / store
+__device__ __forceinline__ void lg_dtsweep_body(const LgWin& w, const uint16_t* __restrict__ hd, uint32_t* du,
+                                                uint32_t* __restrict__ mxp, int H, int W, int wxe, int sx0) {
+    constexpr int EH = E / 2, NG = E / 4, NR = VEC ? EH : E, PF = E <= 8 ? 8 : 64 / E;
+    constexpr uint32_t HOUT = LG_HCAP;   // h outside the image: an upper bound that beats nothing
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int xl = sx0 + E * lane, xe = sx0 + 64 * E;   // the lane's first column, the span's end
+    const int hx0 = (w.bx0 >> 6) << 6, hx1 = min(W, ((w.bx1 >> 6) + 1) << 6);   // columns lg_hrun_kernel wrote
+    const int n = w.by1 - w.by0 + 1, na = n / 2;   // U is stored on rows [by0, by0 + na), D on the rows from there on
+    const int dir = wave == 0 ? 1 : -1, ys = wave == 0 ? w.by0 : w.by1;
+    const int cnt_a = wave == 0 ? na : n - na, cnt_b = n - cnt_a;
+    // beside the span (sx0 % 4 == 0: the two columns left of it lie both in the image or both outside)
+    const uint32_t fl = sx0 > 0 ? 0u : LG_INF, fr0 = xe < W ? 0u : LG_INF, fr1 = xe + 1 < W ? 0u : LG_INF;
+    LgRowStep<E> rs;
+    uint32_t mx = 0;
+    auto load_h = [&](int y, uint32_t* raw) {   // raw words of row y: fix_h makes them h
+        const uint16_t* row = hd + (size_t)y * W;
+        if (VEC) {
+#pragma unroll
+            for (int g = 0; g < NG; g++) {
+                const int xg = xl + 4 * g;
+                const uint2 v = *reinterpret_cast<const uint2*>(row + ((xg >= hx0 && xg < hx1) ? xg : hx0));
+                raw[2 * g] = v.x; raw[2 * g + 1] = v.y;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < E; k++) {
+                const int c = xl + k;
+                raw[k] = row[(c >= hx0 && c < hx1) ? c : hx0];
+            }
+        }
+    };
+    auto fix_h = [&](const uint32_t* raw, uint32_t* hp) {   // columns lg_hrun_kernel did not write: off the leaf, or outside the image
+        if (VEC) {
+#pragma unroll
+            for (int g = 0; g < NG; g++) {
+                const int xg = xl + 4 * g;
+                const bool ld = xg >= hx0 && xg < hx1;
+                const uint32_t f = xg < W ? 0u : (HOUT | (HOUT << 16));
+                hp[2 * g] = ld ? raw[2 * g] : f; hp[2 * g + 1] = ld ? raw[2 * g + 1] : f;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < EH; q++) {
+                uint32_t hv[2];
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    const int c = xl + 2 * q + k;
+                    hv[k] = (c >= hx0 && c < hx1) ? raw[2 * q + k] : (c < W ? 0u : HOUT);
+                }
+                hp[q] = hv[0] | (hv[1] << 16);
+            }
+        }
+    };
+    // a parked row or a final one: the span's columns inside the window (wxe <= W; VEC: wxe % 4 == 0)
+    auto load_row = [&](int y, uint32_t* raw) {   // columns that are not stored are not used either
+        const uint32_t* row = du + (size_t)y * W;
+        if (VEC) {
+#pragma unroll
+            for (int g = 0; g < NG; g++) {
+                const int xg = xl + 4 * g;
+                const uint4 v = *reinterpret_cast<const uint4*>(row + (xg < wxe ? xg : sx0));
+                raw[4 * g] = v.x; raw[4 * g + 1] = v.y; raw[4 * g + 2] = v.z; raw[4 * g + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < E; k++) raw[k] = row[xl + k < wxe ? xl + k : sx0];
+        }
+    };
+    auto store_row = [&](int y, const uint32_t* v) {
+        uint32_t* row = du + (size_t)y * W;
+        if (VEC) {
+#pragma unroll
+            for (int g = 0; g < NG; g++)
+                if (xl + 4 * g < wxe) *reinterpret_cast<uint4*>(row + xl + 4 * g) = make_uint4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < E; k++)
+                if (xl + k < wxe) row[xl + k] = v[k];
+        }
+    };
+    auto edge_row = [&](int y, uint32_t* v) {   // a row beside the box
+        const bool yin = y >= 0 && y < H;
+#pragma unroll
+        for (int k = 0; k < E; k++) v[k] = (yin && xl + k < W) ? 0u : LG_INF;
+    };
+    // cnt rows from row y0 on in the wave's direction; MEET: past mid-height
+    auto run = [&](auto meet, int y0, int cnt) {
+        constexpr bool MEET = decltype(meet)::value;
+        uint32_t hq[PF][NR], oq[MEET ? PF : 1][MEET ? E : 1];
+#pragma unroll
+        for (int q = 0; q < PF; q++)
+            if (q < cnt) {
+                load_h(y0 + dir * q, hq[q]);
+                if (MEET) load_row(y0 + dir * q, oq[q]);
+            }
+        for (int i0 = 0; i0 < cnt; i0 += PF) {
+#pragma unroll
+            for (int q = 0; q < PF; q++) {
+                const int i = i0 + q;
+                if (i < cnt) {   // (wave-uniform)
+                    const int y = y0 + dir * i;
+                    uint32_t hp[EH], v[E];
+                    fix_h(hq[q], hp);
+                    rs.step(hp, v, fl, fr0, fr1);
+                    if (MEET) {
+                        uint32_t o[E];
+#pragma unroll
+                        for (int k = 0; k < E; k++) {
+                            const uint32_t d = min(v[k], oq[q][k]);
+                            if (xl + k < wxe) mx = max(mx, d);
+                            o[k] = __float_as_uint((float)d * (1.0f / 65536.0f));
+                        }
+                        store_row(y, o);
+                    } else {
+                        store_row(y, v);
+                    }
+                    if (i + PF < cnt) {
+                        load_h(y + dir * PF, hq[q]);
+                        if (MEET) load_row(y + dir * PF, oq[q]);
+                    }
+                }
+            }
+        }
+    };
+    if (wave < 2) {
+        uint32_t v[E];
+        const bool in2 = ys - 2 * dir >= 0 && ys - 2 * dir < H, in1 = ys - dir >= 0 && ys - dir < H;
+        edge_row(ys - 2 * dir, v);
+        rs.set_p2(v, in2 ? fl : LG_INF, in2 ? fr0 : LG_INF);
+        edge_row(ys - dir, v);
+        rs.set_p1(v, in1 ? fl : LG_INF, in1 ? fr0 : LG_INF, in1 ? fr1 : LG_INF);
+        run(std::integral_constant<bool, false>(), ys, cnt_a);
+    } else {
+        // the rest of the window is off the leaf
+        for (int y = w.wy0 + (wave - 2); y < w.wy1; y += 2) {
+            const bool box_row = y >= w.by0 && y <= w.by1;
+            uint32_t* row = du + (size_t)y * W;
+            if (VEC) {
+                for (int x = w.wx0 + 4 * lane; x < wxe; x += 256)
+                    if (!(box_row && x >= sx0 && x < xe)) *reinterpret_cast<uint4*>(row + x) = make_uint4(0u, 0u, 0u, 0u);
+            } else {
+                for (int x = w.wx0 + lane; x < wxe; x += 64)
+                    if (!(box_row && x >= sx0 && x < xe)) row[x] = 0u;
+            }
+        }
+    }
+    __syncthreads();   // (workgroup-scope release / acquire: the parked rows of the other wave)
+    if (wave < 2) {
+        run(std::integral_constant<bool, true>(), ys + dir * cnt_a, cnt_b);
+        mx = lg_wave_max_u32(mx);
+        if (lane == 0 && mx) atomicMax(mxp, mx);
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void lg_dtsweep_kernel(const LgWin* __restrict__ wins, const uint32_t* __restrict__ tmp,
+                                                         float* dist_out, uint32_t* __restrict__ maxfix, int H, int W, int wc) {
+    const int frame = (int)blockIdx.x;   // (frame % 8 is the XCD whose L2 lg_hrun_kernel wrote the frame's run distances through)
+    const LgWin w = wins[frame];
+    if (!w.search_in) return;
+    const int wxe = min(W, w.wx0 + w.nw * wc);
+    const int sx0 = w.bx0 & ~3, span = w.bx1 - sx0 + 1;
+    const uint16_t* hd = reinterpret_cast<const uint16_t*>(tmp + (size_t)frame * 2 * H * W);
+    uint32_t* du = reinterpret_cast<uint32_t*>(dist_out + (size_t)frame * H * W);
+    uint32_t* mxp = maxfix + frame * LG_MF;
+    if (span <= 256) lg_dtsweep_body<4, VEC>(w, hd, du, mxp, H, W, wxe, sx0);
+    else if (span <= 512) lg_dtsweep_body<8, VEC>(w, hd, du, mxp, H, W, wxe, sx0);
+    else if (span <= 1024) lg_dtsweep_body<16, VEC>(w, hd, du, mxp, H, W, wxe, sx0);
+    else lg_dtsweep_body<32, VEC>(w, hd, du, mxp, H, W, wxe, sx0);
 }
 
 static int lg_search_groups(int B, int per_batch, int lo, int hi) {
@@ -1548,6 +1742,7 @@ void lg_launch_hrun(const unsigned long long* bits, uint32_t* tmp, const LgWin* 
 // algo 5: pairs of adjacent rows every band_p rows (12, 16, 24 or 32) by the bounded search (phase 0), then the rows between two
 // pairs by the chamfer stencil run down and up in registers, band_e (2 or 4) columns per lane (phase 1: lg_dtband_kernel).
 // Needs H, W >= 16 (the seed rows share the run distances' workspace).
+// algo 6 (W <= 2048): the whole bounding box by that stencil, one workgroup per frame (phase 0 only: lg_dtsweep_kernel).
 int lg_launch_dtsearch(int phase, int algo, const unsigned long long* bits, uint32_t* tmp, float* dist_out, uint32_t* maxfix,
                        const LgWin* win, int B, int H, int W, int WW, hipStream_t s, int band_p, int band_e) {
     static const int g_env = getenv("LG_DT_SEARCH_G") ? atoi(getenv("LG_DT_SEARCH_G")) : 0;
@@ -1559,6 +1754,12 @@ int lg_launch_dtsearch(int phase, int algo, const unsigned long long* bits, uint
         if (phase) return 0;
         const int G = g_env > 0 ? g_env : lg_search_groups(B, 8192, 8, 256);
         LG_LAUNCH_SEARCH(lg_dtsearch_kernel, G);
+        return 1;
+    }
+    if (algo == 6) {   // one two-wave register sweep per frame (W <= 2048: the span of any bounding box fits 64 lanes x 32 columns)
+        if (phase) return 0;
+        if (W % 4 == 0) hipLaunchKernelGGL(lg_dtsweep_kernel<true>, dim3(B), dim3(256), 0, s, win, tmp, dist_out, maxfix, H, W, wc);
+        else hipLaunchKernelGGL(lg_dtsweep_kernel<false>, dim3(B), dim3(256), 0, s, win, tmp, dist_out, maxfix, H, W, wc);
         return 1;
     }
     if (algo == 5) {   // seed pairs every band_p rows by the bounded search, then the rows between them by stencil sweeps

@@ -252,6 +252,16 @@ class GraspPointSelector:
             raise RuntimeError(lib.lg_last_error(self._h).decode())
         return bool(form[0]), bool(form[1])
 
+    def dt_search_form(self):
+        """Inspection: the form of the row search the last call queued for its searched frames (dt_form(i)[0]), in
+        LG_DT_SEARCH_ALGO's numbering: 1, 2 (3, 4 when forced), 5, or 6 = one register sweep per frame; 0: no search is queued."""
+        import ctypes as C
+        algo = C.c_int32()
+        rc = lib.lg_debug_dt_search_form(self._h, C.byref(algo))
+        if rc != 0:
+            raise RuntimeError(lib.lg_last_error(self._h).decode())
+        return int(algo.value)
+
     def cnn_scored(self):
         """Inspection: how many patches the last select_grasp_point(s) / select_grasp_candidates call put through the CNN --
         the candidates that could still beat candidate 0 (lg_cnn_candidate_cannot_win), or every one (B * top_k) for the
