@@ -365,6 +365,14 @@ int lg_debug_dt_form(lg_handle h, int frame, int32_t form[2]);
    2 anchors + searched bands, 3 / 4 the same with four / one anchor rows per lane when forced, 5 seed pairs + stencil bands,
    6 one register sweep per frame); 0: the handle queues no search. */
 int lg_debug_dt_search_form(lg_handle h, int32_t* algo);
+/* *n = frames of the last lg_score_maps / lg_select_grasp* call that the device orientation kernel handed back (more runs than
+   its scratch holds, LG_ORIENT_CAP) and the host threads analysed; 0 where the host analyses every frame anyway
+   (LG_HOST_ORIENT).
+   The small results of a call -- every frame's orientation and status word, the near-tile offsets, the result rows -- are
+   written by the kernels straight into the handle's pinned host buffers through their device aliases and read by the host
+   behind the events it waits for anyway; LG_DIRECT_HOST=0 at lg_create (or an allocation without an alias): they come back by
+   copies on the streams instead.  Same results either way. */
+int lg_debug_orient_redo(lg_handle h, int32_t* n);
 /* The near tiles of a frame on the host (no device, no handle), the code the device runs: the tiles (64 x 16 pixels) of the
    score-plane kernel whose look at the mask can meet the mask's bounding box [bx0, bx1] x [by0, by1] (bx1 < bx0: empty) in an
    H x W frame, halo = gaussian_size / 2 + 1.  They form a rectangle of the tile grid: rect = {tx_lo, tx_hi, ty_lo, ty_hi},
@@ -372,6 +380,25 @@ int lg_debug_dt_search_form(lg_handle h, int32_t* algo);
    other tile is constant whatever the mask.  In sparse mode lg_select_grasp* launches the plane kernel on the near tiles only
    (LG_FINAL_NEAR=0 at lg_create: on every tile, as lg_score_maps does). */
 int lg_near_tile_rect(int bx0, int bx1, int by0, int by1, int H, int W, int halo, int32_t rect[4]);
+/* The stem words of one frame on the host (no device, no handle), the code the device runs: out[H][WW] = the bit rows of
+   dilate(mask & rows [bottom_start, H), ellipse k) & mask for the mask bit rows bits[H][WW] (WW = (W + 63) / 64, bits past W
+   zero), 1 <= k <= 64.  The dilation runs as two chains of nested spans from the ellipse's widest row to its end rows: the
+   accumulator is dilated by the difference between one row's span and the next narrower one and takes that row; only the words
+   of the mask's bounding box, in rows from which the ellipse reaches the bottom region, do arithmetic, every other word is
+   written as zero.  LG_STEM_ALGO=0 at lg_create: the device dilates every row's span from scratch instead (the form spans that
+   are not nested would take).  Returns 1 (the chains ran), LG_ERR_INVALID for a bad argument.
+   lg_stem_words_host_spans: the same for hand-made spans -- n rows, anchor row / column `anchor`, row i covers the columns
+   [lo[i], hi[i]] relative to the anchor (lo > hi: empty; entries in [-32, 32], at most 63 columns) -- algo 1: the chains when the
+   spans are nested, else the per-row loop; algo 0: the per-row loop.  Returns 1 when the chains ran, 0 for the per-row loop.
+   lg_stem_plan: the chains of an ellipse (1 <= k <= 64; n, anchor, lo, hi ignored) or of hand-made spans (k = 0).  Returns 1 when
+   the spans are nested (every row non-empty and inside the next row towards the widest one, 0 inside both end rows), else 0;
+   *i0 = the widest row, span_lo / span_hi = the spans, dlo[i] / dhi[i] (i != i0) = the ends of the chain's previous row minus
+   those of row i (<= 0 / >= 0 when nested).  Output pointers may be null. */
+int lg_stem_words_host(const uint64_t* bits, int H, int W, int WW, int bottom_start, int k, uint64_t* out);
+int lg_stem_words_host_spans(const uint64_t* bits, int H, int W, int WW, int bottom_start, int n, int anchor, const int8_t* lo,
+                             const int8_t* hi, int algo, uint64_t* out);
+int lg_stem_plan(int k, int n, int anchor, const int8_t* lo, const int8_t* hi, int32_t* i0, int8_t span_lo[64], int8_t span_hi[64],
+                 int8_t dlo[64], int8_t dhi[64]);
 /* A frame's sweep window on the host (no device, no handle), the code the device runs.  The bit-row pass reduces a mask to five
    words that all start from zero: box = {max of W - 1 - x, max of x, max of H - 1 - y, max of y, number} over the set pixels
    (the two minima are held as maxima; number 0: empty mask, whatever the other four say).  out = {wx0, wx1, wy0, wy1 (the window:

@@ -120,8 +120,14 @@ SYMBOLS = {
     "lg_debug_dt_max": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "lg_format_grasp_results": (C.c_int, [_VP, C.c_int, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "lg_debug_dt_form": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int32)]),
+    "lg_debug_orient_redo": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "lg_debug_dt_search_form": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "lg_near_tile_rect": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "lg_stem_words_host": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
+    "lg_stem_words_host_spans": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int8),
+                                           C.POINTER(C.c_int8), C.c_int, _VP]),
+    "lg_stem_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int8), C.POINTER(C.c_int8), C.POINTER(C.c_int32),
+                               C.POINTER(C.c_int8), C.POINTER(C.c_int8), C.POINTER(C.c_int8), C.POINTER(C.c_int8)]),
     "lg_window_from_box": (C.c_int, [C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "lg_border_line_max": (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "lg_debug_near_tiles":(C.c_int, [_VP, C.POINTER(C.c_int32), C.c_int]),

@@ -38,7 +38,7 @@ struct LgProfSlot {
 
 // list entries per workgroup of the near launch (lg_launch_final; LG_FINAL_NEAR=n overrides).  256 frames of 1080p, plane kernel
 // alone: 1 / 2 / 4 / 8 entries 0.275 / 0.273 / 0.305 / 0.328 ms (profiles/NOTES_near_tiles.md).  The launch applies at every batch
-// size: the enumeration kernel and its copy in front of the orientation kernel did not lengthen a call of 1 or 32 frames.
+// size: the enumeration kernel (then in front of the orientation kernel, with a copy) did not lengthen a call of 1 or 32 frames.
 #ifndef LG_FINAL_NEAR_TPW
 #define LG_FINAL_NEAR_TPW 1
 #endif
@@ -58,9 +58,17 @@ struct lg_ctx {
     unsigned long long *bits = nullptr, *stem = nullptr, *tilekeys = nullptr;
     uint8_t* tile_state = nullptr;   // [B][tiles]: which tiles' planes lg_final_kernel wrote (sparse planes, Plan::sparse)
     // near launch of lg_final_kernel (sparse planes): first list entry of every frame's near tiles, [B + 1], written by
-    // lg_near_tiles_kernel on the copy stream, and its pinned copy (read by enq_final, after the event the host waits for anyway)
+    // lg_near_tiles_kernel on the caller's stream, and its pinned copy (read by enq_final behind ev_near)
     int32_t* near_off = nullptr;
     int32_t* near_off_host = nullptr;
+    hipEvent_t ev_near = nullptr;    // behind lg_near_tiles_kernel (and the copy of its offsets, where one is made) on the caller's stream
+    // device-side aliases of the small pinned results (LG_DIRECT_HOST=0 or an unmapped allocation: null, copies as before):
+    // lg_near_tiles_kernel, lg_orient_kernel and lg_finish_kernel write near_off_host, fp_host (+ the status words) and
+    // res_host themselves, 22 KB per 256 frames, and the host reads them behind the events it waits for anyway
+    int32_t* near_off_host_dev = nullptr;
+    LgFrameParams* fp_host_dev = nullptr;
+    lg_grasp_result* res_host_dev = nullptr;
+    int last_redo = 0;               // lg_debug_orient_redo: frames the last plane call analysed on the host after the orientation kernel handed them back
     int last_near_B = 0;             // lg_debug_near_tiles: frames of the last lg_select_grasp* call if it took the near launch, else 0
     uint32_t* maxfix = nullptr;
     uint8_t* mask_ws = nullptr;      // lg_select_grasp_labels: the 0 / 1 mask it derives from the labels (grown on demand)
@@ -127,6 +135,8 @@ struct lg_ctx {
     bool opt_nt_stores = false;  // LG_NT_STORES: non-temporal plane stores (measured slower)
     int opt_side_tail = 1;         // LG_SIDE_TAIL=0: frame-border maxima + stem bits after the sweeps on the caller's stream (round 1); 1: on the
                                    // side stream behind the orientation kernel; 2: on a third stream
+    int opt_stem_algo = 1;         // LG_STEM_ALGO=0: stem bits by the per-row kernel (A/B, tests); 1: two chains of nested spans
+    bool opt_direct_host = true;   // LG_DIRECT_HOST=0: the small results come back by hipMemcpyAsync (A/B, tests)
     bool export_pending = false;   // this call's bit-row export has not been queued yet (enq_export)
     std::string orient_note;       // why the device-side orientation scratch could not be set up (host analysis is used then)
     std::atomic<bool> busy{false}; // one call in flight per handle (SURVEY 8b "Threading"): a concurrent second call gets LG_ERR_BUSY
@@ -234,6 +244,7 @@ void free_ws(lg_ctx* h) {
     auto HF = [](void* p) { if (p) hipHostFree(p); };
     HF(h->fp_host); HF(h->bits_host); HF(h->win_host); HF(h->res_host); HF(h->near_off_host);
     h->near_off_host = nullptr;
+    h->near_off_host_dev = nullptr; h->fp_host_dev = nullptr; h->res_host_dev = nullptr;
     F(h->res_dev);
     h->tmp = nullptr; h->bits = h->stem = h->tilekeys = nullptr; h->tile_state = nullptr; h->maxfix = nullptr; h->win = nullptr; h->fp_dev = nullptr;
     h->ws_valid = nullptr; h->cand_xy = h->cand_n = nullptr; h->cand_info = h->patches = h->logits = nullptr;
@@ -281,6 +292,12 @@ int ensure_ws(lg_ctx* h, int B, int H, int W, int K) {
     LG_HIP(h, dev_alloc(&h->surv_count, (size_t)nB));
     LG_HIP(h, dev_alloc(&h->res_dev, (size_t)nB));
     LG_HIP(h, hipHostMalloc((void**)&h->res_host, sizeof(lg_grasp_result) * nB));
+    if (h->opt_direct_host) {
+        if (hipHostGetDevicePointer((void**)&h->near_off_host_dev, h->near_off_host, 0) != hipSuccess) h->near_off_host_dev = nullptr;
+        if (hipHostGetDevicePointer((void**)&h->fp_host_dev, h->fp_host, 0) != hipSuccess) h->fp_host_dev = nullptr;
+        if (hipHostGetDevicePointer((void**)&h->res_host_dev, h->res_host, 0) != hipSuccess) h->res_host_dev = nullptr;
+        (void)hipGetLastError();   // (a refused alias only means the copy is made)
+    }
     if (!h->opt_host_orient && H <= 16384 && W <= 8192) {
         // no device-side scratch (allocation, or the LDS request on a part with less of it): the host contour analysis of
         // every frame is a complete path of its own -- scoring goes on, the reason stays readable in orient_note
@@ -379,7 +396,8 @@ int lg_create(int device, lg_handle* out) {
         hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_orient, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_side, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_search, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&h->ev_search, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&h->ev_near, hipEventDisableTiming) != hipSuccess) {
         g_create_err = std::string("lg_create: stream / event creation -> ") + hipGetErrorString(hipGetLastError());
         delete h;
         return LG_ERR_HIP;
@@ -419,6 +437,8 @@ int lg_create(int device, lg_handle* out) {
     if (const char* e = getenv("LG_DT_BAND_P")) { const int p = atoi(e); if (p == 12 || p == 16 || p == 24 || p == 32) h->opt_dt_band_p = p; }
     if (const char* e = getenv("LG_DT_BAND_E")) { const int v = atoi(e); if (v == 2 || v == 4) h->opt_dt_band_e = v; }
     if (const char* e = getenv("LG_SIDE_TAIL")) h->opt_side_tail = std::max(0, std::min(2, atoi(e)));
+    if (const char* e = getenv("LG_STEM_ALGO")) h->opt_stem_algo = atoi(e) != 0;
+    if (const char* e = getenv("LG_DIRECT_HOST")) h->opt_direct_host = atoi(e) != 0;
     if (const char* e = getenv("LG_CNN_CUS")) {
         const int n = atoi(e);
         int total = 0;
@@ -463,6 +483,7 @@ int lg_destroy(lg_handle h) {
     if (h->ev_orient) hipEventDestroy(h->ev_orient);
     if (h->ev_side) hipEventDestroy(h->ev_side);
     if (h->ev_search) hipEventDestroy(h->ev_search);
+    if (h->ev_near) hipEventDestroy(h->ev_near);
     for (auto& p : h->prof)
         for (auto e : p.ev) hipEventDestroy(e);
     for (auto e : h->ev_pool) hipEventDestroy(e);
@@ -630,6 +651,97 @@ int lg_near_tile_rect(int bx0, int bx1, int by0, int by1, int H, int W, int halo
     return n;
 }
 
+int lg_stem_plan(int k, int n, int anchor, const int8_t* lo, const int8_t* hi, int32_t* i0, int8_t span_lo[64], int8_t span_hi[64],
+                 int8_t dlo[64], int8_t dhi[64]) {
+    LgSeSpans se;
+    if (k >= 1 && k <= 64) {
+        lg_make_se_spans(k, &se);
+    } else {
+        if (k != 0 || !lo || !hi || n < 1 || n > 64 || anchor < 0 || anchor >= n) return LG_ERR_INVALID;
+        memset(&se, 0, sizeof(se));
+        se.n = n; se.anchor = anchor;
+        for (int i = 0; i < n; i++) {
+            if (lo[i] < -32 || lo[i] > 32 || hi[i] < -32 || hi[i] > 32 || hi[i] - lo[i] > 62) return LG_ERR_INVALID;
+            se.lo[i] = lo[i]; se.hi[i] = hi[i];
+        }
+    }
+    LgStemPlan sp;
+    lg_make_stem_plan(se, &sp);
+    if (i0) *i0 = sp.i0;
+    for (int i = 0; i < 64; i++) {
+        if (span_lo) span_lo[i] = i < se.n ? se.lo[i] : 0;
+        if (span_hi) span_hi[i] = i < se.n ? se.hi[i] : 0;
+        if (dlo) dlo[i] = sp.dlo[i];
+        if (dhi) dhi[i] = sp.dhi[i];
+    }
+    return sp.nested;
+}
+
+namespace {
+// a frame's stem words on the host, laid out as the kernels lay them out: the nested-span form on the words of the bounding box
+// (zeros elsewhere), or the per-row form on every word.  Returns 1 when the chains ran, 0 for the per-row loop.
+int stem_words_host(const unsigned long long* bits, int H, int W, int WW, int bottom_start, const LgSeSpans& se, int algo,
+                    unsigned long long* out) {
+    LgStemPlan sp;
+    lg_make_stem_plan(se, &sp);
+    if (!algo || !sp.nested) {
+        for (int y = 0; y < H; y++)
+            for (int w = 0; w < WW; w++) {
+                const unsigned long long self = bits[(size_t)y * WW + w];
+                unsigned long long acc = 0;
+                if (self != 0 && y + (se.n - 1 - se.anchor) >= bottom_start) acc = lg_stem_word_rows(bits, H, WW, bottom_start, y, w, se);
+                out[(size_t)y * WW + w] = acc & self;
+            }
+        return 0;
+    }
+    LgWin wn;
+    memset(&wn, 0, sizeof(wn));
+    wn.bx0 = W; wn.bx1 = -1; wn.by0 = H; wn.by1 = -1;
+    for (int y = 0; y < H; y++)
+        for (int w = 0; w < WW; w++) {
+            const unsigned long long v = bits[(size_t)y * WW + w];
+            if (!v) continue;
+            wn.bx0 = std::min(wn.bx0, 64 * w + __builtin_ctzll(v));
+            wn.bx1 = std::max(wn.bx1, 64 * w + 63 - __builtin_clzll(v));
+            wn.by0 = std::min(wn.by0, y);
+            wn.by1 = y;
+        }
+    const LgStemRect rc = lg_stem_active(wn, H, WW, bottom_start, se.n, se.anchor);
+    const int ya = rc.ya, yb = rc.yb, w0 = rc.w0, w1 = rc.w1;
+    for (int y = 0; y < H; y++)
+        for (int w = 0; w < WW; w++) {
+            const size_t o = (size_t)y * WW + w;
+            if (!(y >= ya && y <= yb && w >= w0 && w <= w1)) { out[o] = 0ull; continue; }
+            const unsigned long long self = bits[o];
+            out[o] = self ? (lg_stem_word_chain(bits, H, WW, bottom_start, y, w, se, sp) & self) : 0ull;
+        }
+    return 1;
+}
+}  // namespace
+
+int lg_stem_words_host(const uint64_t* bits, int H, int W, int WW, int bottom_start, int k, uint64_t* out) {
+    if (!bits || !out || H < 1 || W < 1 || WW != (W + 63) / 64 || bottom_start < 0 || bottom_start > H || k < 1 || k > 64)
+        return LG_ERR_INVALID;
+    LgSeSpans se;
+    lg_make_se_spans(k, &se);
+    return stem_words_host((const unsigned long long*)bits, H, W, WW, bottom_start, se, 1, (unsigned long long*)out);
+}
+
+int lg_stem_words_host_spans(const uint64_t* bits, int H, int W, int WW, int bottom_start, int n, int anchor, const int8_t* lo,
+                             const int8_t* hi, int algo, uint64_t* out) {
+    if (!bits || !out || !lo || !hi || H < 1 || W < 1 || WW != (W + 63) / 64 || bottom_start < 0 || bottom_start > H || n < 1 ||
+        n > 64 || anchor < 0 || anchor >= n)
+        return LG_ERR_INVALID;
+    LgSeSpans se;
+    memset(&se, 0, sizeof(se));
+    se.n = n; se.anchor = anchor;
+    for (int i = 0; i < n; i++) {
+        if (lo[i] < -32 || lo[i] > 32 || hi[i] < -32 || hi[i] > 32 || hi[i] - lo[i] > 62) return LG_ERR_INVALID;
+        se.lo[i] = lo[i]; se.hi[i] = hi[i];
+    }
+    return stem_words_host((const unsigned long long*)bits, H, W, WW, bottom_start, se, algo, (unsigned long long*)out);
+}
+
 int lg_window_from_box(const uint32_t box[5], int H, int W, int search_mode, int32_t out[12]) {
     int nw = 0;
     const int wc = (H >= 1 && W >= 1) ? lg_dt_geometry(W, &nw) : 0;
@@ -656,6 +768,13 @@ int lg_debug_near_tiles(lg_handle h, int32_t* off, int cap) {
     if (h->last_near_B <= 0 || !h->near_off_host) return fail(h, LG_ERR_INVALID, "lg_debug_near_tiles: the last call did not take the near launch");
     if (cap < h->last_near_B + 1) return fail(h, LG_ERR_INVALID, "lg_debug_near_tiles: cap must hold B + 1 entries");
     memcpy(off, h->near_off_host, sizeof(int32_t) * (h->last_near_B + 1));   // (the call that wrote it has been synchronised)
+    return LG_OK;
+}
+
+int lg_debug_orient_redo(lg_handle h, int32_t* n) {
+    if (!h || !n) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    *n = h->last_redo;
     return LG_OK;
 }
 
@@ -734,9 +853,13 @@ int enq_tail(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
         lg_make_se_spans(pl.P.stem_se, &se);
         // bottom[-third:, :] = 1 (:693-694): a frame shorter than the divisor has third == 0, and numpy's [-0:] is every row
         const int third = pl.H / pl.P.stem_bottom_div;
+        // two chains of nested spans on the words of the bounding boxes; spans that are not nested (no ellipse gives any), or
+        // LG_STEM_ALGO=0: the per-row kernel
+        LgStemPlan sp;
+        lg_make_stem_plan(se, &sp);
         ProfScope ps(h, "stem", s);
-        lg_launch_stem_bits(h->bits + off * words, h->stem + off * words, n, pl.H, pl.W, pl.WW,
-                            third ? pl.H - third : 0, se, s);
+        lg_launch_stem_bits(h->bits + off * words, h->stem + off * words, h->win + off, n, pl.H, pl.W, pl.WW,
+                            third ? pl.H - third : 0, se, h->opt_stem_algo ? &sp : nullptr, s);
     }
     return LG_OK;
 }
@@ -761,24 +884,29 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
     LG_HIP(h, hipEventRecord(ev_prep, s));
     LG_HIP(h, hipStreamWaitEvent(h->copy_stream, ev_prep, 0));
     if (pl.near) {   // (one sub-batch: off = 0, n = B)  list offsets of the near tiles + the far tiles' keys and state bytes
-        ProfScope ps(h, "near_tiles", h->copy_stream);
-        lg_launch_near_tiles(h->win, n, pl.H, pl.W, pl.P.gaussian_size / 2 + 1, h->near_off, h->tilekeys, h->tile_state, h->copy_stream);
+        // On the caller's stream, which (the row search runs on a stream of its own) has little to do until the plane kernel and
+        // orders the plane kernel and top-k behind it for free -- not in front of the orientation kernel on the side stream,
+        // whose chain nothing of this feeds.  The host reads near_off_host[n] behind ev_near (enq_final), after ev_orient.
+        ProfScope ps(h, "near_tiles", s);
+        lg_launch_near_tiles(h->win, n, pl.H, pl.W, pl.P.gaussian_size / 2 + 1, h->near_off, h->near_off_host_dev, h->tilekeys,
+                             h->tile_state, s);
+        if (!h->near_off_host_dev)
+            LG_HIP(h, hipMemcpyAsync(h->near_off_host, h->near_off, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost, s));
+        LG_HIP(h, hipEventRecord(h->ev_near, s));
     }
-    // its offsets come back in front of the event the host waits for before it enqueues the plane kernel: ev_orient, or ev_copy
-    // of the bit-row export where the host analyses every frame
-    auto near_copy = [&]() {
-        return hipMemcpyAsync(h->near_off_host, h->near_off, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost, h->copy_stream);
-    };
-    if (pl.near && !h->orient) LG_HIP(h, near_copy());
-    if (h->orient) {   // contour analysis on the device, beside the sweeps; the host reads theta / status back
+    if (h->orient) {   // contour analysis on the device, beside the sweeps; the host reads theta / status behind ev_orient
+        // where the pinned copies have device aliases the kernel writes them itself, else they are copied back
+        const bool direct = h->fp_host_dev && h->orient->h_status_dev;
         {
             ProfScope ps(h, "orient", h->copy_stream);
-            lg_launch_orient(h->orient, h->bits + off * words, h->win + off, h->fp_dev + off, off, n, pl.H, pl.W, pl.WW, h->copy_stream);
+            lg_launch_orient(h->orient, h->bits + off * words, h->win + off, h->fp_dev + off, off, n, pl.H, pl.W, pl.WW, h->copy_stream,
+                             direct ? h->fp_host_dev + off : nullptr);
         }
-        if (pl.near) LG_HIP(h, near_copy());
-        LG_HIP(h, hipMemcpyAsync(h->fp_host + off, h->fp_dev + off, sizeof(LgFrameParams) * n, hipMemcpyDeviceToHost, h->copy_stream));
-        LG_HIP(h, hipMemcpyAsync(h->orient->h_status + off, h->orient->status + off, sizeof(int) * n, hipMemcpyDeviceToHost,
-                                 h->copy_stream));
+        if (!direct) {
+            LG_HIP(h, hipMemcpyAsync(h->fp_host + off, h->fp_dev + off, sizeof(LgFrameParams) * n, hipMemcpyDeviceToHost, h->copy_stream));
+            LG_HIP(h, hipMemcpyAsync(h->orient->h_status + off, h->orient->status + off, sizeof(int) * n, hipMemcpyDeviceToHost,
+                                     h->copy_stream));
+        }
         LG_HIP(h, hipEventRecord(h->ev_orient, h->copy_stream));
     }
     if (h->opt_side_tail) {   // beside the sweeps (latency bound, two workgroups per CU), not behind them: 0.3 ms per 256 frames;
@@ -788,7 +916,8 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
         // with the pruned border search and the two-level hull test, which make the side chain the shorter one again, 0.34 against
         // 0.45 ms: 2.074, 2.093 vs 2.044 .. 2.061 ms, NOTES_side_chain; and with form 6 of the search, one workgroup per CU: 2.070,
         // 2.047, 2.018 vs 2.004, 2.026, 2.011 ms -- the stem bits' dilation and the sweep share the vector ALUs, both take longer,
-        // NOTES_dt_sweep)
+        // NOTES_dt_sweep; and with the nested-span stem kernel, 0.084 instead of 0.101 ms: 1.9005, 1.8853, 1.9201 vs 1.9185, 1.9067,
+        // 1.8976 ms, not every run faster, NOTES_side_copies)
         // Small batches are a chain of latencies, not of throughput: orientation (0.13 ms for one frame; 0.10 since the two-level
         // hull test), border maxima (0.08; 0.035 since the pruned search) and stem bits (0.01) one behind the other on the side
         // stream were the longest chain between the bit rows and the plane kernel of a single-frame call (0.22 ms; the row search
@@ -890,6 +1019,7 @@ void host_orient_frame(lg_ctx* h, const Plan& pl, int b) {
 // the host threads.  LG_HOST_ORIENT: every frame on the host.  *upload = fp_host has entries the device does not have yet.
 int finish_orient(lg_ctx* h, const Plan& pl, int off, int n, bool* upload) {
     *upload = true;
+    h->last_redo = 0;
     if (!h->orient) {
         if (h->export_pending) { const int rc = enq_export(h, pl, 0, pl.B, nullptr); if (rc) return rc; }
         LG_HIP(h, hipEventSynchronize(h->ev_copy));   // bit rows are on the host; the sweeps are running
@@ -900,6 +1030,7 @@ int finish_orient(lg_ctx* h, const Plan& pl, int off, int n, bool* upload) {
     std::vector<int> redo;
     for (int i = 0; i < n; i++)
         if (h->orient->h_status[off + i]) redo.push_back(off + i);
+    h->last_redo = (int)redo.size();
     *upload = !redo.empty();
     if (redo.empty()) return LG_OK;
     if (h->export_pending) { const int rc = enq_export(h, pl, 0, pl.B, nullptr); if (rc) return rc; }
@@ -953,7 +1084,8 @@ int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upl
     a.no_skip = h->opt_no_skip;
     a.persist = 0;   // (lg_launch_final: the tile walk stays an experiment switch)
     a.nt_stores = h->opt_nt_stores ? 1 : 0;  // measured: non-temporal plane stores are slower here (0.57 vs 0.50 ms)
-    if (pl.near) {   // (one sub-batch: off = 0, n = B; the host has waited for ev_orient / ev_copy, behind the copy of near_off)
+    if (pl.near) {   // (one sub-batch: off = 0, n = B)
+        LG_HIP(h, hipEventSynchronize(h->ev_near));   // near_off_host is written (the kernel ended long ago: it follows the bit-row pass)
         a.near_off = h->near_off;
         a.near_total = h->near_off_host[n];
         a.near_tpw = h->opt_final_near;
@@ -1767,7 +1899,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         memset(&fa, 0, sizeof(fa));
         fa.cand_n = h->cand_n; fa.cand_xy = h->cand_xy; fa.cand_info = h->cand_info; fa.logits = h->logits;
         fa.slot = prune ? h->surv_slot : nullptr; fa.slot_frames = SB;
-        fa.fp = h->fp_dev; fa.bits = h->bits; fa.out = h->res_dev;
+        fa.fp = h->fp_dev; fa.bits = h->bits; fa.out = h->res_host_dev ? h->res_host_dev : h->res_dev;
         fa.B = B; fa.H = H; fa.W = W; fa.WW = pl.WW; fa.K = K; fa.use_cnn = use_cnn ? 1 : 0; fa.mask_is_bool = P.mask_is_bool;
         fa.cx = P.cx; fa.cy = P.cy; fa.f = P.f;
         lg_make_se_spans(2 * P.pregrasp_clearance + 1, &fa.se);
@@ -1780,7 +1912,9 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
             lg_launch_candidates(fa, h->cand_rows_dev, s);
         }
     }
-    LG_HIP(h, hipMemcpyAsync(h->res_host, h->res_dev, sizeof(lg_grasp_result) * B, hipMemcpyDeviceToHost, s));
+    // (with a device alias lg_finish_kernel wrote the rows into res_host itself: they are there behind the synchronise below)
+    if (!h->res_host_dev)
+        LG_HIP(h, hipMemcpyAsync(h->res_host, h->res_dev, sizeof(lg_grasp_result) * B, hipMemcpyDeviceToHost, s));
     if (cands)
         LG_HIP(h, hipMemcpyAsync(h->cand_rows_host, h->cand_rows_dev, sizeof(lg_grasp_candidate) * B * K, hipMemcpyDeviceToHost, s));
     const double t_enq2 = now();

@@ -314,26 +314,11 @@ void lg_launch_export_rows(const unsigned long long* bits, const LgWin* wins, un
 
 // ============================================================================ stem penalty (binary dilation on bit rows)
 // stem = dilate(mask & bottom_region, ellipse k) & mask     (grasp_point_selector.py:688-701)
-// dilate(x,y) = OR over SE rows i, dx in [lo_i, hi_i] of src(x+dx, y+i-anchor)  (cv2.dilate, anchor k/2)
-struct LgU192 {
-    unsigned long long w0, w1, w2;  // bit p of the 192-bit row segment: w0 = bits 0..63 (word w-1), w1 = word w, w2 = word w+1
-};
-__device__ __forceinline__ LgU192 lg_shr192(LgU192 r, int s) {  // 0 < s < 64
-    LgU192 o;
-    o.w0 = (r.w0 >> s) | (r.w1 << (64 - s));
-    o.w1 = (r.w1 >> s) | (r.w2 << (64 - s));
-    o.w2 = (r.w2 >> s);
-    return o;
-}
-__device__ __forceinline__ LgU192 lg_or192(LgU192 a, LgU192 b) {
-    LgU192 o = {a.w0 | b.w0, a.w1 | b.w1, a.w2 | b.w2};
-    return o;
-}
-
+// The per-word code is in lg_internal.h (lg_stem_word_rows, lg_stem_word_chain).
+// Per-row form, one thread per (frame, y, word): the fallback for spans that are not nested, and the A/B arm (LG_STEM_ALGO=0).
 __global__ __launch_bounds__(256) void lg_stem_bits_kernel(const unsigned long long* __restrict__ bits,
                                                            unsigned long long* __restrict__ stem, int H, int W, int WW,
                                                            int bottom_start, LgSeSpans se) {
-    // one thread per (frame, y, word)
     long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     long long per_frame = (long long)H * WW;
     int b = blockIdx.y;
@@ -342,39 +327,48 @@ __global__ __launch_bounds__(256) void lg_stem_bits_kernel(const unsigned long l
     const unsigned long long* fb = bits + (long long)b * per_frame;
     unsigned long long self = fb[(long long)y * WW + w];
     unsigned long long acc = 0;
-    if (self != 0 && y + (se.n - 1 - se.anchor) >= bottom_start) {
-        for (int i = 0; i < se.n; i++) {
-            int yy = y + i - se.anchor;
-            int lo = se.lo[i], hi = se.hi[i];
-            if (lo > hi || yy < bottom_start || yy >= H) continue;
-            const unsigned long long* row = fb + (long long)yy * WW;
-            LgU192 r;
-            r.w0 = (w > 0) ? row[w - 1] : 0ull;
-            r.w1 = row[w];
-            r.w2 = (w + 1 < WW) ? row[w + 1] : 0ull;
-            if (!(r.w0 | r.w1 | r.w2)) continue;
-            // T bit p = OR_{j=0..n} R[p+j]
-            int n = hi - lo;
-            LgU192 t = r;
-            int covered = 1;  // t covers shifts [0, covered-1]
-            while (covered * 2 <= n + 1) {
-                t = lg_or192(t, lg_shr192(t, covered));
-                covered *= 2;
-            }
-            if (covered < n + 1) t = lg_or192(t, lg_shr192(t, n + 1 - covered));
-            // out bit b = T bit (64 + b + lo), lo in [-anchor, 0]
-            int sh = 64 + lo;  // 64-anchor .. 64
-            unsigned long long o = (sh == 64) ? t.w1 : ((t.w0 >> sh) | (t.w1 << (64 - sh)));
-            if (lo > 0) o = (t.w1 >> lo) | (t.w2 << (64 - lo));
-            acc |= o;
-        }
-    }
+    if (self != 0 && y + (se.n - 1 - se.anchor) >= bottom_start) acc = lg_stem_word_rows(fb, H, WW, bottom_start, y, w, se);
     stem[(long long)b * per_frame + gid] = acc & self;
 }
 
-void lg_launch_stem_bits(const unsigned long long* bits, unsigned long long* stem, int B, int H, int W, int WW,
-                         int bottom_start, const LgSeSpans& se, hipStream_t s) {
+// Nested-span form.  gridDim.x workgroups per frame: first every word outside the frame's active rectangle (lg_stem_active) is
+// zeroed by its index alone, without a load -- the whole plane is written on every call, lg_final_kernel reads whole tile rows
+// and a small leaf after a large one must not meet stale words -- then the words of the rectangle, mapped densely onto the
+// threads, do the arithmetic.  A frame whose bounding box lies above the ellipse's reach does none.
+__global__ __launch_bounds__(256) void lg_stem_chain_kernel(const unsigned long long* __restrict__ bits,
+                                                            unsigned long long* __restrict__ stem,
+                                                            const LgWin* __restrict__ wins, int H, int WW, int bottom_start,
+                                                            LgSeSpans se, LgStemPlan plan) {
+    const int b = blockIdx.y;
+    const size_t per_frame = (size_t)H * WW;
+    const unsigned long long* fb = bits + (size_t)b * per_frame;
+    unsigned long long* fs = stem + (size_t)b * per_frame;
+    const LgStemRect rc = lg_stem_active(wins[b], H, WW, bottom_start, se.n, se.anchor);
+    const int ya = rc.ya, yb = rc.yb, w0 = rc.w0, w1 = rc.w1;
+    const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+    for (int i = tid; i < (int)per_frame; i += nth) {   // (H * WW <= 16384 * 128)
+        const int y = i / WW, w = i - y * WW;
+        if (!(y >= ya && y <= yb && w >= w0 && w <= w1)) fs[i] = 0ull;
+    }
+    if (ya > yb) return;
+    const int nw = w1 - w0 + 1, nact = (yb - ya + 1) * nw;
+    for (int i = tid; i < nact; i += nth) {
+        const int r = i / nw, y = ya + r, w = w0 + (i - r * nw);
+        const size_t o = (size_t)y * WW + w;
+        const unsigned long long self = fb[o];
+        fs[o] = self ? (lg_stem_word_chain(fb, H, WW, bottom_start, y, w, se, plan) & self) : 0ull;
+    }
+}
+
+void lg_launch_stem_bits(const unsigned long long* bits, unsigned long long* stem, const LgWin* wins, int B, int H, int W, int WW,
+                         int bottom_start, const LgSeSpans& se, const LgStemPlan* plan, hipStream_t s) {
     long long per_frame = (long long)H * WW;
+    if (plan && plan->nested && wins) {
+        // eight words of the plane per thread, at most 16 workgroups per frame (256 frames of 1080p: 4096 workgroups)
+        const unsigned nblk = (unsigned)std::max<long long>(1, std::min<long long>((per_frame + 2047) / 2048, 16));
+        hipLaunchKernelGGL(lg_stem_chain_kernel, dim3(nblk, B), dim3(256), 0, s, bits, stem, wins, H, WW, bottom_start, se, *plan);
+        return;
+    }
     dim3 grid((unsigned)((per_frame + 255) / 256), B);
     hipLaunchKernelGGL(lg_stem_bits_kernel, grid, dim3(256), 0, s, bits, stem, H, W, WW, bottom_start, se);
 }
@@ -2448,7 +2442,7 @@ void lg_launch_final(const LgFinalArgs& a_in, hipStream_t s, hipEvent_t ev_start
 // byte 0.  Workgroup 0 then scans the frames' near counts into near_off (thread = frame, frames t, t + 256, ... in rounds with
 // a running base, as lg_survivors_kernel).  No atomics: the same output on every run.
 __global__ __launch_bounds__(256) void lg_near_tiles_kernel(const LgWin* __restrict__ win, int B, int H, int W, int halo,
-                                                            int32_t* __restrict__ near_off,
+                                                            int32_t* __restrict__ near_off, int32_t* __restrict__ near_off_h,
                                                             unsigned long long* __restrict__ tilekeys,
                                                             uint8_t* __restrict__ tile_state) {
     const int tiles_x = (W + LG_TW - 1) / LG_TW, tiles_y = (H + LG_TH - 1) / LG_TH, ntile = tiles_x * tiles_y;
@@ -2486,17 +2480,23 @@ __global__ __launch_bounds__(256) void lg_near_tiles_kernel(const LgWin* __restr
         for (int w = 0; w < wave; w++) pos += s_wave[w];
         __syncthreads();   // everyone has read s_base and s_wave
         if (t == 255) s_base = pos + c;
-        if (b < B) near_off[b] = pos;
+        if (b < B) {
+            near_off[b] = pos;
+            if (near_off_h) near_off_h[b] = pos;   // (the host's pinned copy through its device alias)
+        }
         __syncthreads();
     }
-    if (t == 0) near_off[B] = s_base;
+    if (t == 0) {
+        near_off[B] = s_base;
+        if (near_off_h) near_off_h[B] = s_base;
+    }
 }
 
-void lg_launch_near_tiles(const LgWin* win, int B, int H, int W, int halo, int32_t* near_off, unsigned long long* tilekeys,
-                          uint8_t* tile_state, hipStream_t s) {
+void lg_launch_near_tiles(const LgWin* win, int B, int H, int W, int halo, int32_t* near_off, int32_t* near_off_host_dev,
+                          unsigned long long* tilekeys, uint8_t* tile_state, hipStream_t s) {
     const long long total = (long long)((W + LG_TW - 1) / LG_TW) * ((H + LG_TH - 1) / LG_TH) * B;
     hipLaunchKernelGGL(lg_near_tiles_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, win, B, H, W, halo, near_off,
-                       tilekeys, tile_state);
+                       near_off_host_dev, tilekeys, tile_state);
 }
 
 // ============================================================================ the tail of select_grasp_point, per frame

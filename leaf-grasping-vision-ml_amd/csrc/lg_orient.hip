@@ -169,18 +169,32 @@ __device__ __forceinline__ bool hull_vertex(const short* X, RowOf row, int ja, i
     return LEFT ? p * q2 < p2 * q : p * q2 > p2 * q;
 }
 
-__device__ void write_none(LgFrameParams* fp, double* out, int* status, int b, int st) {
+// A frame's parameters and status word: into device memory (the plane kernel reads fp) and, where the host's pinned copies
+// have device aliases (fp_h, status_h: both or neither), straight into those -- the host reads them behind the event it waits
+// for, without a copy in between.
+struct OrientOut {
+    LgFrameParams* fp;
+    int* status;
+    LgFrameParams* fp_h;
+    int* status_h;
+};
+__device__ __forceinline__ void put_frame(const OrientOut& o, int b, const LgFrameParams& f, int st) {
+    o.fp[b] = f;
+    o.status[b] = st;
+    if (o.fp_h) { o.fp_h[b] = f; o.status_h[b] = st; }
+}
+
+__device__ void write_none(const OrientOut& o, double* out, int b, int st) {
     LgFrameParams f;
     f.sin_t = 0.f; f.cos_t = 0.f; f.has_angle = 0; f.theta = __builtin_nanf("");
-    fp[b] = f;
     for (int i = 0; i < 5; i++) out[5 * (size_t)b + i] = __builtin_nan("");
-    status[b] = st;
+    put_frame(o, b, f, st);
 }
 
 __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ bits, const LgWin* __restrict__ win, int H, int W,
                                                        int WW, int cap, uint32_t* run_x_, uint16_t* run_y_, int* roots_,
                                                        int* row_start_, short* rowL_, short* rowR_, unsigned char* vflag_,
-                                                       int* comp_, LgFrameParams* fp, double* out, int* status) {
+                                                       int* comp_, OrientOut oo, double* out) {
 #pragma clang fp contract(off)
     // parent[cap] | L[n], R[n] shorts, survivor lists [n], [n], ballots | hull x[OHULL], y[OHULL] doubles
     extern __shared__ __align__(16) unsigned char s_dyn[];
@@ -191,7 +205,7 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
     const LgWin w = win[b];
     const int hyb = w.by1 - w.by0 + 1;
     if (w.bx1 < w.bx0 || hyb <= 0) {                      // empty mask: the reference returns None
-        if (tid == 0) write_none(fp, out, status, b, 0);
+        if (tid == 0) write_none(oo, out, b, 0);
         return;
     }
     FrameScratch fs;
@@ -220,7 +234,7 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
     int R = 0;
     int base = block_scan(sum, s_scan, &R);
     if (R > cap) {
-        if (tid == 0) write_none(fp, out, status, b, 1);
+        if (tid == 0) write_none(oo, out, b, 1);
         return;
     }
     int* parent = (int*)s_dyn;
@@ -424,7 +438,7 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
     int br = block_scan(cr, s_scan, &totR);
     const int nh = totL + totR;
     if (nh > OHULL) {
-        if (tid == 0) write_none(fp, out, status, b, 1);
+        if (tid == 0) write_none(oo, out, b, 1);
         return;
     }
     double* hx = (double*)s_dyn;                          // (Ls / Rs are dead: every thread passed the scans' barriers)
@@ -450,10 +464,9 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
             LgFrameParams f;
             const double ang = M_PI / 2;
             f.sin_t = (float)sin(ang); f.cos_t = (float)cos(ang); f.has_angle = 1; f.theta = (float)ang;
-            fp[b] = f;
             double* o = out + 5 * (size_t)b;
             o[0] = ang; o[1] = 0; o[2] = 0; o[3] = hx[0]; o[4] = hyv[0];
-            status[b] = 0;
+            put_frame(oo, b, f, 0);
         }
         return;
     }
@@ -494,7 +507,7 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
     if (m_rank != 0x7fffffff && (u64)__double_as_longlong(m_area) == s_key) atomicMin(&s_rank, m_rank);
     __syncthreads();
     if (s_rank == 0x7fffffff) {                            // (cannot happen: distinct vertices give edges of non-zero length)
-        if (tid == 0) write_none(fp, out, status, b, 1);
+        if (tid == 0) write_none(oo, out, b, 1);
         return;
     }
     if (m_rank == s_rank) {
@@ -504,11 +517,10 @@ __global__ __launch_bounds__(OT) void lg_orient_kernel(const u64* __restrict__ b
         if (ang <= 0) ang += M_PI;
         LgFrameParams f;
         f.sin_t = (float)sin(ang); f.cos_t = (float)cos(ang); f.has_angle = 1; f.theta = (float)ang;
-        fp[b] = f;
         double* o = out + 5 * (size_t)b;
         o[0] = ang; o[1] = m_w > m_h ? m_w : m_h; o[2] = m_w < m_h ? m_w : m_h;
         o[3] = m_sc * m_ux - m_tc * m_uy; o[4] = m_sc * m_uy + m_tc * m_ux;
-        status[b] = 0;
+        put_frame(oo, b, f, 0);
     }
     OPHASE(7);
 }
@@ -553,6 +565,11 @@ int lg_orient_ensure(LgOrientWs*& w, int B, int H, std::string* err) {
     A(dalloc(&w->vflag, nb * 2 * H)); A(dalloc(&w->comp, nb * 4 * w->cap)); A(dalloc(&w->out, nb * 5)); A(dalloc(&w->status, nb));
     A(hipHostMalloc((void**)&w->h_out, sizeof(double) * 5 * nb));
     A(hipHostMalloc((void**)&w->h_status, sizeof(int) * nb));
+    // device-side alias of the pinned status words (lg_launch_orient with fp_host_dev writes them directly); none: copies
+    if (rc == hipSuccess && hipHostGetDevicePointer((void**)&w->h_status_dev, w->h_status, 0) != hipSuccess) {
+        w->h_status_dev = nullptr;
+        (void)hipGetLastError();
+    }
     if (rc != hipSuccess) {
         if (err) *err = std::string("orientation scratch: ") + hipGetErrorString(rc);
         lg_orient_free(w);
@@ -573,9 +590,14 @@ int lg_orient_ensure(LgOrientWs*& w, int B, int H, std::string* err) {
 
 // frames [off, off + n) of the workspace: bits / win / fp point at frame `off`
 void lg_launch_orient(LgOrientWs* w, const unsigned long long* bits, const LgWin* win, LgFrameParams* fp, int off, int n, int H,
-                      int W, int WW, hipStream_t s) {
+                      int W, int WW, hipStream_t s, LgFrameParams* fp_host_dev) {
     const size_t o = (size_t)off;
+    OrientOut oo;
+    oo.fp = fp; oo.status = w->status + o;
+    const bool direct = fp_host_dev && w->h_status_dev;
+    oo.fp_h = direct ? fp_host_dev : nullptr;
+    oo.status_h = direct ? w->h_status_dev + o : nullptr;
     hipLaunchKernelGGL(lg_orient_kernel, dim3(n), dim3(OT), w->lds, s, bits, win, H, W, WW, w->cap, w->run_x + o * w->cap,
                        w->run_y + o * w->cap, w->roots + o * w->cap, w->row_start + o * (H + 1), w->rowL + o * H, w->rowR + o * H,
-                       w->vflag + o * 2 * H, w->comp + o * 4 * w->cap, fp, w->out + 5 * o, w->status + o);
+                       w->vflag + o * 2 * H, w->comp + o * 4 * w->cap, oo, w->out + 5 * o);
 }
