@@ -207,14 +207,20 @@ int lg_topk_nms(lg_handle h, const float* trad, const uint8_t* valid, int B, int
                 int min_dist, int32_t* out_xy, int32_t* out_n, void* stream);
 
 /* 9-channel 32x32 patches around n_xy points per frame.  maps[] as produced by lg_score_maps
-   (indices 0..6 are read).  xy [B][k][2] DEVICE, n [B] DEVICE; patches [B][k][9][32][32] f32 DEVICE. */
+   (indices 0..6 are read).  xy [B][k][2] DEVICE, n [B] DEVICE; patches [B][k][9][32][32] f32 DEVICE.
+   Depth and the seven planes are min-max normalised per window where max > min, by numpy's rules: a channel whose window
+   holds a NaN has a NaN minimum and maximum and stays raw (the NaN included); one that holds an infinity is divided by an
+   infinite range (0 at its finite pixels, NaN at the infinite ones).  Depth is read as passed, off the leaf too. */
 int lg_gather_patches(lg_handle h, const float* depth, const uint8_t* mask,
                       const float* const maps[LG_NUM_MAPS], int B, int H, int W, int k,
                       const int32_t* xy, const int32_t* n, float* patches, void* stream);
 
 int lg_cnn_load(lg_handle h, const lg_cnn_weights* w);
 int lg_cnn_unload(lg_handle h);
-/* patches [N][9][32][32] f32 DEVICE -> logits [N] f32 DEVICE. */
+/* patches [N][9][32][32] f32 DEVICE -> logits [N] f32 DEVICE.
+   Every ReLU and max-pool propagates NaN as torch's relu and max_pool2d do: a patch that holds a NaN or an infinity in any
+   channel gets a NaN logit (and through lg_ml_combined_score a NaN ml score, confidence and combined score, which never wins
+   the selection); the other patches of the call are computed as if it held finite values, bit for bit. */
 int lg_cnn_forward(lg_handle h, const float* patches, int N, float* logits, void* stream);
 
 /* Whole GraspPointSelector.select_grasp_point for B frames: maps -> valid -> top-k -> (CNN rescoring

@@ -51,6 +51,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
+// The maximum of every ReLU and 2x2 max-pool below: a NaN operand gives NaN, as torch's relu and max_pool2d do (C's fmax
+// returns the other operand, which would turn a patch with a NaN or an infinity in it into a finite logit).  One
+// v_maximum3_f32; with finite operands it is the same number fmax gives.
+__device__ __forceinline__ float lg_nanmax(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
 struct LayerCfg { int cin, cinp, cout, wi; bool pool; };
 constexpr LayerCfg kLayers[6] = {
     {9, 10, 64, 32, false}, {64, 64, 64, 32, true},   {64, 64, 128, 16, false},
@@ -207,24 +212,24 @@ __global__ __launch_bounds__(256, 2) void lg_conv3x3_kernel(const float* __restr
                 for (int i = 0; i < 2; i++) {
                     const int pb = wp_i * 2 + i;
                     const int row = y0 + pb * PBROWS + p / WI, x = p % WI;
-                    out_n[(size_t)co * OPL + row * OP + x] = fmaxf(acc[i][j][r] + bv, 0.0f);
+                    out_n[(size_t)co * OPL + row * OP + x] = lg_nanmax(acc[i][j][r] + bv, 0.0f);
                 }
             } else {
                 if (WI == 32) {
-                    float v = fmaxf(acc[0][j][r], acc[1][j][r]);   // the wave's two pixel blocks are rows y0+2a, y0+2a+1
-                    v = fmaxf(v, __shfl_xor(v, 1, 64));
+                    float v = lg_nanmax(acc[0][j][r], acc[1][j][r]);   // the wave's two pixel blocks are rows y0+2a, y0+2a+1
+                    v = lg_nanmax(v, __shfl_xor(v, 1, 64));
                     const int yo = (y0 + wp_i * 2) / 2, xo = p >> 1;
-                    if ((p & 1) == 0) out_n[(size_t)co * OPL + yo * OP + xo] = fmaxf(v + bv, 0.0f);
+                    if ((p & 1) == 0) out_n[(size_t)co * OPL + yo * OP + xo] = lg_nanmax(v + bv, 0.0f);
                 } else {
 #pragma unroll
                     for (int i = 0; i < 2; i++) {
                         float v = acc[i][j][r];
-                        v = fmaxf(v, __shfl_xor(v, WI, 64));
-                        v = fmaxf(v, __shfl_xor(v, 1, 64));
+                        v = lg_nanmax(v, __shfl_xor(v, WI, 64));
+                        v = lg_nanmax(v, __shfl_xor(v, 1, 64));
                         const int pb = wp_i * 2 + i;
                         const int row = y0 + pb * PBROWS + p / WI, x = p % WI;
                         if (((p / WI) & 1) == 0 && (x & 1) == 0)
-                            out_n[(size_t)co * OPL + (row >> 1) * OP + (x >> 1)] = fmaxf(v + bv, 0.0f);
+                            out_n[(size_t)co * OPL + (row >> 1) * OP + (x >> 1)] = lg_nanmax(v + bv, 0.0f);
                     }
                 }
             }
@@ -326,7 +331,7 @@ __global__ __launch_bounds__(256, 2) void lg_conv0_kernel(const float* __restric
 #pragma unroll
                 for (int i = 0; i < 2; i++) {
                     const int y = band * ROWS + 2 * wave + i;
-                    out_n[(size_t)co * PLANE + y * WP + p] = fmaxf(acc[i][j][r] + bv[j][r], 0.0f);
+                    out_n[(size_t)co * PLANE + y * WP + p] = lg_nanmax(acc[i][j][r] + bv[j][r], 0.0f);
                 }
             }
     }
@@ -525,11 +530,11 @@ __global__ __launch_bounds__(256, 2) void lg_wino_kernel(const float* __restrict
             if (n < N) {
                 float* o = out + ((size_t)n * COUT + co) * OPL + OO;
                 if (POOL) {
-                    o[trg * OP + tcg] = fmaxf(fmaxf(fmaxf(y00, y01), fmaxf(y10, y11)), 0.0f);
+                    o[trg * OP + tcg] = lg_nanmax(lg_nanmax(lg_nanmax(y00, y01), lg_nanmax(y10, y11)), 0.0f);
                 } else {
                     float* o0 = o + (2 * trg) * OP + 2 * tcg;    // (interior pixels start at an odd column: dword stores)
-                    o0[0] = fmaxf(y00, 0.f); o0[1] = fmaxf(y01, 0.f);
-                    o0[OP] = fmaxf(y10, 0.f); o0[OP + 1] = fmaxf(y11, 0.f);
+                    o0[0] = lg_nanmax(y00, 0.f); o0[1] = lg_nanmax(y01, 0.f);
+                    o0[OP] = lg_nanmax(y10, 0.f); o0[OP + 1] = lg_nanmax(y11, 0.f);
                 }
             }
         }
@@ -1016,18 +1021,18 @@ __global__ __launch_bounds__(512) void lg_wino4_kernel(const float* __restrict__
                     if (POOL) {
 #pragma unroll
                         for (int p = 0; p < 2; p++) {
-                            const float v0 = fmaxf(fmaxf(fmaxf(y[2 * p][0], y[2 * p][1]), fmaxf(y[2 * p + 1][0], y[2 * p + 1][1])), 0.f);
-                            const float v1 = fmaxf(fmaxf(fmaxf(y[2 * p][2], y[2 * p][3]), fmaxf(y[2 * p + 1][2], y[2 * p + 1][3])), 0.f);
+                            const float v0 = lg_nanmax(lg_nanmax(lg_nanmax(y[2 * p][0], y[2 * p][1]), lg_nanmax(y[2 * p + 1][0], y[2 * p + 1][1])), 0.f);
+                            const float v1 = lg_nanmax(lg_nanmax(lg_nanmax(y[2 * p][2], y[2 * p][3]), lg_nanmax(y[2 * p + 1][2], y[2 * p + 1][3])), 0.f);
                             if (LG_W4_NT) __builtin_nontemporal_store((f32x2u){v0, v1}, reinterpret_cast<f32x2u*>(o + (2 * trg + p) * OP + 2 * tcg));
                             else *reinterpret_cast<f32x2u*>(o + (2 * trg + p) * OP + 2 * tcg) = (f32x2u){v0, v1};
                         }
                     } else {
 #pragma unroll
                         for (int p = 0; p < 4; p++)
-                            if (LG_W4_NT) __builtin_nontemporal_store((f32x4u){fmaxf(y[p][0], 0.f), fmaxf(y[p][1], 0.f), fmaxf(y[p][2], 0.f), fmaxf(y[p][3], 0.f)},
+                            if (LG_W4_NT) __builtin_nontemporal_store((f32x4u){lg_nanmax(y[p][0], 0.f), lg_nanmax(y[p][1], 0.f), lg_nanmax(y[p][2], 0.f), lg_nanmax(y[p][3], 0.f)},
                                                                       reinterpret_cast<f32x4u*>(o + (4 * trg + p) * OP + 4 * tcg));
                             else *reinterpret_cast<f32x4u*>(o + (4 * trg + p) * OP + 4 * tcg) =
-                                (f32x4u){fmaxf(y[p][0], 0.f), fmaxf(y[p][1], 0.f), fmaxf(y[p][2], 0.f), fmaxf(y[p][3], 0.f)};
+                                (f32x4u){lg_nanmax(y[p][0], 0.f), lg_nanmax(y[p][1], 0.f), lg_nanmax(y[p][2], 0.f), lg_nanmax(y[p][3], 0.f)};
                     }
                     // The halo around the interior is (and stays) zero, and is written all the same: a cache line that keeps
                     // bytes its writer did not touch leaves the L2 as a masked write, which the memory side has to merge with
@@ -1207,7 +1212,7 @@ __global__ __launch_bounds__(256) void lg_head_kernel(const float* __restrict__ 
             if (c < F) {
                 float e = ca_b2[c];
                 for (int j = 0; j < hid; j++) {
-                    const float z = fmaxf(s_a[0][j] + s_a[1][j] + s_a[2][j] + s_a[3][j] + ca_b1[j], 0.0f);
+                    const float z = lg_nanmax(s_a[0][j] + s_a[1][j] + s_a[2][j] + s_a[3][j] + ca_b1[j], 0.0f);
                     e += ca_w2[c * hid + j] * z;
                 }
                 f[i] *= 1.0f / (1.0f + expf(-e));
@@ -1221,19 +1226,19 @@ __global__ __launch_bounds__(256) void lg_head_kernel(const float* __restrict__ 
     for (int o = t; o < d1; o += 256) {
         float s = b0[o];
         for (int c = 0; c < F; c++) s += w0[c * d1 + o] * s_f[c];
-        s_g[o] = fmaxf(s, 0.0f);
+        s_g[o] = lg_nanmax(s, 0.0f);
     }
     __syncthreads();
     for (int o = t; o < d2; o += 256) {
         float s = b1[o];
         for (int c = 0; c < d1; c++) s += w1[c * d2 + o] * s_g[c];
-        s_f[o] = fmaxf(s, 0.0f);
+        s_f[o] = lg_nanmax(s, 0.0f);
     }
     __syncthreads();
     for (int o = t; o < d3; o += 256) {
         float s = b2[o];
         for (int c = 0; c < d2; c++) s += w2[c * d3 + o] * s_f[c];
-        s_g[o] = fmaxf(s, 0.0f);
+        s_g[o] = lg_nanmax(s, 0.0f);
     }
     __syncthreads();
     {

@@ -3071,6 +3071,9 @@ struct LgGatherMaps { const float* p[7]; };
 // thread as in the plane kernel, with the stored flatness and distance, behind the plane kernel's own wave-level predicate
 // (lg_wave_on_mask: the sign of a zero depends on it).  The window then reads those five planes from LDS.
 struct LgGatherNoDefer { int unused; };
+// numpy's min and max return NaN for a window that holds one (fminf / fmaxf skip it)
+__device__ __forceinline__ float lg_nanmin(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+__device__ __forceinline__ float lg_nanmax(float a, float b) { return __builtin_elementwise_maximum(a, b); }
 template <bool HALO, bool DEFER>
 __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict__ depth,
                                                         const uint8_t* __restrict__ mask, LgGatherMaps maps,
@@ -3180,21 +3183,21 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
             else
                 val = (c == 0) ? depth[o] : (c == 1) ? (mask[o] ? 1.0f : 0.0f) : mat[q] ? maps.p[c - 2][o] : cst;
             v[q] = val;
-            mn = fminf(mn, val);
-            mx = fmaxf(mx, val);
+            mn = lg_nanmin(mn, val);
+            mx = lg_nanmax(mx, val);
         }
         if (c != 1) {
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) {
-                mn = fminf(mn, __shfl_xor(mn, o, 64));
-                mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+                mn = lg_nanmin(mn, __shfl_xor(mn, o, 64));
+                mx = lg_nanmax(mx, __shfl_xor(mx, o, 64));
             }
             __syncthreads();  // previous channel's readers are done
             if ((t & 63) == 0) { s_mn[t >> 6] = mn; s_mx[t >> 6] = mx; }
             __syncthreads();
-            mn = fminf(fminf(s_mn[0], s_mn[1]), fminf(s_mn[2], s_mn[3]));
-            mx = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
-            if (mx > mn) {
+            mn = lg_nanmin(lg_nanmin(s_mn[0], s_mn[1]), lg_nanmin(s_mn[2], s_mn[3]));
+            mx = lg_nanmax(lg_nanmax(s_mx[0], s_mx[1]), lg_nanmax(s_mx[2], s_mx[3]));
+            if (mx > mn) {   // false with a NaN in the channel, as numpy's p.max() > p.min(): the channel stays raw
                 const float range = mx - mn;
 #pragma unroll
                 for (int q = 0; q < 4; q++) v[q] = (v[q] - mn) / range;

@@ -140,6 +140,77 @@ def test_selector_exposes_the_candidate_calls():
         assert name in _lib.SYMBOLS
 
 
+def lib_combine(logit, trad):
+    ml, conf, comb = C.c_double(-7.0), C.c_double(-7.0), C.c_double(-7.0)
+    assert _lib.lib.lg_ml_combined_score(float(logit), float(trad), C.byref(ml), C.byref(conf), C.byref(comb)) == 0
+    return ml.value, conf.value, comb.value
+
+
+def ref_combine(logit, trad):
+    """grasp_point_selector.py:133-136 and :222-226 as the reference writes them: the sigmoid as torch computes it (0 at -inf,
+    where math.exp would raise), then Python floats and Python's min."""
+    with np.errstate(over="ignore"):
+        s = float(1.0 / (1.0 + np.exp(-np.float64(logit))))
+    ml = float(np.tanh(s * 3.0) * 0.5 + 0.5)
+    conf = 1.0 - abs(ml - 0.5) * 2
+    w = min(0.3, conf * 0.6)
+    return ml, conf, (1.0 - w) * trad + w * ml
+
+
+@pytest.mark.parametrize("trad", [0.0, 0.37, 0.9, 1.5])
+def test_combined_score_of_a_non_finite_logit(trad):
+    """A NaN logit (a non-finite value in the candidate's window) gives NaN ml, confidence and combined score: Python's
+    min(0.3, nan) is 0.3 and so is fmin's, and 0.3 * nan is NaN.  +Inf gives ml = tanh(3)/2 + 1/2, -Inf gives 0.5."""
+    assert min(0.3, float("nan")) == 0.3
+    for nan in (float("nan"), -float("nan")):
+        got = lib_combine(nan, trad)
+        assert all(math.isnan(v) for v in got), got
+        assert all(math.isnan(v) for v in ref_combine(nan, trad))
+    for logit, ml in ((math.inf, math.tanh(3.0) / 2 + 0.5), (-math.inf, 0.5)):
+        got, exp = lib_combine(logit, trad), ref_combine(logit, trad)
+        assert exp[0] == pytest.approx(ml, rel=0, abs=1e-15)
+        np.testing.assert_allclose(got, exp, rtol=0, atol=1e-15)
+    for logit in (-40.0, -1.0, 0.0, 0.3, 25.0):    # finite control: the same expression
+        np.testing.assert_allclose(lib_combine(logit, trad), ref_combine(logit, trad), rtol=0, atol=1e-15)
+    got = lib_combine(0.3, float("nan"))           # a NaN traditional score: ml and confidence finite, combined NaN
+    assert not math.isnan(got[0]) and not math.isnan(got[1]) and math.isnan(got[2])
+
+
+def test_rank_with_nan_combined_scores_off_rank_0():
+    """NaN combined scores (scored candidates whose window held a hole) at candidates other than 0: a NaN never wins, such a
+    candidate is only ever taken on its traditional score as the first one left, and the finite ones order as they do when
+    the NaN rows are unscored."""
+    nan = float("nan")
+    trad = [0.50, 0.45, 0.40, 0.35, 0.30, 0.25]
+    comb = [0.52, nan, 0.70, nan, 0.60, nan]
+    scored = [1] * 6
+    exp = ref_rank(trad, comb, scored, True)
+    got = lib_rank(trad, comb, scored, True)
+    assert got == exp
+    assert got[0] == [2, 4, 0, 1, 3, 5] and got[1] == [0.70, 0.60, 0.52, 0.45, 0.35, 0.25] and got[2] == [1, 1, 1, 0, 0, 0]
+    for r, i in enumerate(got[0]):
+        if math.isnan(comb[i]):
+            assert got[2][r] == 0 and got[1][r] == trad[i]
+    # the same list with the NaN rows unscored instead: the same order and picks
+    unscored = [0 if math.isnan(c) else 1 for c in comb]
+    assert lib_rank(trad, comb, unscored, True) == got
+    # randomised: NaN combined scores anywhere but at candidate 0, finite traditional scores
+    rng = np.random.default_rng(5)
+    for trial in range(300):
+        n = int(rng.integers(2, 65))
+        t = rng.random(n)
+        c = rng.random(n)
+        holes = rng.random(n) < 0.4
+        holes[0] = False
+        c[holes] = np.nan
+        s = np.ones(n, np.int32)
+        o, p, b = lib_rank(t, c, s, True)
+        assert (o, p, b) == ref_rank(t, c, s, True), trial
+        assert not any(math.isnan(v) for v in p)
+        assert all(b[r] == 0 and p[r] == t[i] for r, i in enumerate(o) if holes[i]), trial
+        assert (o, p, b) == lib_rank(t, c, (~holes).astype(np.int32), True), trial
+
+
 @pytest.mark.parametrize("n", [1, 2, 64])
 def test_rank_all_ties(n):
     order, pick, by = lib_rank([0.25] * n, [0.25] * n, [1] * n, n > 1)
