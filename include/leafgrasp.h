@@ -368,9 +368,13 @@ int lg_debug_dt_max(lg_handle h, int frame, uint32_t out[2], int32_t win[4]);
    skipped (the maximum provably lies on the frame border).  Which form a batch takes is decided on the device. */
 int lg_debug_dt_form(lg_handle h, int frame, int32_t form[2]);
 /* *algo = the form of the row search the last call queued for its searched frames (LG_DT_SEARCH_ALGO's numbering: 1 one level,
-   2 anchors + searched bands, 3 / 4 the same with four / one anchor rows per lane when forced, 5 seed pairs + stencil bands,
-   6 one register sweep per frame); 0: the handle queues no search. */
+   5 seed pairs + stencil bands, 6 one register sweep per frame; 2 to 4 were the two-level search with recorded minimising rows
+   and are no longer taken); 0: the handle queues no search. */
 int lg_debug_dt_search_form(lg_handle h, int32_t* algo);
+/* The table behind it on the host (no device, no handle): the form a batch of n frames of H x W takes when LG_DT_SEARCH_ALGO is
+   `forced` (0: by size).  1 up to 64 x 1080 x 1920 pixels in the batch; above, 6 where 16 <= W <= 2048 and H >= 16, else 5 where
+   H, W >= 16, else 1.  Forcing 5 or 6 gives the same answer whatever the batch; forcing 1 gives 1. */
+int lg_dt_form_host(int forced, int n, int H, int W);
 /* *n = frames of the last lg_score_maps / lg_select_grasp* call that the device orientation kernel handed back (more runs than
    its scratch holds, LG_ORIENT_CAP) and the host threads analysed; 0 where the host analyses every frame anyway
    (LG_HOST_ORIENT).

@@ -122,6 +122,7 @@ SYMBOLS = {
     "lg_debug_dt_form": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int32)]),
     "lg_debug_orient_redo": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "lg_debug_dt_search_form": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
+    "lg_dt_form_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "lg_near_tile_rect": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "lg_stem_words_host": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "lg_stem_words_host_spans": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int8),

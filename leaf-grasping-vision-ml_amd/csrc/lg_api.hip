@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "lg_cnn.h"
+#include "lg_dt.h"
 #include "lg_eval.h"
 #include "lg_leaf.h"
 #include "lg_internal.h"
@@ -111,9 +112,8 @@ struct lg_ctx {
     LgLeafProf* leaf_prof = nullptr;   // per-kernel times of the leaf stage (lg_profile_enable)
     LgOrientWs* orient = nullptr;   // device-side orientation scratch (lg_orient.hip)
     hipEvent_t ev_orient = nullptr, ev_side = nullptr, ev_search = nullptr;
-    int opt_dt_algo = 0;            // LG_DT_SEARCH_ALGO=1: one-level row search at every batch size; 2: anchors + bands (3 / 4: with four / one
-                                    // anchor rows per lane); 5: seed row pairs + stencil bands; 6: one two-wave register sweep per frame;
-                                    // 0: by batch size
+    int opt_dt_algo = 0;            // LG_DT_SEARCH_ALGO=1: one-level row search at every batch size; 5: seed row pairs + stencil bands;
+                                    // 6: one two-wave register sweep per frame; 0: by batch size (lg_dt_form, lg_dt.h)
     int last_dt_algo = 0;           // lg_debug_dt_search_form: the form the row search of the last call took (0: no search was queued)
     int opt_dt_band_p = 16, opt_dt_band_e = 4;   // LG_DT_BAND_P=12 | 16 | 24 | 32: rows from one seed pair of form 5 to the next;
                                     // LG_DT_BAND_E=2 | 4: columns per lane of its band kernel (experiments, tests)
@@ -433,7 +433,10 @@ int lg_create(int device, lg_handle* out) {
     if (const char* e = getenv("LG_CNN_PRUNE")) h->opt_cnn_prune = atoi(e) != 0;
     if (const char* e = getenv("LG_DEFER_PLANES")) h->opt_defer_planes = atoi(e) != 0;
     if (const char* e = getenv("LG_DT_SEARCH")) h->opt_dt_search = std::max(0, std::min(2, atoi(e)));
-    if (const char* e = getenv("LG_DT_SEARCH_ALGO")) h->opt_dt_algo = std::max(0, std::min(6, atoi(e)));
+    if (const char* e = getenv("LG_DT_SEARCH_ALGO")) {
+        const int f = atoi(e);
+        if (f == 0 || f == LG_DT_FORM_ROWS || f == LG_DT_FORM_BANDS || f == LG_DT_FORM_SWEEP) h->opt_dt_algo = f;
+    }
     if (const char* e = getenv("LG_DT_BAND_P")) { const int p = atoi(e); if (p == 12 || p == 16 || p == 24 || p == 32) h->opt_dt_band_p = p; }
     if (const char* e = getenv("LG_DT_BAND_E")) { const int v = atoi(e); if (v == 2 || v == 4) h->opt_dt_band_e = v; }
     if (const char* e = getenv("LG_SIDE_TAIL")) h->opt_side_tail = std::max(0, std::min(2, atoi(e)));
@@ -798,6 +801,8 @@ int lg_debug_dt_search_form(lg_handle h, int32_t* algo) {
     return LG_OK;
 }
 
+int lg_dt_form_host(int forced, int n, int H, int W) { return lg_dt_form(forced, n, H, W); }
+
 }  // extern "C"
 
 namespace {
@@ -822,23 +827,6 @@ struct Plan {  // one call's geometry, parameters and plane pointers (absolute, 
     bool defer = false;
 };
 
-
-// which form of the row search a batch of n frames takes (LG_DT_SEARCH_ALGO forces one): one level up to 64 frames of 1080p (one
-// launch, the device is not full: 32 of 1080p 0.14 vs 0.18 ms); above, two levels: seed row pairs + stencil bands (form 5; 256 of
-// 1080p 0.24 + 0.18 ms against 0.28 + 0.36 for form 2's anchors + searched bands, which took this place before)
-// Form 6 (one two-wave register sweep per frame) replaces form 5 there when a bounding box's span fits 64 lanes x 32 columns,
-// W <= 2048 (H, W >= 16 like form 5): 256 of 1080p 0.229 ms against 0.235 + 0.140 for seed pairs + bands, and one workgroup per CU
-// instead of 32 k workgroups beside the side chain (profiles/NOTES_dt_sweep.md).  4K keeps form 5.
-int dt_algo(const lg_ctx* h, int n, int H, int W) {
-    const bool sweep_ok = W <= 2048 && H >= 16 && W >= 16;
-    if (h->opt_dt_algo == 6 && sweep_ok) return 6;
-    if (h->opt_dt_algo >= 5 && (H < 16 || W < 16)) return 1;   // (form 5's seed rows need the room of sixteen rows and columns)
-    if (h->opt_dt_algo == 6) return 5;   // (wider than 2048 columns)
-    if (h->opt_dt_algo) return h->opt_dt_algo;
-    if ((long long)n * H * W <= 64ll * 1080 * 1920) return 1;
-    if (sweep_ok) return 6;   // (profiles/NOTES_dt_sweep.md)
-    return (H < 16 || W < 16) ? 2 : 5;   // seed pairs + stencil bands instead of anchors + searched bands (profiles/NOTES_dt_bands.md)
-}
 
 // frame-border maxima of d_out + stem bits: both read only the bit rows, neither is needed before the plane kernel
 int enq_tail(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
@@ -965,20 +953,23 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
             ProfScope ps(h, "dt_hrun", ss);
             lg_launch_hrun(h->bits + off * words, h->tmp + 2 * off * px, h->win + off, n, pl.H, pl.W, pl.WW, ss);
         }
-        const int algo = dt_algo(h, n, pl.H, pl.W);
-        h->last_dt_algo = algo;
-        auto launch = [&](int phase) {
-            return lg_launch_dtsearch(phase, algo, h->bits + off * words, h->tmp + 2 * off * px, pl.maps[LG_MAP_DISTANCE] + off * px,
-                                      h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, pl.WW, ss, h->opt_dt_band_p,
-                                      h->opt_dt_band_e);
-        };
+        const int form = lg_dt_form(h->opt_dt_algo, n, pl.H, pl.W);
+        h->last_dt_algo = form;
+        const unsigned long long* bits = h->bits + off * words;
+        uint32_t *tmp = h->tmp + 2 * off * px, *maxfix = h->maxfix + LG_MF * (size_t)off;
+        float* dist = pl.maps[LG_MAP_DISTANCE] + off * px;
+        const LgWin* win = h->win + off;
         {
-            ProfScope ps(h, "dt_search", ss);   // the one-level search, the anchor rows, or the whole box by the register sweep
-            launch(0);
+            ProfScope ps(h, "dt_search", ss);   // the one-level search, the seed rows, or the whole box by the register sweep
+            switch (form) {
+                case LG_DT_FORM_BANDS: lg_launch_dt_seeds(bits, tmp, dist, maxfix, win, n, pl.H, pl.W, pl.WW, h->opt_dt_band_p, ss); break;
+                case LG_DT_FORM_SWEEP: lg_launch_dt_sweep(tmp, dist, maxfix, win, n, pl.H, pl.W, ss); break;
+                default: lg_launch_dt_rows(bits, tmp, dist, maxfix, win, n, pl.H, pl.W, pl.WW, ss); break;
+            }
         }
-        if (algo != 1 && algo != 6) {
-            ProfScope ps(h, "dt_band", ss);     // the rows between the anchors
-            for (int phase = 1; launch(phase) > 0; phase++) {}
+        if (form == LG_DT_FORM_BANDS) {
+            ProfScope ps(h, "dt_band", ss);     // the rows between the seed pairs
+            lg_launch_dt_bands(bits, tmp, dist, maxfix, win, n, pl.H, pl.W, pl.WW, h->opt_dt_band_p, h->opt_dt_band_e, ss);
         }
         if (ss != s) LG_HIP(h, hipEventRecord(h->ev_search, ss));
     }

@@ -413,25 +413,6 @@ void lg_launch_export_rows(const unsigned long long* bits, const LgWin* wins, un
 // plan (lg_make_stem_plan of se) nested and wins given: the nested-span kernel on the frames' bounding boxes; else the per-row kernel
 void lg_launch_stem_bits(const unsigned long long* bits, unsigned long long* stem, const LgWin* wins, int B, int H, int W, int WW,
                          int bottom_start, const LgSeSpans& se, const LgStemPlan* plan, hipStream_t s);
-// columns per sweep wave / waves per sweep workgroup for width W (0 if unsupported)
-int lg_dt_geometry(int W, int* waves);
-// search_mode: 0 = d_in by the two sweeps for every frame, 1 = by the row search wherever it applies (a non-empty mask with
-// at least one zero pixel), 2 = the row search when the batch's estimated search work stays below the sweeps' latency
-// mf: what lg_launch_pack_bits / lg_launch_pack_labels accumulated on the same stream
-void lg_launch_window(const uint32_t* mf, LgWin* win, int B, int H, int W, int search_mode, hipStream_t s);
-// d_in without the row-sequential sweeps (frames with LgWin::search_in): horizontal run distances of the bounding-box rows into
-// `tmp` (the d_in half of the sweep workspace, as uint16), then the bounded search over rows, which writes distance_map inside
-// the window and the maximum into maxfix[b][0]
-void lg_launch_hrun(const unsigned long long* bits, uint32_t* tmp, const LgWin* win, int B, int H, int W, int WW, hipStream_t s);
-// algo 1: one-level search (phase 0 only); algo 2: phase 0 = anchor rows (every 8th), phase 1 = the rows between them;
-// algo 5 (H, W >= 16): phase 0 = pairs of adjacent rows every band_p rows, phase 1 = the rows between them by stencil sweeps
-int lg_launch_dtsearch(int phase, int algo, const unsigned long long* bits, uint32_t* tmp, float* dist_out, uint32_t* maxfix,
-                       const LgWin* win, int B, int H, int W, int WW, hipStream_t s, int band_p = 16, int band_e = 4);
-int lg_launch_dt(bool bwd, const uint8_t* mask, uint32_t* tmp, float* dist_out, uint32_t* maxfix, const LgWin* win, int B,
-                 int H, int W, uint32_t init0, hipStream_t s);   // init0: lg_params.chamfer_init_dist0 (frames without a zero pixel)
-// max d_out outside the sweep windows (closed-form chamfer norm on the frame border) -> atomicMax into maxfix[b][1]
-void lg_launch_dout_border(const unsigned long long* bits, const LgWin* win, uint32_t* maxfix, int B, int H, int W, int WW,
-                           hipStream_t s);
 void lg_launch_final(const LgFinalArgs& a, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // Near tiles of a batch, in front of the near launch of lg_final_kernel (LgFinalArgs::near_off): near_off[b] = near tiles of the
 // frames before b (exclusive scan of lg_near_tiles over win[0 .. B), near_off[B] = their total), and every FAR tile's constant

@@ -254,7 +254,8 @@ class GraspPointSelector:
 
     def dt_search_form(self):
         """Inspection: the form of the row search the last call queued for its searched frames (dt_form(i)[0]), in
-        LG_DT_SEARCH_ALGO's numbering: 1, 2 (3, 4 when forced), 5, or 6 = one register sweep per frame; 0: no search is queued."""
+        LG_DT_SEARCH_ALGO's numbering: 1 = one level, 5 = seed row pairs + stencil bands, 6 = one register sweep per frame; 0: no
+        search is queued."""
         import ctypes as C
         algo = C.c_int32()
         rc = lib.lg_debug_dt_search_form(self._h, C.byref(algo))

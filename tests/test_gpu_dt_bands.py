@@ -1,5 +1,5 @@
 """Form 5 of the sweep-free distance transform (LG_DT_SEARCH_ALGO=5): pairs of adjacent rows every P rows by the bounded row
-search (lg_dtanchor_kernel<4, P, true>), the rows between two pairs by the 5 x 5 chamfer stencil run downwards and upwards in
+search (lg_dtseed_kernel<P>), the rows between two pairs by the 5 x 5 chamfer stencil run downwards and upwards in
 registers (lg_dtband_kernel<P, E>; the identities: tests/test_dt_band_math.py).  Every built P -- and both column counts per
 lane -- must give the oracle's two-pass transform bit for bit: distance_map, max d_in and max d_out.  The shapes are the
 smallest that reach every path: widths that are no multiple of 4 (the scalar loads and stores) and multiples of 4 (the vector

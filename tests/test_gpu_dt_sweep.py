@@ -19,12 +19,11 @@ SHAPES = [(96, 128), (131, 258), (150, 333), (40, 520), (24, 1030), (24, 2048), 
 SCALE = np.float32(1.0 / 65536.0)
 
 
-@pytest.fixture(scope="module")
-def sel():
+def _selector(algo):
     import leafgrasp_amd as L
 
     assert torch.cuda.is_available()
-    env = {"LG_DT_SEARCH": "1", "LG_DT_SEARCH_ALGO": "6"}
+    env = {"LG_DT_SEARCH": "1", "LG_DT_SEARCH_ALGO": algo}
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:   # the options are read when a handle is created
@@ -37,6 +36,11 @@ def sel():
             else:
                 os.environ[k] = v
     return s
+
+
+@pytest.fixture(scope="module")
+def sel():
+    return _selector("6")
 
 
 def _shape_masks(H, W):
@@ -166,3 +170,26 @@ def test_stale_workspace_a_large_leaf_then_a_small_one(sel, cases):
     for n in ("3 % holes", "box of one pixel", "ring", "box of 1 rows", "leaf on the left border", "box of one column"):
         assert _check(sel, per, [n]) == 1
         assert sel.dt_search_form() == 6
+
+
+def test_a_retired_form_number_is_ignored(cases):
+    """LG_DT_SEARCH_ALGO=3 named the two-level search, which the library no longer has: the value leaves the default, a batch
+    this small takes form 1, and the results are the oracle's."""
+    s3 = _selector("3")
+    assert _check(s3, cases[(40, 520)], ["ring", "concave C", "3 % holes"]) == 3
+    assert s3.dt_search_form() == 1
+
+
+@pytest.mark.parametrize("algo", ["5", "6"])
+def test_forms_5_and_6_on_a_frame_lower_than_sixteen_rows_take_form_1(algo):
+    """The seed rows of form 5 and the row registers of form 6 need the room of sixteen rows and columns."""
+    H, W = 12, 40
+    per = {}
+    for n, m in _shape_masks(H, W).items():
+        if n in ("ring", "3 % holes", "lattice of zero pixels", "leaf in the last corner", "box of 2 rows"):
+            d, fix = O.distance_transform(m, 5, return_fix=True)
+            per[n] = (m, d, fix.max(), O.distance_transform(1 - m, 5).max())
+    assert len(per) == 5
+    s = _selector(algo)
+    assert _check(s, per, list(per)) == 5
+    assert s.dt_search_form() == 1

@@ -1,6 +1,6 @@
-# Counters of the distance-transform search kernels (lg_hrun / lg_dtsearch / lg_dtanchor / lg_dtband) in one bench pass:
-#   bash tools/pmc_dt.sh <tag> [LG_DT_SEARCH mode] [LG_DT_SEARCH_ALGO]
-TAG=${1:-a}; MODE=${2:-1}; ALGO=${3:-2}
+# Counters of the distance-transform search kernels (lg_hrun / lg_dtsearch / lg_dtseed / lg_dtband / lg_dtsweep) in one bench pass:
+#   bash tools/pmc_dt.sh <tag> [LG_DT_SEARCH mode] [LG_DT_SEARCH_ALGO: 1 rows, 5 seed pairs + bands, 6 register sweep, 0 by size]
+TAG=${1:-a}; MODE=${2:-1}; ALGO=${3:-5}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_dt
 mkdir -p $OUT && cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 export LG_DT_SEARCH=$MODE LG_DT_SEARCH_ALGO=$ALGO
