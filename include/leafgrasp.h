@@ -335,8 +335,11 @@ int lg_midrib_walk(const uint8_t* enhanced, const uint8_t* mask, int H, int W, i
                         [y-16,y+16) x [x-16,x+16) of depth / mask / the seven score planes maps[0..6] of ONE frame around
                         n points xy [n][2] DEVICE, rotated by rot[i] quarter turns (torch.rot90; rot may be NULL).
                         out_depth, out_mask [n][32][32], out_scores [n][7][32][32] f32 DEVICE; flags [n] int32 DEVICE:
-                        bit 0 non-finite depth, 1 empty mask patch, 2 non-finite score, 3 window outside the frame
-                        (_check_boundaries :83-89; nothing written).
+                        bit 0 non-finite depth, 1 empty mask patch, 2 non-finite score, 3 window outside the frame:
+                        set alone, nothing written for that point.  A window is inside iff 16 <= x <= W-16 and
+                        16 <= y <= H-16, where the slices of :103-104 are full -- the far edge is inclusive.  This is
+                        NOT _check_boundaries :83-89 (x >= W-16 refused), which collect_sample applies to the
+                        positive point only; negatives go straight to _extract_patches.
    lg_negative_masks    the regions negatives are drawn from: tip = (dilate5x5(distance_map) == distance_map) & mask
                         (_get_tip_points :426-443), stem = the mask's bottom quarter eroded twice by the 5x5 ellipse
                         (_get_stem_points :445-460); u8 [H][W] DEVICE each.

@@ -1795,7 +1795,10 @@ __global__ __launch_bounds__(256) void lg_harvest_kernel(const float* __restrict
     const int k = rot ? (rot[i] & 3) : 0;
     if (t == 0) { s_flag = 0; s_any = 0; }
     __syncthreads();
-    if (px < 16 || py < 16 || px + 16 > W || py + 16 > H) {   // _check_boundaries :83-89
+    // the reference's slices [y-16:y+16, x-16:x+16] (:103-104) are full for 16 <= x <= W-16, 16 <= y <= H-16: the far
+    // edge is inclusive, unlike _check_boundaries :83-89, which collect_sample applies to the positive point only.
+    // (compared as px > W - 16: px + 16 would wrap for a coordinate near INT_MAX and let the window through)
+    if (px < 16 || py < 16 || px > W - 16 || py > H - 16) {
         if (t == 0) flags[i] = 8;
         return;
     }

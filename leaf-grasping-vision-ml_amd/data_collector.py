@@ -9,8 +9,10 @@ format of `training_data.pt`).  What runs where:
     (cv2.findContours EXTERNAL/NONE + max contourArea of _get_edge_points :462-490; curvature test in NumPy);
   * bookkeeping, random choices (`random.uniform` / `random.sample` in the reference's order), saving: Python.
 Differences a maintainer should know: patch_size must be 32 (the kernel's window); tensors must live on the HIP device;
-`scores['distance_map']` is used as the distance transform of the mask (the reference recomputes the same transform with
-cv2.distanceTransform); samples are kept on the CPU; `load_existing_data` uses torch.load(weights_only=True).
+the tip points come from the distance transform of the mask, recomputed on the device per `collect_sample` like the
+reference's cv2.distanceTransform (`scores['distance_map']` only fills the patches); a window is taken wherever the
+reference's slices are full, 16 <= x <= W-16 and 16 <= y <= H-16, while `_check_boundaries` (far edge exclusive) guards
+the positive point only; samples are kept on the CPU; `load_existing_data` uses torch.load(weights_only=True).
 """
 import ctypes as C
 import os
@@ -269,7 +271,7 @@ class EnhancedGraspDataCollector:
 
     def _get_tip_points(self, mask, dist=None):
         """Local maxima of the distance transform (5x5), on the mask, sorted by distance, top quarter.  `dist` is the
-        chamfer-5 distance transform of `mask` (scores['distance_map']); computed on the fly when omitted."""
+        chamfer-5 distance transform of `mask`; computed on the device when omitted, as collect_sample does."""
         try:
             m = (torch.as_tensor(mask).to(self.device) != 0).to(torch.uint8).contiguous()
             if dist is None:
@@ -403,8 +405,10 @@ class EnhancedGraspDataCollector:
             m, d, planes = _dev if _dev is not None else self._device_inputs(leaf_mask, depth_tensor, scores)
             max_attempts, max_negative_samples = 10, 3
             attempts = collected = 0
-            # the three point lists do not change between attempts (the reference recomputes identical lists)
-            tip_points = self._get_tip_points(m, planes[REQUIRED_SCORES.index("distance_map")])
+            # the three point lists do not change between attempts (the reference recomputes identical lists).  The tip
+            # points follow the MASK (:425 recomputes cv2.distanceTransform): scores['distance_map'] only fills the
+            # patches, whatever the caller stored in it
+            tip_points = self._get_tip_points(m)
             stem_points = self._get_stem_points(m)
             edge_points = self._get_edge_points(m)
             while collected < max_negative_samples and attempts < max_attempts:

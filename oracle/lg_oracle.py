@@ -130,17 +130,28 @@ def leaf_contour_points(mask_u8):
 
 # --------------------------------------------------------------------------- ml_grasp_optimizer/data_collector.py
 # Restatement of EnhancedGraspDataCollector's geometry helpers (cv2 calls replaced by the stand-ins above: "parity
-# unpinned" vs real OpenCV; the pure-torch / pure-Python helpers are pinned by tests/golden/collector_vectors.npz).
+# unpinned" vs real OpenCV; the pure-torch / pure-Python helpers are pinned by tests/golden/collector_vectors.npz and,
+# at the frame's edges, tests/golden/collector_edges.npz).
 SCORE_KEYS = ("sdf_score", "approach_score", "flatness_map", "isolation_map", "distance_map", "accessibility_map",
               "stem_penalty")   # required_scores, data_collector.py:138-140
 
 
+def collector_check_boundaries(x, y, shape, half_size=16):
+    """_check_boundaries (:83-89): the far edge is EXCLUSIVE (x >= W - h is refused).  collect_sample (:203) applies it
+    to the positive point only; the negatives of :332 go straight to _extract_patches."""
+    return not (y < half_size or y >= shape[0] - half_size or x < half_size or x >= shape[1] - half_size)
+
+
 def collector_extract_patches(x, y, mask, depth, scores, patch_size=32, k=0):
     """_extract_patches (:91-173) + _rotate_tensor (:395-398): raw slices [y-h:y+h, x-h:x+h], rotated k quarter turns.
-    Returns (depth [P,P], mask [P,P] float, scores [7,P,P]) or None like the reference's validation."""
+    Returns (depth [P,P], mask [P,P] float, scores [7,P,P]) or None like the reference's validation.  The window rule
+    is that of the slices (:103-117): they are PxP for h <= x <= W - h and h <= y <= H - h, far edge INCLUSIVE, and
+    empty or short just outside (pinned by tests/golden/collector_edges.npz).  Coordinates below zero, which Python
+    slices would wrap, never reach the reference's method (:185 refuses them, the negatives are pixels of the mask)
+    and are refused here."""
     h = patch_size // 2
     H, W = mask.shape
-    if y < h or y >= H - h or x < h or x >= W - h:      # _check_boundaries :83-89 (note: >= H - h excludes y = H - h)
+    if x < h or x > W - h or y < h or y > H - h:
         return None
     d = np.asarray(depth)[y - h:y + h, x - h:x + h].astype(np.float32)
     m = (np.asarray(mask)[y - h:y + h, x - h:x + h] != 0).astype(np.float32)
