@@ -105,7 +105,12 @@ typedef struct lg_params {
                                                        (2147483647; revisions that lifted the 8192-pixel ceiling).  The pinned
                                                        opencv-python 4.10.0.84 is absent here: parity unpinned.
                                                        Range [INT_MAX >> 2, INT_MAX] */
-    int32_t reserved_;                              /* 0 */
+    int32_t label_aware;                            /* 0 (default): the reference as written -- _calculate_isolation_score and
+                                                       calculate_pre_grasp_point see the one leaf they were handed (DESIGN 2 quirks 1
+                                                       and 14).  1: both see the OTHER leaves of the label image, as their comments
+                                                       promise; only lg_select_grasp_labels / lg_select_grasp_candidates_labels take
+                                                       it (see there), every entry without a label image returns LG_ERR_INVALID.
+                                                       Any other value: LG_ERR_INVALID */
 } lg_params;
 
 /* Raw GraspPointCNN(in_channels=9, attention_type, encoder_filters) state_dict tensors, HOST pointers,
@@ -234,7 +239,18 @@ int lg_select_grasp(lg_handle h, const float* depth, const uint8_t* mask, int B,
    by select_grasp_point (scripts/leaf_grasp_node_v3.py:118-125) with the comparison folded into the library's first pass over
    the frame.  labels [B][H][W] int16 DEVICE (the label image lg_leaf_select_batch reads), leaf_ids [B] HOST (an id no label
    carries, e.g. INT32_MIN, gives that frame an empty mask and found = 0).  Everything else as lg_select_grasp; the node's mask
-   is a torch.bool tensor: set lg_params.mask_is_bool = 1 for its behaviour at the image border. */
+   is a torch.bool tensor: set lg_params.mask_is_bool = 1 for its behaviour at the image border.
+   lg_params.label_aware = 1 (opt-in; 0 leaves every result as it was).  Per frame, with id = leaf_ids[b], current = (labels ==
+   id), others = (labels > 0) & (labels != id) (a negative label is background) and all = labels > 0:
+     isolation plane (:605-627 with `other_leaves` = others): ic / iw = others dilated by the 30 / 40 ellipses (anchor k / 2,
+       outside the frame = 0), dc / dw = cv2.distanceTransform(1 - ic / 1 - iw, DIST_L2, 3) in exact 16.16 integers, each
+       divided by its own whole-frame maximum + 1e-6 in float32, iso_w_close * sc + iso_w_wide * sw, times the height ramp,
+       times current.  A frame whose `others` is empty keeps the closed-form plane of label_aware = 0, bit for bit.
+     pre-grasp clearance (:786-815): the five probes test dilate(all, ellipse 2 * pregrasp_clearance + 1) instead of the
+       dilated current leaf -- the result row's and every ranked candidate's pre-grasp point.
+   Traditional score, validity, the candidates and the 3-D point do not read either.  The CNN sees the new channel 5: ml_score,
+   combined and the pick may change -- a model trained on the degenerate channel should be retrained on patches collected in
+   this mode.  Workspace for the mode is allocated by the first call that sets it. */
 int lg_select_grasp_labels(lg_handle h, const float* depth, const int16_t* labels, const int32_t* leaf_ids, int B, int H, int W,
                            const lg_params* p, float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid,
                            lg_grasp_result* results, void* stream);
@@ -470,6 +486,23 @@ int lg_debug_cnn_survivors(lg_handle h, int32_t* sub_frames, int32_t* n_sub, int
    it is 0 that wave stored +0.0 in every masked plane, where it is 1 a pixel off the mask got (expression) * 0, which can be
    -0.0.  0 otherwise, LG_ERR_INVALID for a bad argument. */
 int lg_debug_patch(lg_handle h, int64_t slot, float* out);
+/* lg_debug_isolation_fields: the two raw 16.16 chamfer-3 transforms of frame `frame` of the last lg_select_grasp*_labels call
+   with label_aware = 1 on this handle: dc_fix / dw_fix [H][W] HOST (either may be NULL), the transforms of 1 - ic and 1 - iw
+   over the WHOLE frame (the two raster sweeps compute every pixel), max_fix[2] their whole-frame maxima.  Returns 1 when the
+   frame had another leaf and the fields were computed, 0 when it took the closed form (nothing is written), < 0 on error (no
+   such call, or a later call reused the workspace). */
+int lg_debug_isolation_fields(lg_handle h, int frame, uint32_t* dc_fix, uint32_t* dw_fix, uint32_t max_fix[2]);
+/* Host forms of the label-aware arithmetic (no device, no handle).
+   lg_norm3_host: out[i] = N3(|dx[i]|, |dy[i]|) = (max - min) * 62587 + min * 89738, the closed-form norm of the (0.955, 1.3693)
+   chamfer mask in 16.16: on a frame with a zero pixel the two raster passes give min over the zero pixels q of N3(p - q).
+   lg_dilate_words_host: out = cv2.dilate(bits, ellipse k) on bit rows [H][WW] (bit j of word w = pixel 64 w + j; bits past W
+   are ignored and come out 0), 1 <= k <= 64 -- the per-word code of the device's whole-frame dilation. */
+/* lg_label_aware_check: the rule every entry applies to lg_params.label_aware -- LG_OK for 0, and for 1 when the entry has a
+   label image (has_labels != 0: lg_select_grasp_labels, lg_select_grasp_candidates_labels); LG_ERR_INVALID for 1 on an entry
+   that takes a mask (lg_select_grasp, lg_select_grasp_candidates, lg_score_maps) and for any other value. */
+int lg_label_aware_check(const lg_params* p, int has_labels);
+int lg_norm3_host(const int32_t* dx, const int32_t* dy, int n, uint32_t* out);
+int lg_dilate_words_host(const uint64_t* bits, int H, int W, int WW, int k, uint64_t* out);
 int lg_debug_ws_plane_bytes(lg_handle h, int64_t bytes[LG_NUM_MAPS]);
 int lg_wave_rows_on_mask(const uint64_t* bits, int H, int WW, int y, int w);
 

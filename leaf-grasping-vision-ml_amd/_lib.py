@@ -20,7 +20,7 @@ class LgParams(C.Structure):
         "sdf_w_sdf", "optimal_distance", "access_w_dist", "access_w_dir", "flat_scale", "iso_w_close",
         "iso_w_wide", "iso_ramp_top", "iso_ramp_bottom", "min_edge_distance", "stem_valid_thresh")] + \
         [(n, C.c_int32) for n in ("stem_se", "stem_bottom_div", "top_k", "nms_min_distance",
-                                  "pregrasp_clearance", "mask_is_bool", "gaussian_size", "chamfer_init_dist0", "reserved_")]
+                                  "pregrasp_clearance", "mask_is_bool", "gaussian_size", "chamfer_init_dist0", "label_aware")]
 
 
 _FP = C.POINTER(C.c_float)
@@ -137,6 +137,10 @@ SYMBOLS = {
     "lg_debug_cnn_survivors": (C.c_int, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), _FP, C.c_int64, C.POINTER(C.c_int64)]),
     "lg_debug_patch": (C.c_int, [_VP, C.c_int64, _FP]),
+    "lg_debug_isolation_fields": (C.c_int, [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_uint32)]),
+    "lg_label_aware_check": (C.c_int, [C.POINTER(LgParams), C.c_int]),
+    "lg_norm3_host": (C.c_int, [_VP, _VP, C.c_int, _VP]),
+    "lg_dilate_words_host": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "lg_debug_ws_plane_bytes": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "lg_wave_rows_on_mask": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int]),
     "lg_harvest_patches": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

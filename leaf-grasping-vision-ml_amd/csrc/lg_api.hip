@@ -74,6 +74,14 @@ struct lg_ctx {
     uint32_t* maxfix = nullptr;
     uint8_t* mask_ws = nullptr;      // lg_select_grasp_labels: the 0 / 1 mask it derives from the labels (grown on demand)
     size_t mask_ws_cap = 0;
+    // label-aware mode (lg_params.label_aware): bit rows of the other leaves [B][H][WW], their two dilations [2][B][H][WW] and
+    // the frames' LG_ISO_MF words; allocated by the first call that sets the mode, grown on demand.  The two transforms live in
+    // `tmp`, which the distance transform of the same call has finished with by then.
+    unsigned long long *iso_others = nullptr, *iso_dil = nullptr;
+    uint32_t* iso_mf = nullptr;
+    size_t iso_words_cap = 0;
+    int iso_B_cap = 0;
+    int last_iso_B = 0, last_iso_H = 0, last_iso_W = 0;   // lg_debug_isolation_fields: shape of the last label-aware call (0: none since)
     int32_t* ids_dev = nullptr;      //   and the frames' leaf ids (device / pinned host staging)
     int32_t* ids_host = nullptr;
     int ids_cap = 0;
@@ -238,7 +246,7 @@ void free_ws(lg_ctx* h) {
     for (int i = 0; i < LG_NUM_MAPS; i++) { F(h->ws_maps_base[i]); h->ws_maps_base[i] = h->ws_maps[i] = nullptr; }
     F(h->ws_valid); F(h->cand_xy); F(h->cand_n); F(h->cand_info); F(h->patches); F(h->logits);
     F(h->surv_keep); F(h->surv_list); F(h->surv_slot); F(h->surv_count);
-    F(h->near_off); h->near_off = nullptr; h->last_near_B = 0;
+    F(h->near_off); h->near_off = nullptr; h->last_near_B = 0; h->last_iso_B = 0;
     h->surv_keep = nullptr; h->surv_list = h->surv_slot = h->surv_count = nullptr;
     h->last_scored = 0; h->last_scored_subs = 0; h->last_cnn_B = 0; h->last_patch_floats = 0;
     auto HF = [](void* p) { if (p) hipHostFree(p); };
@@ -475,6 +483,9 @@ int lg_destroy(lg_handle h) {
     if (h->mask_ws) hipFree(h->mask_ws);
     if (h->ids_dev) hipFree(h->ids_dev);
     if (h->ids_host) hipHostFree(h->ids_host);
+    if (h->iso_others) hipFree(h->iso_others);
+    if (h->iso_dil) hipFree(h->iso_dil);
+    if (h->iso_mf) hipFree(h->iso_mf);
     if (h->cand_rows_dev) hipFree(h->cand_rows_dev);
     if (h->cand_rows_host) hipHostFree(h->cand_rows_host);
     lg_cnn_free(&h->cnn);
@@ -803,6 +814,60 @@ int lg_debug_dt_search_form(lg_handle h, int32_t* algo) {
 
 int lg_dt_form_host(int forced, int n, int H, int W) { return lg_dt_form(forced, n, H, W); }
 
+int lg_debug_isolation_fields(lg_handle h, int frame, uint32_t* dc_fix, uint32_t* dw_fix, uint32_t max_fix[2]) {
+    if (!h || !max_fix || frame < 0) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (frame >= h->last_iso_B || !h->tmp || !h->iso_mf)
+        return fail(h, LG_ERR_INVALID, "lg_debug_isolation_fields: the last call on this workspace was not label-aware, or has no such frame");
+    hipSetDevice(h->device);
+    hipDeviceSynchronize();
+    uint32_t mf[LG_ISO_MF];
+    if (hipMemcpy(mf, h->iso_mf + LG_ISO_MF * (size_t)frame, sizeof(mf), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(h, LG_ERR_HIP, "lg_debug_isolation_fields: copy failed");
+    if (mf[2] == 0u) return 0;   // no other leaf: the closed form, no fields
+    max_fix[0] = mf[0]; max_fix[1] = mf[1];
+    const size_t px = (size_t)h->last_iso_H * h->last_iso_W;
+    uint32_t* dst[2] = {dc_fix, dw_fix};
+    for (int f = 0; f < 2; f++)
+        if (dst[f] && hipMemcpy(dst[f], h->tmp + ((size_t)frame * 2 + f) * px, sizeof(uint32_t) * px, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(h, LG_ERR_HIP, "lg_debug_isolation_fields: copy failed");
+    return 1;
+}
+
+int lg_label_aware_check(const lg_params* p, int has_labels) {
+    if (!p || (p->label_aware != 0 && p->label_aware != 1)) return LG_ERR_INVALID;
+    return (p->label_aware && !has_labels) ? LG_ERR_INVALID : LG_OK;
+}
+
+int lg_norm3_host(const int32_t* dx, const int32_t* dy, int n, uint32_t* out) {
+    if (n < 0 || (n > 0 && (!dx || !dy || !out))) return LG_ERR_INVALID;
+    for (int i = 0; i < n; i++) {
+        const int ax = dx[i] < 0 ? -dx[i] : dx[i], ay = dy[i] < 0 ? -dy[i] : dy[i];
+        if (ax > 16384 || ay > 16384) return LG_ERR_INVALID;   // (the norm of two such lengths stays below 2^32)
+        out[i] = lg_norm3(ax, ay);
+    }
+    return LG_OK;
+}
+
+int lg_dilate_words_host(const uint64_t* bits, int H, int W, int WW, int k, uint64_t* out) {
+    if (!bits || !out || H < 1 || W < 1 || WW != (W + 63) / 64 || k < 1 || k > 64) return LG_ERR_INVALID;
+    LgSeSpans se;
+    lg_make_se_spans(k, &se);
+    LgStemPlan sp;
+    lg_make_stem_plan(se, &sp);
+    // (bits past W are ignored: the source rows are taken with their last word masked)
+    std::vector<unsigned long long> src((size_t)H * WW);
+    for (int y = 0; y < H; y++)
+        for (int w = 0; w < WW; w++) {
+            unsigned long long v = (unsigned long long)bits[(size_t)y * WW + w];
+            if (w == WW - 1 && (W & 63)) v &= ~0ull >> (64 - (W & 63));
+            src[(size_t)y * WW + w] = v;
+        }
+    for (int y = 0; y < H; y++)
+        for (int w = 0; w < WW; w++) out[(size_t)y * WW + w] = lg_frame_dilate_word(src.data(), H, W, WW, y, w, se, sp);
+    return LG_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -825,6 +890,8 @@ struct Plan {  // one call's geometry, parameters and plane pointers (absolute, 
     // sdf, approach, isolation, accessibility and stem are neither allocated nor written: the gather computes them at the
     // pixels of its windows
     bool defer = false;
+    // label-aware mode (lg_params.label_aware, labels given): the bit-row pass also writes the other leaves' rows (iso_others)
+    bool label_aware = false;
 };
 
 
@@ -857,9 +924,13 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
     h->export_pending = true;
     const size_t px = (size_t)pl.H * pl.W, words = (size_t)pl.H * pl.WW;
     LG_HIP(h, hipMemsetAsync(h->maxfix + LG_MF * (size_t)off, 0, sizeof(uint32_t) * LG_MF * n, s));
+    if (pl.label_aware) LG_HIP(h, hipMemsetAsync(h->iso_mf + LG_ISO_MF * (size_t)off, 0, sizeof(uint32_t) * LG_ISO_MF * n, s));
     {
         ProfScope ps(h, "prep", s);
-        if (pl.labels)
+        if (pl.labels && pl.label_aware)   // (one sub-batch: off = 0)
+            lg_launch_pack_labels(pl.labels + off * px, h->ids_dev + off, h->mask_ws + off * px, h->bits + off * words, n, pl.H, pl.W,
+                                  pl.WW, s, h->maxfix + LG_MF * (size_t)off, h->iso_others + off * words, h->iso_mf + LG_ISO_MF * (size_t)off);
+        else if (pl.labels)
             lg_launch_pack_labels(pl.labels + off * px, h->ids_dev + off, h->mask_ws + off * px, h->bits + off * words, n, pl.H, pl.W,
                                   pl.WW, s, h->maxfix + LG_MF * (size_t)off);
         else
@@ -947,6 +1018,7 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
     // latency-bound work on one workgroup per frame.  Inside the sub-batch pipeline (whose stages own the side streams): in line.
     hipStream_t ss = (s == h->s_dt[0] || s == h->s_dt[1]) ? s : h->s_dt[1];
     h->last_dt_algo = 0;
+    h->last_iso_B = 0;   // (the sweeps' scratch held the fields of an earlier label-aware call)
     if (h->opt_dt_search) {
         if (ss != s) LG_HIP(h, hipStreamWaitEvent(ss, h->ev_prep, 0));
         {
@@ -1106,6 +1178,7 @@ int make_plan(lg_ctx* h, Plan& pl, const float* depth, const uint8_t* mask, int 
         return fail(h, LG_ERR_INVALID, "gaussian_size / 2 must be smaller than H and W (reflect padding)");
     if (pl.P.chamfer_init_dist0 < (int32_t)LG_INIT0)   // (a zeroed struct, or a value a real distance could reach)
         return fail(h, LG_ERR_INVALID, "chamfer_init_dist0 must be in [INT_MAX >> 2, INT_MAX] (lg_default_params: INT_MAX >> 2)");
+    if (lg_label_aware_check(&pl.P, 1)) return fail(h, LG_ERR_INVALID, "label_aware must be 0 or 1");
     pl.B = B; pl.H = H; pl.W = W; pl.WW = (W + 63) / 64;
     pl.tiles_x = (W + LG_TW - 1) / LG_TW; pl.tiles_y = (H + LG_TH - 1) / LG_TH;
     if (pl.tiles_x * pl.tiles_y > 8192) return fail(h, LG_ERR_UNSUPPORTED, "image too large for the top-k tile table");
@@ -1126,6 +1199,7 @@ int lg_score_maps(lg_handle h, const float* depth, const uint8_t* mask, int B, i
     Plan pl;
     int rc = make_plan(h, pl, depth, mask, B, H, W, pin, out_maps, out_valid, "lg_score_maps");
     if (rc) return rc;
+    if (lg_label_aware_check(&pl.P, 0)) return fail(h, LG_ERR_INVALID, "lg_score_maps: label_aware needs the label image (lg_select_grasp_labels, lg_select_grasp_candidates_labels)");
     hipStream_t s = (hipStream_t)stream_;
     LG_HIP(h, hipSetDevice(h->device));
     rc = ensure_ws(h, B, H, W, pl.P.top_k);
@@ -1240,6 +1314,7 @@ int lg_negative_masks(lg_handle h, const float* distance_map, const uint8_t* mas
     int rc = ensure_ws(h, 1, H, W, 20);
     if (rc) return rc;
     // scratch for the first erosion: the u8 view of the forward-sweep workspace (H*W bytes needed, 8*H*W available)
+    h->last_iso_B = 0;
     lg_launch_negative_masks(distance_map, mask, out_tip, out_stem, reinterpret_cast<uint8_t*>(h->tmp), H, W, s);
     LG_HIP(h, hipGetLastError());
     return LG_OK;
@@ -1715,6 +1790,9 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     int rc = make_plan(h, pl, depth, mask, B, H, W, pin, out_maps, out_valid, "lg_select_grasp");
     if (rc) return rc;
     pl.labels = labels;
+    if (lg_label_aware_check(&pl.P, labels ? 1 : 0))
+        return fail(h, LG_ERR_INVALID, "lg_select_grasp: label_aware needs the label image (lg_select_grasp_labels, lg_select_grasp_candidates_labels)");
+    pl.label_aware = pl.P.label_aware != 0;
     pl.sparse = !out_valid;
     for (int i = 0; i < LG_NUM_MAPS; i++) pl.sparse = pl.sparse && !pl.maps[i];
     const lg_params& P = pl.P;
@@ -1723,6 +1801,24 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     LG_HIP(h, hipSetDevice(h->device));
     rc = ensure_ws(h, B, H, W, P.top_k);
     if (rc) return rc;
+    h->last_iso_B = 0;   // (this call's distance transform overwrites the fields of an earlier label-aware call)
+    if (pl.label_aware) {   // workspace of the mode: on the first call that asks for it
+        const size_t words = (size_t)B * H * pl.WW;
+        if (words > h->iso_words_cap || B > h->iso_B_cap) {
+            hipDeviceSynchronize();
+            if (h->iso_others) hipFree(h->iso_others);
+            if (h->iso_dil) hipFree(h->iso_dil);
+            if (h->iso_mf) hipFree(h->iso_mf);
+            h->iso_others = h->iso_dil = nullptr; h->iso_mf = nullptr; h->iso_words_cap = 0; h->iso_B_cap = 0;
+            if (hipMalloc((void**)&h->iso_others, sizeof(unsigned long long) * words) != hipSuccess ||
+                hipMalloc((void**)&h->iso_dil, sizeof(unsigned long long) * 2 * words) != hipSuccess ||
+                hipMalloc((void**)&h->iso_mf, sizeof(uint32_t) * LG_ISO_MF * B) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(h, LG_ERR_NOMEM, "lg_select_grasp_labels: label-aware workspace");
+            }
+            h->iso_words_cap = words; h->iso_B_cap = B;
+        }
+    }
     if (cands && (size_t)B * P.top_k > h->cand_rows_cap) {   // candidate rows: on the first call that asks for them
         if (h->cand_rows_dev) { hipDeviceSynchronize(); hipFree(h->cand_rows_dev); h->cand_rows_dev = nullptr; }
         if (h->cand_rows_host) { hipHostFree(h->cand_rows_host); h->cand_rows_host = nullptr; }
@@ -1767,7 +1863,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     // Measured on MI355X (B=128, 1080p): SB=32 is 14.8 ms/step vs 11.5 ms unpiped -- the chain
     // D(0)->F(0)->T(0) must drain before the first CNN launch, and D's latency does not shrink with SB.
     // Kept for experiments (LG_SUBBATCH=n in the environment when the handle is created); the default is one sub-batch.
-    if (h->opt_subbatch > 0) SB = h->opt_subbatch;
+    if (h->opt_subbatch > 0 && !pl.label_aware) SB = h->opt_subbatch;   // (the label-aware transforms reuse the sweeps' scratch: one sub-batch)
     const int nsub = (B + SB - 1) / SB;
     const bool piped = nsub > 1;
     std::vector<LgFinalArgs> fargs((size_t)nsub);   // the plane launches' arguments, for the deferred gather
@@ -1785,6 +1881,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         LG_HIP(h, hipEventRecord(h->ev_begin, s));
         for (hipStream_t q : {sD[0], sD[1], sM, sT}) LG_HIP(h, hipStreamWaitEvent(q, h->ev_begin, 0));
     }
+    const LgIsoFields iso_fields = {h->tmp, h->iso_mf};   // (label-aware mode; one sub-batch: frame 0 of the call)
     auto enq_G = [&](int k) -> int {
         const int off = k * SB, n = std::min(SB, B - off);
         if (piped) LG_HIP(h, hipStreamWaitEvent(sM, EV(k, 4), 0));
@@ -1803,7 +1900,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
                 lg_launch_gather(depth + off * px, mask + off * px, mp, pl.sparse ? h->tile_state + (size_t)off * tiles : nullptr,
                                  P.flat_scale, n, H, W, K, h->cand_xy + (size_t)off * K * 2,
                                  h->cand_n + off, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, sM, list, count,
-                                 pl.defer ? &fargs[k] : nullptr);
+                                 pl.defer ? &fargs[k] : nullptr, pl.label_aware ? &iso_fields : nullptr);
             }
             std::string err;
             hipStream_t sC = sM;
@@ -1843,6 +1940,20 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         if (rc) return rc;
         if (piped) LG_HIP(h, hipEventRecord(EV(k, 2), sD[k & 1]));
     }
+    if (pl.label_aware) {
+        // others -> two dilations -> two chamfer-3 transforms, behind the distance transform on the caller's stream: the fields
+        // take the sweeps' scratch (h->tmp, [B][2][H][W] words), free from here on.  A frame without another leaf is skipped
+        // by every kernel.
+        {
+            ProfScope ps(h, "iso_dilate", s);
+            lg_launch_iso_dilate(h->iso_others, h->iso_dil, h->iso_mf, B, H, W, pl.WW, s);
+        }
+        {
+            ProfScope ps(h, "iso_sweeps", s);
+            if (lg_launch_iso_sweeps(h->iso_dil, h->tmp, h->iso_mf, B, H, W, pl.WW, (uint32_t)P.chamfer_init_dist0, s))
+                return fail(h, LG_ERR_UNSUPPORTED, "label_aware: width");
+        }
+    }
     if (trace && !piped) hipEventRecord(tev[1], s);   // after the sweeps
     const double t_enq1 = now();
     const double t_copy = now();
@@ -1855,6 +1966,11 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         if (piped) LG_HIP(h, hipStreamWaitEvent(sM, EV(k, 2), 0));
         rc = enq_final(h, pl, off, n, sM, upload_fp, &fargs[k]);
         if (rc) return rc;
+        if (pl.label_aware && pl.maps[LG_MAP_ISOLATION]) {   // stored plane (dense calls, LG_DEFER_PLANES=0): the current leaf's pixels
+            ProfScope ps(h, "iso_plane", sM);
+            lg_launch_iso_plane(iso_fields, h->bits, h->win, pl.maps[LG_MAP_ISOLATION], B, H, W, pl.WW, P.iso_w_close, P.iso_w_wide,
+                                fargs[k].iso_ramp_top, fargs[k].iso_ramp_step, sM);
+        }
         if (trace && !piped) hipEventRecord(tev[2], s);   // after the fused planes
         if (piped) {
             LG_HIP(h, hipEventRecord(EV(k, 3), sM));
@@ -1890,6 +2006,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         memset(&fa, 0, sizeof(fa));
         fa.cand_n = h->cand_n; fa.cand_xy = h->cand_xy; fa.cand_info = h->cand_info; fa.logits = h->logits;
         fa.slot = prune ? h->surv_slot : nullptr; fa.slot_frames = SB;
+        fa.bits2 = pl.label_aware ? h->iso_others : nullptr;
         fa.fp = h->fp_dev; fa.bits = h->bits; fa.out = h->res_host_dev ? h->res_host_dev : h->res_dev;
         fa.B = B; fa.H = H; fa.W = W; fa.WW = pl.WW; fa.K = K; fa.use_cnn = use_cnn ? 1 : 0; fa.mask_is_bool = P.mask_is_bool;
         fa.cx = P.cx; fa.cy = P.cy; fa.f = P.f;
@@ -1918,6 +2035,7 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     if (use_cnn) { h->last_cnn_B = B; h->last_cnn_K = K; h->last_cnn_SB = SB; h->last_cnn_pruned = prune; }
     h->last_patch_floats = use_cnn ? (long long)B * K * lg_cnn_halo_patch_floats() : 0;
     if (pl.near) h->last_near_B = B;
+    if (pl.label_aware) { h->last_iso_B = B; h->last_iso_H = H; h->last_iso_W = W; }
     if (trace && !piped) {
         float a[5] = {0};
         for (int i = 1; i <= 4; i++) hipEventElapsedTime(&a[i], tev[0], tev[i]);

@@ -344,6 +344,39 @@ __host__ __device__ inline unsigned long long lg_stem_word_chain(const unsigned 
     }
     return out;
 }
+// ---- label-aware mode (lg_params.label_aware; lg_iso.hip)
+// Closed-form norm of the (0.955, 1.3693) chamfer mask: with a zero pixel in the image, the two 3x3 raster passes of
+// cv2.distanceTransform give min over the zero pixels q of lg_norm3(|p - q|) (a <= b <= 2a: a diagonal step never loses against
+// two straight ones, and never beats one).  The device runs the raster passes themselves (lg_iso_sweep_kernel), whose integers
+// are OpenCV's by construction; the norm is the independent statement of their result that the CPU tests hold to the oracle.
+__host__ __device__ inline uint32_t lg_norm3(int dx, int dy) {
+    const uint32_t a = (uint32_t)(dx > dy ? dx : dy), b = (uint32_t)(dx > dy ? dy : dx);
+    return (a - b) * LG_A3 + b * LG_B3;
+}
+// One word of cv2.dilate(frame, ellipse) on bit rows: the stem code with the whole frame as its bottom region (the source-row
+// fetch then zeroes only the rows outside the frame), by the chains when the spans are nested.  last_mask: the valid bits of
+// the row's last word (the dilation of a pixel near the right border reaches past W; there is no pixel there).
+// lg_iso_dilate_kernel and the host export lg_dilate_words_host run this code.
+__host__ __device__ inline unsigned long long lg_frame_dilate_word(const unsigned long long* fb, int H, int W, int WW, int y, int w,
+                                                                   const LgSeSpans& se, const LgStemPlan& pl) {
+    unsigned long long o = pl.nested ? lg_stem_word_chain(fb, H, WW, 0, y, w, se, pl) : lg_stem_word_rows(fb, H, WW, 0, y, w, se);
+    if (w == WW - 1 && (W & 63)) o &= ~0ull >> (64 - (W & 63));
+    return o;
+}
+// Words per frame of the label-aware mode's `iso_mf` array (zeroed in front of the bit-row pass): [0], [1] whole-frame maxima
+// of the two chamfer-3 transforms (atomicMax), [2] != 0: the frame has a pixel of another leaf, [3] unused
+#define LG_ISO_MF 4
+// isolation of one pixel of the current leaf from the two transforms (oracle lines 401, 404-408 in order and type: float32
+// transforms, max + 1e-6 in float32 as numpy adds a Python float to a float32 scalar, the weighted sum in float32)
+__host__ __device__ inline float lg_iso_value(uint32_t dc_fix, uint32_t dw_fix, uint32_t maxc, uint32_t maxw, float w_close,
+                                              float w_wide, float ramp) {
+#pragma clang fp contract(off)
+    const float k = 1.0f / 65536.0f;
+    const float sc = ((float)dc_fix * k) / ((float)maxc * k + 1e-6f);
+    const float sw = ((float)dw_fix * k) / ((float)maxw * k + 1e-6f);
+    return (w_close * sc + w_wide * sw) * ramp;
+}
+
 // Rows and words of a frame's stem plane that can be non-zero: the words of the mask's bounding box in the rows from which
 // the ellipse reaches the bottom region.  *ya > *yb: none.
 struct LgStemRect { int ya, yb, w0, w1; };   // rows [ya, yb], words [w0, w1], inclusive
@@ -406,8 +439,11 @@ struct LgFinalArgs {
 void lg_launch_pack_bits(const uint8_t* mask, unsigned long long* bits, int B, int H, int W, int WW, hipStream_t s,
                          uint32_t* mf = nullptr);
 // mask[b] = labels[b] == ids[b] (0 / 1 bytes) and its bit rows in one pass (ids: DEVICE, one per frame)
+// others / iso_mf (label-aware mode; both or neither): also the bit rows of others[b] = labels[b] > 0 && labels[b] != ids[b], in
+// the same read of the labels, and iso_mf[b * LG_ISO_MF + 2] != 0 for a frame that has such a pixel (iso_mf zeroed by the caller)
 void lg_launch_pack_labels(const int16_t* labels, const int32_t* ids_dev, uint8_t* mask, unsigned long long* bits, int B, int H,
-                           int W, int WW, hipStream_t s, uint32_t* mf = nullptr);
+                           int W, int WW, hipStream_t s, uint32_t* mf = nullptr, unsigned long long* others = nullptr,
+                           uint32_t* iso_mf = nullptr);
 void lg_launch_export_rows(const unsigned long long* bits, const LgWin* wins, unsigned long long* dst_host_devptr, int B,
                            int H, int WW, hipStream_t s);
 // plan (lg_make_stem_plan of se) nested and wins given: the nested-span kernel on the frames' bounding boxes; else the per-row kernel
@@ -437,7 +473,28 @@ void lg_launch_topk(const float* trad, const uint8_t* valid, const float* depth,
 void lg_launch_gather(const float* depth, const uint8_t* mask, const float* const* maps_dev, const uint8_t* tile_state,
                       float flat_scale, int B, int H, int W, int k, const int32_t* xy, const int32_t* n, float* patches,
                       bool haloed, hipStream_t s, const int32_t* list = nullptr, const int32_t* count = nullptr,
-                      const LgFinalArgs* defer = nullptr);
+                      const LgFinalArgs* defer = nullptr, const struct LgIsoFields* iso = nullptr);
+
+// ---- label-aware isolation (lg_iso.hip), every launch over the frames [0, B) of its pointers
+// The two transforms of a batch and where the deferred gather / the plane kernel find them.  A frame with iso_mf[.. + 2] == 0
+// (no other leaf) is skipped by every kernel: its plane stays the closed form.
+struct LgIsoFields {
+    const uint32_t* fields;   // [B][2][H][W] 16.16 transforms of 1 - ic (0) and 1 - iw (1)
+    const uint32_t* iso_mf;   // [B][LG_ISO_MF]
+};
+// the generic-width companion of lg_launch_pack_labels: others' bit rows and flag alone, one wave ballot per word
+void lg_launch_pack_others(const int16_t* labels, const int32_t* ids_dev, unsigned long long* others, uint32_t* iso_mf, int B, int H,
+                           int W, int WW, hipStream_t s);
+// dil[0][b] = dilate(others[b], ellipse 30), dil[1][b] = dilate(others[b], ellipse 40) as bit rows (dil: [2][B][H][WW])
+void lg_launch_iso_dilate(const unsigned long long* others, unsigned long long* dil, const uint32_t* iso_mf, int B, int H, int W, int WW,
+                          hipStream_t s);
+// The 3x3 raster passes of cv2.distanceTransform(1 - dil[f][b], DIST_L2, 3) into fields[b][f], forward then backward (two
+// launches), and the whole-frame maxima into iso_mf[b][f].  0: queued, -1: width not supported (W > 8192)
+int lg_launch_iso_sweeps(const unsigned long long* dil, uint32_t* fields, uint32_t* iso_mf, int B, int H, int W, int WW, uint32_t init0,
+                         hipStream_t s);
+// dense planes: isolation[b] on the pixels of the current leaf (bit rows `bits`, bounding boxes `win`) from the fields
+void lg_launch_iso_plane(const LgIsoFields& f, const unsigned long long* bits, const LgWin* win, float* iso, int B, int H, int W, int WW,
+                         float w_close, float w_wide, float ramp_top, float ramp_step, hipStream_t s);
 
 // The host half of select_grasp_point on the device (lg_finish_kernel): CNN rescoring of the candidates, 3-D point, pre-grasp point
 struct LgFinishArgs {
@@ -449,6 +506,8 @@ struct LgFinishArgs {
     int slot_frames;              //   slots count from the first patch of the candidate's sub-batch of this many frames
     const LgFrameParams* fp;      // [B] (theta)
     const unsigned long long* bits;   // [B][H][WW] mask bit rows
+    const unsigned long long* bits2;  // null, or (label-aware mode) [B][H][WW] bit rows of the other leaves: the pre-grasp probes
+                                      //   test bits | bits2 = every leaf of the label image
     lg_grasp_result* out;         // [B] DEVICE
     int B, H, W, WW, K, use_cnn, mask_is_bool;
     double cx, cy, f;

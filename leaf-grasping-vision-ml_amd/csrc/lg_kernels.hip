@@ -196,9 +196,14 @@ void lg_launch_pack_bits(const uint8_t* mask, unsigned long long* bits, int B, i
 // [B][H][W] int16 and one leaf id per frame in, the 0 / 1 byte mask (what the sweeps and the patch gather read) and the bit rows
 // out.  One pass over the labels instead of torch's comparison (labels in, mask out) + lg_pack_bits (mask in).  A lane takes 16
 // labels (two 16-byte loads), four adjacent lanes assemble a word; W % 16 == 0 (the launcher falls back otherwise).
+// OTHERS (label-aware mode; false: the code as it was, the two extra arguments unused): the same labels also give the bit rows
+// of the other leaves, label > 0 && label != id, and the frame's "has another leaf" word (iso_mf[.. + 2], one atomic per wave
+// that saw one).
+template <bool OTHERS>
 __global__ __launch_bounds__(256) void lg_pack_labels16_kernel(const int16_t* __restrict__ labels, const int32_t* __restrict__ ids,
                                                                uint8_t* __restrict__ mask, unsigned long long* __restrict__ bits,
-                                                               int H, int W, int WW, uint32_t* __restrict__ mf) {
+                                                               int H, int W, int WW, uint32_t* __restrict__ mf,
+                                                               unsigned long long* __restrict__ others, uint32_t* __restrict__ iso_mf) {
     __shared__ uint32_t s_box[5];
     const int slots_per_row = 4 * WW, frame = blockIdx.y;
     const int nslots = H * slots_per_row;                        // of one frame; a multiple of 4
@@ -207,12 +212,13 @@ __global__ __launch_bounds__(256) void lg_pack_labels16_kernel(const int16_t* __
     unsigned long long* fb = bits + (size_t)frame * H * WW;
     const int id = ids[frame];
     LgBoxAcc acc;
+    unsigned o_any = 0;
     const int stride = gridDim.x * 256;  // multiple of 4: a word's four slots stay in adjacent lanes
     for (int sid = blockIdx.x * 256 + threadIdx.x; sid < nslots; sid += stride) {
         const int row = sid / slots_per_row;
         const int slot = sid - row * slots_per_row;
         const int x = slot * 16;
-        unsigned b16 = 0;
+        unsigned b16 = 0, o16 = 0;
         if (x < W) {
             const uint4 v0 = *reinterpret_cast<const uint4*>(fl + (size_t)row * W + x);
             const uint4 v1 = *reinterpret_cast<const uint4*>(fl + (size_t)row * W + x + 8);
@@ -222,6 +228,10 @@ __global__ __launch_bounds__(256) void lg_pack_labels16_kernel(const int16_t* __
             for (int q = 0; q < 8; q++) {
                 const unsigned lo = (int)(int16_t)(w8[q] & 0xffffu) == id ? 1u : 0u, hi = (int)(int16_t)(w8[q] >> 16) == id ? 1u : 0u;
                 b16 |= (lo | (hi << 1)) << (2 * q);
+                if constexpr (OTHERS) {
+                    const int l0 = (int)(int16_t)(w8[q] & 0xffffu), l1 = (int)(int16_t)(w8[q] >> 16);
+                    o16 |= ((l0 > 0 && l0 != id ? 1u : 0u) | (l1 > 0 && l1 != id ? 2u : 0u)) << (2 * q);
+                }
                 const uint32_t two = lo | (hi << 8);
                 if (q & 1) mb[q >> 1] |= two << 16; else mb[q >> 1] = two;
             }
@@ -232,8 +242,18 @@ __global__ __launch_bounds__(256) void lg_pack_labels16_kernel(const int16_t* __
         word |= __shfl_xor(word, 1, 64);
         word |= __shfl_xor(word, 2, 64);
         if ((slot & 3) == 0) fb[(size_t)row * WW + (slot >> 2)] = word;
+        if constexpr (OTHERS) {
+            unsigned long long ow = (unsigned long long)o16 << (16 * (slot & 3));
+            ow |= __shfl_xor(ow, 1, 64);
+            ow |= __shfl_xor(ow, 2, 64);
+            if ((slot & 3) == 0) others[((size_t)frame * H + row) * WW + (slot >> 2)] = ow;
+            o_any |= o16;
+        }
     }
     if (mf) lg_box_flush(acc, s_box, mf + (size_t)frame * LG_MF);
+    if constexpr (OTHERS) {
+        if (__ballot(o_any != 0) != 0ull && (threadIdx.x & 63) == 0) atomicOr(&iso_mf[(size_t)frame * LG_ISO_MF + 2], 1u);
+    }
 }
 __global__ __launch_bounds__(256) void lg_labels_mask_kernel(const int16_t* __restrict__ labels, const int32_t* __restrict__ ids,
                                                              uint8_t* __restrict__ mask, long long px_per_frame, long long total) {
@@ -241,12 +261,17 @@ __global__ __launch_bounds__(256) void lg_labels_mask_kernel(const int16_t* __re
         mask[i] = (int)labels[i] == ids[i / px_per_frame] ? 1 : 0;
 }
 void lg_launch_pack_labels(const int16_t* labels, const int32_t* ids_dev, uint8_t* mask, unsigned long long* bits, int B, int H,
-                           int W, int WW, hipStream_t s, uint32_t* mf) {
+                           int W, int WW, hipStream_t s, uint32_t* mf, unsigned long long* others, uint32_t* iso_mf) {
     if ((W & 15) == 0 && ((uintptr_t)labels & 15) == 0 && ((uintptr_t)mask & 15) == 0) {
-        hipLaunchKernelGGL(lg_pack_labels16_kernel, dim3(lg_pack_blocks((long long)H * WW * 4, B, 16384), B), dim3(256), 0, s, labels,
-                           ids_dev, mask, bits, H, W, WW, mf);
+        const dim3 grid(lg_pack_blocks((long long)H * WW * 4, B, 16384), B);
+        if (others)
+            hipLaunchKernelGGL(lg_pack_labels16_kernel<true>, grid, dim3(256), 0, s, labels, ids_dev, mask, bits, H, W, WW, mf, others, iso_mf);
+        else
+            hipLaunchKernelGGL(lg_pack_labels16_kernel<false>, grid, dim3(256), 0, s, labels, ids_dev, mask, bits, H, W, WW, mf,
+                               (unsigned long long*)nullptr, (uint32_t*)nullptr);
         return;
     }
+    if (others) lg_launch_pack_others(labels, ids_dev, others, iso_mf, B, H, W, WW, s);
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(lg_labels_mask_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 16384)), dim3(256), 0, s, labels,
                        ids_dev, mask, (long long)H * W, total);
@@ -1082,6 +1107,7 @@ __device__ inline LgPoint3d lg_point_3d_pre(const LgFinishArgs& a, int b, int x,
     if (!(nrm > 0.0) || !isfinite(nrm)) return R;    // reference: exception -> None
     const double dxn = X / nrm, dyn = Y / nrm;
     const unsigned long long* fb = a.bits + (size_t)b * H * WW;
+    const unsigned long long* fb2 = a.bits2 ? a.bits2 + (size_t)b * H * WW : nullptr;   // label-aware mode: the other leaves
     bool done = false;
     for (int step = 0; step < 5 && !done; step++) {
         // np.arange(0.05, 0.10, 0.01)[step] = start + step * ((start + delta) - start)
@@ -1102,6 +1128,7 @@ __device__ inline LgPoint3d lg_point_3d_pre(const LgFinishArgs& a, int b, int x,
                     if (w == (x0 >> 6)) m &= ~0ull << (x0 & 63);
                     if (w == (x1 >> 6)) m &= ~0ull >> (63 - (x1 & 63));
                     hit |= (row[w] & m) != 0ull;
+                    if (fb2) hit |= (fb2[(size_t)yy * WW + w] & m) != 0ull;
                 }
             }
         }
@@ -1615,14 +1642,17 @@ struct LgGatherNoDefer { int unused; };
 // numpy's min and max return NaN for a window that holds one (fminf / fmaxf skip it)
 __device__ __forceinline__ float lg_nanmin(float a, float b) { return __builtin_elementwise_minimum(a, b); }
 __device__ __forceinline__ float lg_nanmax(float a, float b) { return __builtin_elementwise_maximum(a, b); }
-template <bool HALO, bool DEFER>
+// LA (label-aware mode, with DEFER; false: the extra argument is an unused placeholder): isolation of a frame that has another
+// leaf comes from the two chamfer-3 transforms (lg_iso_value) instead of the plane kernel's closed form.
+template <bool HALO, bool DEFER, bool LA = false>
 __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict__ depth,
                                                         const uint8_t* __restrict__ mask, LgGatherMaps maps,
                                                         const uint8_t* __restrict__ tile_state, float flat_scale, int H,
                                                         int W, int k, const int32_t* __restrict__ xy,
                                                         const int32_t* __restrict__ n, float* __restrict__ patches,
                                                         const int32_t* __restrict__ list, const int32_t* __restrict__ count,
-                                                        typename std::conditional<DEFER, LgFinalArgs, LgGatherNoDefer>::type fa) {
+                                                        typename std::conditional<DEFER, LgFinalArgs, LgGatherNoDefer>::type fa,
+                                                        typename std::conditional<LA, LgIsoFields, LgGatherNoDefer>::type iso) {
     __shared__ float s_pl[DEFER ? 5 : 1][DEFER ? 1024 : 1];   // sdf, approach, isolation, accessibility, stem of the rectangle
     __shared__ float s_mn[4], s_mx[4];
     __shared__ int s_mat[3][2];   // state of the <= 3 x 2 tiles under the window (rows ty_lo.., columns tx_lo..)
@@ -1697,6 +1727,19 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
             bool o_valid[4];
             const LgPixFrame pf = lg_pix_frame(&fa, fa.fp + frame, fa.maxfix + LG_MF * (size_t)frame);
             lg_pixels4<true>(&fa, pf, y, x0, H, W, mnib, snib, din, o_flat, fa.w_flat, o_sdf, o_app, o_iso, o_acc, o_stem, o_trad, o_valid);
+            if constexpr (LA) {
+                const uint32_t* imf = iso.iso_mf + (size_t)frame * LG_ISO_MF;
+                if (imf[2] != 0u) {
+                    const uint32_t* fc = iso.fields + (size_t)frame * 2 * H * W;
+                    const float ramp = __builtin_fmaf(fa.iso_ramp_step, (float)y, fa.iso_ramp_top);
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const size_t o = (size_t)y * W + min(x0 + j, W - 1);
+                        o_iso[j] = lg_iso_value(fc[o], fc[(size_t)H * W + o], imf[0], imf[1], fa.iso_w_close, fa.iso_w_wide, ramp) *
+                                   (((mnib >> j) & 1u) ? 1.0f : 0.0f);
+                    }
+                }
+            }
 #pragma unroll
             for (int j = 0; j < 4; j++)
                 if (gx + j < RW) {
@@ -1763,19 +1806,23 @@ __global__ __launch_bounds__(256) void lg_gather_kernel(const float* __restrict_
 
 void lg_launch_gather(const float* depth, const uint8_t* mask, const float* const* maps_host, const uint8_t* tile_state,
                       float flat_scale, int B, int H, int W, int k, const int32_t* xy, const int32_t* n, float* patches,
-                      bool haloed, hipStream_t s, const int32_t* list, const int32_t* count, const LgFinalArgs* defer) {
+                      bool haloed, hipStream_t s, const int32_t* list, const int32_t* count, const LgFinalArgs* defer,
+                      const LgIsoFields* iso) {
     LgGatherMaps gm;
     for (int i = 0; i < 7; i++) gm.p[i] = maps_host[i];
     const LgGatherNoDefer nd = {0};
-    if (defer)   // (lg_select_grasp*: haloed patches; the frames and their tile_state are those of *defer)
+    if (defer && iso)   // (label-aware mode: isolation from the transforms; without `defer` the gather reads the stored plane)
+        hipLaunchKernelGGL((lg_gather_kernel<true, true, true>), dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H,
+                           W, k, xy, n, patches, list, count, *defer, *iso);
+    else if (defer)   // (lg_select_grasp*: haloed patches; the frames and their tile_state are those of *defer)
         hipLaunchKernelGGL((lg_gather_kernel<true, true>), dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W, k,
-                           xy, n, patches, list, count, *defer);
+                           xy, n, patches, list, count, *defer, nd);
     else if (haloed)
         hipLaunchKernelGGL((lg_gather_kernel<true, false>), dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W, k,
-                           xy, n, patches, list, count, nd);
+                           xy, n, patches, list, count, nd, nd);
     else
         hipLaunchKernelGGL((lg_gather_kernel<false, false>), dim3(k, B), dim3(256), 0, s, depth, mask, gm, tile_state, flat_scale, H, W,
-                           k, xy, n, patches, list, count, nd);
+                           k, xy, n, patches, list, count, nd, nd);
 }
 
 // ============================================================================ training-sample harvesting

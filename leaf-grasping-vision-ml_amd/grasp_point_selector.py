@@ -305,6 +305,17 @@ class GraspPointSelector:
             raise RuntimeError(lib.lg_last_error(self._h).decode())
         return out
 
+    def isolation_fields(self, frame, H, W):
+        """Inspection: (dc_fix, dw_fix, (max_c, max_w)) of frame `frame` of the last label-aware select call -- the raw 16.16
+        chamfer-3 transforms over the whole [H, W] frame and their maxima (lg_debug_isolation_fields) -- or None for a frame
+        without another leaf (it took the closed form)."""
+        dc, dw = np.zeros((H, W), np.uint32), np.zeros((H, W), np.uint32)
+        mx = (C.c_uint32 * 2)()
+        rc = lib.lg_debug_isolation_fields(self._h, int(frame), dc.ctypes.data, dw.ctypes.data, mx)
+        if rc < 0:
+            raise RuntimeError(lib.lg_last_error(self._h).decode())
+        return (dc, dw, (int(mx[0]), int(mx[1]))) if rc == 1 else None
+
     def ws_plane_bytes(self):
         """Inspection: dict plane name -> bytes of device memory this handle holds for its own copy of that plane
         (lg_debug_ws_plane_bytes).  A selector that has only made calls without return_maps holds distance_map,
@@ -424,12 +435,15 @@ class GraspPointSelector:
             return out, {n: maps[i] for i, n in enumerate(MAP_NAMES)}, valid
         return out
 
-    def select_grasp_points_for_leaves(self, label_tensors, leaf_ids, depth_tensors, image_processor=None):
+    def select_grasp_points_for_leaves(self, label_tensors, leaf_ids, depth_tensors, image_processor=None, label_aware=False):
         """select_grasp_points_batch(label_tensors == leaf_ids[:, None, None], depth_tensors) -- the node's `optimal_mask =
         mask_tensor == optimal_leaf_id` and select_grasp_point (leaf_grasp_node_v3.py:118-125) -- with the comparison folded into
         the library's first pass over the frames (lg_select_grasp_labels).  label_tensors: [B,H,W] int16 on this device; leaf_ids:
         B ints, None for a frame without a leaf (the node does not call select_grasp_point for it: its triple is (None, None,
-        None)).  The mask counts as the torch.bool tensor the node passes."""
+        None)).  The mask counts as the torch.bool tensor the node passes.
+        label_aware=True (lg_params.label_aware): the isolation map and the pre-grasp clearance see the other leaves of the
+        label image (every label > 0 that is not the frame's leaf) instead of the one leaf alone; a frame without another leaf
+        keeps its results.  The CNN then sees another channel 5: retrain a model that was trained on the degenerate one."""
         lab = label_tensors
         if not (torch.is_tensor(lab) and lab.dtype == torch.int16 and lab.is_cuda and lab.dim() == 3 and lab.is_contiguous()):
             raise ValueError("label_tensors must be a contiguous [B,H,W] int16 tensor on the device")
@@ -437,8 +451,9 @@ class GraspPointSelector:
         if d.shape != lab.shape:
             raise ValueError(f"labels {tuple(lab.shape)} and depth {tuple(d.shape)} must both be [B,H,W]")
         B, H, W = lab.shape
-        p = self._sync_params(image_processor)
+        p = LgParams.from_buffer_copy(self._sync_params(image_processor))   # the selector's own params stay label-blind
         p.mask_is_bool = 1
+        p.label_aware = 1 if label_aware else 0
         ids = (C.c_int32 * B)(*[(-(1 << 30)) if i is None else int(i) for i in leaf_ids])
         res = (LgGraspResult * B)()
         with torch.cuda.device(self.device):
@@ -476,7 +491,8 @@ class GraspPointSelector:
         self.last_results = res
         return _triples(res, B), np.frombuffer(rows, dtype=GRASP_CANDIDATE_DTYPE).reshape(B, p.top_k)
 
-    def select_grasp_candidates_for_leaves(self, label_tensors, leaf_ids, depth_tensors, image_processor=None, top_k=20):
+    def select_grasp_candidates_for_leaves(self, label_tensors, leaf_ids, depth_tensors, image_processor=None, top_k=20,
+                                           label_aware=False):
         """select_grasp_candidates_batch(label_tensors == leaf_ids[:, None, None], depth_tensors) through the labels entry point
         (as select_grasp_points_for_leaves; the mask counts as a torch.bool tensor).  A None leaf id gives the (None, None, None)
         triple and zero candidate rows."""
@@ -488,6 +504,7 @@ class GraspPointSelector:
             raise ValueError(f"labels {tuple(lab.shape)} and depth {tuple(d.shape)} must both be [B,H,W]")
         B, H, W = lab.shape
         p = self._candidate_params(image_processor, top_k, True)
+        p.label_aware = 1 if label_aware else 0   # (as select_grasp_points_for_leaves; every ranked candidate's pre-grasp too)
         ids = (C.c_int32 * B)(*[(-(1 << 30)) if i is None else int(i) for i in leaf_ids])   # no label carries it: no candidates
         res = (LgGraspResult * B)()
         rows = (LgGraspCandidate * (B * p.top_k))()

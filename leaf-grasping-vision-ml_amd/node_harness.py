@@ -12,8 +12,11 @@ from .leaf_scorer import OptimalLeafSelector
 
 
 class LeafGraspHarness:
-    def __init__(self, height=1080, width=1440, device="cuda:0", load_model=True):
+    def __init__(self, height=1080, width=1440, device="cuda:0", load_model=True, label_aware=False):
         self.height, self.width = height, width
+        # True: the batch path's grasp selection sees the other leaves of the label image (lg_params.label_aware: the isolation
+        # map and the pre-grasp clearance).  The single-frame path follows the node and hands over one leaf's mask.
+        self.label_aware = bool(label_aware)
         self.device = torch.device(device)
         self.kernel_size = 21              # leaf_grasp_node_v3.py:35
         self.gaussian_kernel_size = 5      # :37
@@ -146,9 +149,12 @@ class LeafGraspHarness:
             return
         if mask_t.dtype == torch.int16 and mask_t.is_contiguous() and depth_t.is_contiguous():
             # the comparison inside the library's first pass over the labels (frames without a leaf get an empty mask there)
-            self.grasp_selector.select_grasp_points_for_leaves(mask_t, ids, depth_t, image_processor=self.image_processor)
+            self.grasp_selector.select_grasp_points_for_leaves(mask_t, ids, depth_t, image_processor=self.image_processor,
+                                                               label_aware=self.label_aware)
             rows = range(B)
         else:
+            if self.label_aware:
+                raise ValueError("label_aware needs contiguous int16 label frames on the device")
             idt = torch.tensor([ids[b] for b in keep], dtype=mask_t.dtype, device=self.device).reshape(-1, 1, 1)
             if len(keep) == B:
                 optimal, dep = mask_t == idt, depth_t
