@@ -544,16 +544,17 @@ int lg_train_grad_buffer(lg_trainer* t, float** dev_ptr, int64_t* n);
 int lg_train_apply(lg_trainer* t, const lg_train_hparams* hp, float* grad_norm_host);
 
 /* ---- trainer -> inference hand-off and validation on the device (scripts/train_model.py:280-311)
-   lg_cnn_load_from_trainer   what lg_cnn_load does, computed on the device from the trainer's flat parameter and buffer
-                     vectors: BatchNorm folding, the direct, F(2x2) and F(4x4) Winograd weight layouts, the transposed
-                     classifier.  Every float equals what lg_cnn_load writes for trainer.state_dict (the same IEEE double
-                     operations in the same order, rounded once).  Whether the inference kernels take the model is decided
+   lg_cnn_load_from_trainer   lg_cnn_load without the host: the one fold both entries share (device kernels: BatchNorm
+                     folding, the direct, F(2x2) and F(4x4) Winograd weight layouts, the transposed classifier; IEEE double
+                     operations in a fixed order, rounded once) reads the trainer's flat parameter and buffer vectors where
+                     lg_cnn_load reads a device copy of the caller's host tensors, so every float equals what lg_cnn_load
+                     writes for trainer.state_dict.  Whether the inference kernels take the model is decided
                      before anything is touched -- lg_cnn_load's conditions and messages, and the classifier sizes a forward
                      would refuse: on LG_ERR_UNSUPPORTED / LG_ERR_INVALID (a null trainer, a trainer on another device) the
                      model loaded before stays loaded and usable.  Same geometry as the loaded model (encoder_filters,
                      attention_type): the weight buffers are rewritten in place, nothing is freed or allocated and the
-                     activation workspace stays; otherwise as lg_cnn_load.  LG_CNN_F23 / LG_CNN_DIRECT / LG_CNN_WINO_MASK
-                     are read as lg_cnn_load reads them.
+                     activation workspace stays; otherwise as lg_cnn_load (which always frees first and allocates anew).
+                     LG_CNN_F23 / LG_CNN_DIRECT / LG_CNN_WINO_MASK are read at the end of either load.
                      Ordering: the fold runs on the legacy default stream behind an event recorded on the trainer's own
                      stream(s) -- no lg_train_sync is needed after lg_train_step -- and that stream is synchronised before
                      the call returns: a forward enqueued on any stream afterwards reads the new weights.  A forward still
@@ -582,8 +583,8 @@ int lg_train_apply(lg_trainer* t, const lg_train_hparams* hp, float* grad_norm_h
                      UWINO of layer 0, attention tensors of another attention type).  cap = 0: size query.  LG_CNNW_SCALARS:
                      n_layers, F, Fp, npix, act_per_patch, standard, att_type, att_b (0 without spatial attention), then
                      cin, cout, cinp, coutp, wi, pool of every layer, as floats.  LG_CNNW_ALLOCS: copies nothing; *n = the
-                     weight buffers lg_cnn_load_from_trainer has allocated on this handle so far (an in-place refresh adds
-                     none: the buffers sit where they sat).  Synchronises the device. */
+                     weight buffers lg_cnn_load and lg_cnn_load_from_trainer have allocated on this handle so far (an
+                     in-place refresh adds none: the buffers sit where they sat).  Synchronises the device. */
 enum { LG_CNNW_BCONV = 0, LG_CNNW_WCONV = 1, LG_CNNW_UWINO = 2, LG_CNNW_UWINO4 = 3, LG_CNNW_FCW = 4, LG_CNNW_FCB = 5,
        LG_CNNW_ATT_W = 6, LG_CNNW_CA_W1 = 7, LG_CNNW_CA_B1 = 8, LG_CNNW_CA_W2 = 9, LG_CNNW_CA_B2 = 10, LG_CNNW_ZEROS = 11,
        LG_CNNW_SCALARS = 12, LG_CNNW_ALLOCS = 13 };

@@ -1577,7 +1577,7 @@ int lg_cnn_forward(lg_handle h, const float* patches, int N, float* logits, void
     return LG_OK;
 }
 
-// The trainer's weights into this handle's inference CNN without leaving the device (lg_cnn.hip: the fold and transform kernels).
+// The trainer's weights into this handle's inference CNN without leaving the device (lg_cnn_load.hip: the fold and transform kernels).
 // The fold runs on the legacy default stream -- ordered after every blocking stream's earlier work, a forward on torch's default
 // stream included -- behind an event recorded on each of the trainer's (non-blocking) streams.
 int lg_cnn_load_from_trainer(lg_handle h, lg_trainer* t) {
@@ -1608,7 +1608,7 @@ int lg_debug_cnn_weights(lg_handle h, int which, int layer, float* out, int64_t 
     LG_ENTER(h);
     *n = 0;
     const LgCnn& c = h->cnn;
-    if (which == LG_CNNW_ALLOCS) { *n = (int64_t)c.handoff_allocs; return LG_OK; }
+    if (which == LG_CNNW_ALLOCS) { *n = (int64_t)c.weight_allocs; return LG_OK; }
     if (!c.loaded) return fail(h, LG_ERR_NO_MODEL, "lg_debug_cnn_weights: no model loaded");
     if (which == LG_CNNW_SCALARS) {
         std::vector<float> sc = {(float)c.n_layers, (float)c.F, (float)c.Fp, (float)c.npix, (float)c.act_per_patch, c.standard ? 1.f : 0.f,

@@ -1,6 +1,9 @@
 // GraspPointCNN (scripts/utils/ml_grasp_optimizer/model.py:5-128, eval mode; the four attention types and the four
 // encoder_filters configurations of the reference's sweep) on gfx950: BN folded at load, 3x3 convs as implicit GEMM on
 // v_mfma_f32_32x32x2_f32 (exact fp32), fused bias+ReLU(+2x2 max-pool) epilogues.
+// lg_cnn.hip: the forward kernels, their launch tables and the run path.  lg_cnn_load.hip: the layer plan, the table of weight
+// buffers and the one fold (three device kernels) behind both loaders -- lg_cnn_upload stages the caller's host tensors on the
+// device and then runs what lg_cnn_upload_from_trainer runs on the trainer's vectors.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,14 +13,30 @@
 
 struct RtLayer { int cin, cout, cinp, coutp, wi; bool pool; };   // real / padded channels, image width, 2x2 pool after it
 
-struct LgCnn {
-    bool loaded = false;
-    int max_cus = 0;              // > 0: the persistent conv kernels take this many workgroups (CUs) instead of all (LG_CNN_CUS experiment)
+// What (n_blocks, encoder_filters) make of the network: n_blocks x [conv(cin->f), conv(f->f), pool], channels padded to the
+// kernels' 64-channel granule.  The defaults are the node's model, encoder [64,128,256].
+struct LgCnnPlan {
     int n_layers = 6;             // 2 conv layers per encoder block
     RtLayer layers[8] = {};
     bool standard = true;         // encoder [64,128,256]: the direct kernels / A-B switches exist for this one only
     int F = 256, Fp = 256, npix = 16;   // final filters (real / padded), pixels of the last feature map
     size_t act_per_patch = 64 * 32 * 32;  // floats of the largest activation per patch
+    int hid = 16;                 // channel attention's hidden width, F / 16
+    int dims[5] = {256, 256, 128, 64, 1};   // classifier widths F, F, F / 2, F / 4, 1
+};
+// The plan of a model and whether the inference kernels take it (lg_cnn_load's codes and messages).  n_blocks == 0: three
+// blocks of [64,128,256].  need_head: also refuse a classifier size lg_head_kernel has no instance for (a hand-off does, while
+// the old model can still be kept; lg_cnn_load leaves that to the first forward).  Geometry is judged first (LG_ERR_UNSUPPORTED);
+// an attention_type out of range comes last (LG_ERR_INVALID), with *p filled in.
+int lg_cnn_plan(int n_blocks, const int32_t* filters, int attention_type, bool need_head, LgCnnPlan* p, std::string* err);
+bool wino_supported(int cin, int cout, int wi, bool pool);   // the shapes lg_wino_kernel / lg_wino4_kernel are instantiated for
+bool lg_head_supported(int F, int npix);                     // the instances of lg_head_kernel          (both: lg_cnn.hip)
+
+// Weight buffers are allocated and freed through one table (weight_buffers, lg_cnn_load.hip) of the plan and att_type held
+// here: a slot the table does not list for them is null.
+struct LgCnn : LgCnnPlan {
+    bool loaded = false;
+    int max_cus = 0;              // > 0: the persistent conv kernels take this many workgroups (CUs) instead of all (LG_CNN_CUS experiment)
     float* wconv[8] = {nullptr};  // packed [ky][kx][cin_pad][cout], BN folded (layer 0; all layers of the standard model)
     float* bconv[8] = {nullptr};
     float* uwino[8] = {nullptr};  // Winograd F(2x2,3x3) weights [cin][cout][16] (layers 1..)
@@ -42,11 +61,13 @@ struct LgCnn {
     unsigned* kerr_dev = nullptr;
     int wino_mask = 0x3f;         // bit L = layer L on Winograd (LG_CNN_DIRECT / LG_CNN_WINO_MASK at load time; bits 1..5: standard encoder only)
     int capN = 0;
-    long long handoff_allocs = 0; // weight buffers lg_cnn_upload_from_trainer has allocated on this handle (0 more on an in-place refresh)
+    long long weight_allocs = 0;  // weight buffers either loader has allocated on this handle (0 more on an in-place refresh)
 };
 
+// Frees the loaded model first (a refused load leaves none, never refreshes in place), stages the host tensors of *w in one
+// device vector, folds on the legacy default stream and synchronises it.
 int lg_cnn_upload(LgCnn* c, const lg_cnn_weights* w, std::string* err);
-void lg_cnn_free(LgCnn* c);
+void lg_cnn_free(LgCnn* c);   // weights and workspace
 // patches: dense [N][9][32][32] (haloed_in = false) or haloed planes [N][12][34][36] (planes 9..11 and all halos zero) (what lg_select_grasp's
 // gather writes directly; lg_cnn_halo_patch_floats() floats per patch)
 // allow_split = false: no item of lg_wino4_kernel is split along the input channels, so a patch's logit does not depend on the
@@ -61,7 +82,7 @@ bool lg_cnn_take_error(LgCnn* c);
 
 // ---- trainer -> inference hand-off on the device (lg_cnn_load_from_trainer)
 // What the fold kernels need of an lg_trainer (lg_train.hip): the flat parameter / buffer vectors and the offsets of every tensor
-// in them, in the order of lg_cnn_weights.
+// in them, in the order of lg_cnn_weights.  (lg_cnn_upload builds one of its staged copy of the host tensors.)
 struct LgTrainView {
     int device = 0, n_blocks = 0, att = 0, F = 0, hid = 0;
     int filters[4] = {0, 0, 0, 0};
@@ -76,10 +97,10 @@ struct LgTrainView {
     hipStream_t stream[2] = {nullptr, nullptr};  // the streams the trainer's steps run on
 };
 bool lg_train_view(lg_trainer* t, LgTrainView* v);
-// lg_cnn_upload computed on the device from the trainer's vectors, on stream s (the caller orders s after the trainer's
-// streams); synchronises s before it returns (the spatial attention's bias comes back as one 4-byte copy).  Every float written
-// equals what lg_cnn_upload writes for the same state.  Support is decided before anything is touched; same geometry as loaded
-// (n_layers, layers[], att_type): the weight buffers are rewritten in place, nothing is freed or allocated.
+// The weights from the trainer's vectors, on stream s (the caller orders s after the trainer's streams); synchronises s before it
+// returns (the spatial attention's bias comes back as one 4-byte copy).  The fold is lg_cnn_upload's, so every float equals what
+// that writes for the same state.  Support is decided before anything is touched; same geometry as loaded (n_layers, layers[],
+// att_type): the weight buffers are rewritten in place, nothing is freed or allocated.
 int lg_cnn_upload_from_trainer(LgCnn* c, const LgTrainView* v, hipStream_t s, std::string* err);
 // the weight buffer `which` (LG_CNNW_*) of layer `layer`: its device pointer and floats; false: no such buffer for this model
 bool lg_cnn_weight_buffer(const LgCnn* c, int which, int layer, const float** p, size_t* n);

@@ -17,12 +17,9 @@
 #include "lg_cnn.h"
 
 #include <math.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <type_traits>
-#include <vector>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -1277,12 +1274,16 @@ void launch_conv0(const float* in, const LgCnn* c, float* out, int N, hipStream_
     X(128, 128, 32, true) X(128, 256, 16, false) X(256, 256, 16, true) X(256, 512, 8, false) X(512, 512, 8, true)  \
     X(256, 512, 4, false) X(512, 512, 4, true)
 
+}  // namespace
+
 bool wino_supported(int cin, int cout, int wi, bool pool) {
 #define X(CI, CO, W_, P) if (cin == CI && cout == CO && wi == W_ && pool == P) return true;
     LG_WINO_SHAPES(X)
 #undef X
     return false;
 }
+
+namespace {
 
 // out_halo: the next layer is a convolution (haloed plane); false: the head reads dense [C][npix]
 bool launch_wino_rt(int cin, int cout, int wi, bool pool, bool out_halo, const float* in, const float* U, const float* bias,
@@ -1367,464 +1368,9 @@ bool lg_cnn_take_error(LgCnn* c) {
     return true;
 }
 
-void lg_cnn_free(LgCnn* c) {
-    auto F = [](float*& p) { if (p) hipFree(p); p = nullptr; };
-    for (int i = 0; i < 8; i++) { F(c->wconv[i]); F(c->bconv[i]); F(c->uwino[i]); F(c->uwino4[i]); F(c->act[i]); }
-    F(c->att_w); F(c->ca_w1); F(c->ca_b1); F(c->ca_w2); F(c->ca_b2);
-    for (int i = 0; i < 4; i++) { F(c->fcw[i]); F(c->fcb[i]); }
-    F(c->in_halo); F(c->zeros); F(c->kpart);
-    if (c->kflag) { hipFree(c->kflag); c->kflag = nullptr; }
-    if (c->kerr_host) { hipHostFree(c->kerr_host); c->kerr_host = nullptr; c->kerr_dev = nullptr; }
-    c->capN = 0;
-    c->loaded = false;
-}
-
-static int upload(float** dst, const std::vector<float>& v, std::string* err) {
-    if (hipMalloc((void**)dst, v.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        *err = "lg_cnn_load: device allocation/copy failed";
-        return LG_ERR_HIP;
-    }
-    return LG_OK;
-}
-
-int lg_cnn_upload(LgCnn* c, const lg_cnn_weights* w, std::string* err) {
-    lg_cnn_free(c);
-    const float eps = w->bn_eps > 0.f ? w->bn_eps : 1e-5f;
-    // ---- layer plan: n_blocks x [conv(cin->f), conv(f->f), pool]; channels padded to the kernels' 64-channel granule
-    const int nb = w->n_blocks > 0 ? w->n_blocks : 3;
-    int filt[4] = {64, 128, 256, 0};
-    if (w->n_blocks > 0)
-        for (int b = 0; b < 4; b++) filt[b] = w->filters[b];
-    if (nb < 1 || nb > 4) { *err = "lg_cnn_load: 1..4 encoder blocks"; return LG_ERR_UNSUPPORTED; }
-    c->n_layers = 2 * nb;
-    int cin = 9, cinp = 10, wi = 32;
-    size_t per = 0;
-    for (int b = 0; b < nb; b++) {
-        const int f = filt[b], fp = (f + 63) / 64 * 64;
-        if (f < 16 || f > 512 || (f % 16) != 0) { *err = "lg_cnn_load: encoder filters must be multiples of 16 in [16, 512]"; return LG_ERR_UNSUPPORTED; }
-        c->layers[2 * b] = {cin, f, cinp, fp, wi, false};
-        c->layers[2 * b + 1] = {f, f, fp, fp, wi, true};
-        per = std::max(per, (size_t)fp * wi * wi);
-        cin = f; cinp = fp; wi /= 2;
-    }
-    c->F = filt[nb - 1]; c->Fp = (c->F + 63) / 64 * 64; c->npix = wi * wi;
-    c->act_per_patch = per;
-    c->standard = nb == 3 && filt[0] == 64 && filt[1] == 128 && filt[2] == 256;
-    if (c->layers[0].coutp != 64 && c->layers[0].coutp != 128) { *err = "lg_cnn_load: first stage wider than 128 channels"; return LG_ERR_UNSUPPORTED; }
-    for (int L = 1; L < c->n_layers; L++) {
-        const RtLayer& l = c->layers[L];
-        if (!wino_supported(l.cinp, l.coutp, l.wi, l.pool)) {
-            *err = "lg_cnn_load: encoder_filters outside the reference's configurations ([32,64,128], [64,128,256], "
-                   "[64,128,256,512], [128,256,512])";
-            return LG_ERR_UNSUPPORTED;
-        }
-    }
-    for (int L = 0; L < c->n_layers; L++) {
-        const RtLayer& l = c->layers[L];
-        if (!w->conv_w[L] || !w->conv_b[L] || !w->bn_g[L] || !w->bn_b[L] || !w->bn_m[L] || !w->bn_v[L]) {
-            *err = "lg_cnn_load: missing encoder tensor";
-            return LG_ERR_INVALID;
-        }
-        // fold eval-mode BatchNorm2d: y = (conv + b - mean) * g / sqrt(var + eps) + beta; padded channels stay 0
-        std::vector<float> bp(l.coutp, 0.0f);
-        std::vector<double> scv(l.cout);
-        for (int co = 0; co < l.cout; co++) {
-            scv[co] = (double)w->bn_g[L][co] / sqrt((double)w->bn_v[L][co] + (double)eps);
-            bp[co] = (float)(((double)w->conv_b[L][co] - (double)w->bn_m[L][co]) * scv[co] + (double)w->bn_b[L][co]);
-        }
-        int rc = upload(&c->bconv[L], bp, err);
-        if (rc) return rc;
-        if (L == 0 || c->standard) {   // direct implicit-GEMM weights [tap][cin_pad][cout] (layer 0; A/B path of the standard model)
-            std::vector<float> wp((size_t)9 * l.cinp * l.coutp, 0.0f);
-            for (int co = 0; co < l.cout; co++)
-                for (int ci = 0; ci < l.cin; ci++)
-                    for (int tap = 0; tap < 9; tap++)
-                        wp[((size_t)tap * l.cinp + ci) * l.coutp + co] =
-                            (float)((double)w->conv_w[L][((size_t)co * l.cin + ci) * 9 + tap] * scv[co]);
-            rc = upload(&c->wconv[L], wp, err);
-            if (rc) return rc;
-        }
-        if (L >= 1) {
-            // Winograd-domain weights U = G g G^T of the BN-folded kernel (position 4i+j), rounded once from double, in the order
-            // lg_wino_kernel's A fragments are read
-            std::vector<float> uw((size_t)l.cinp * l.coutp * 16, 0.0f);
-            for (int co = 0; co < l.cout; co++) {
-                for (int ci = 0; ci < l.cin; ci++) {
-                    double g[3][3], gg[4][3];
-                    for (int tap = 0; tap < 9; tap++)
-                        g[tap / 3][tap % 3] = (double)w->conv_w[L][((size_t)co * l.cin + ci) * 9 + tap] * scv[co];
-                    for (int j = 0; j < 3; j++) {
-                        gg[0][j] = g[0][j];
-                        gg[1][j] = 0.5 * (g[0][j] + g[1][j] + g[2][j]);
-                        gg[2][j] = 0.5 * (g[0][j] - g[1][j] + g[2][j]);
-                        gg[3][j] = g[2][j];
-                    }
-                    // [k-step = ci/4][16-channel block][q = position group][lane = (ci%4)*16 + co%16][4 positions]
-                    float* u = &uw[((((size_t)(ci / 4) * (l.coutp / 16) + co / 16) * 4) * 64 + (ci % 4) * 16 + co % 16) * 4];
-                    for (int i = 0; i < 4; i++) {
-                        u[256 * i + 0] = (float)gg[i][0];
-                        u[256 * i + 1] = (float)(0.5 * (gg[i][0] + gg[i][1] + gg[i][2]));
-                        u[256 * i + 2] = (float)(0.5 * (gg[i][0] - gg[i][1] + gg[i][2]));
-                        u[256 * i + 3] = (float)gg[i][2];
-                    }
-                }
-            }
-            rc = upload(&c->uwino[L], uw, err);
-            if (rc) return rc;
-        }
-        {
-            // F(4x4,3x3) weights U = G g G^T (6x6) of the BN-folded kernel in the order lg_wino4_kernel's A fragments are read:
-            // [k-step = ci/4][64-channel block][cb = (co%64)/16][position group pg = pos/4][lane = (ci%4)*16 + co%16][pos%4]
-            static const double G4[6][3] = {{1.0 / 4, 0, 0},          {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                            {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-            const int cinp4 = L == 0 ? 12 : l.cinp;   // layer 0: 9 feature planes + 3 zero planes
-            std::vector<float> u4((size_t)cinp4 * l.coutp * 36, 0.0f);
-            const int ncb = l.coutp / 64;
-            for (int co = 0; co < l.cout; co++) {
-                for (int ci = 0; ci < l.cin; ci++) {
-                    double g[3][3], gg[6][3];
-                    for (int tap = 0; tap < 9; tap++)
-                        g[tap / 3][tap % 3] = (double)w->conv_w[L][((size_t)co * l.cin + ci) * 9 + tap] * scv[co];
-                    for (int i = 0; i < 6; i++)
-                        for (int j = 0; j < 3; j++) gg[i][j] = G4[i][0] * g[0][j] + G4[i][1] * g[1][j] + G4[i][2] * g[2][j];
-                    const size_t base = ((((size_t)(ci / 4) * ncb + co / 64) * 4 + (co % 64) / 16) * 9) * 256 + ((ci % 4) * 16 + co % 16) * 4;
-                    for (int i = 0; i < 6; i++)
-                        for (int j = 0; j < 6; j++) {
-                            const int pos = 6 * i + j;
-                            u4[base + (size_t)(pos / 4) * 256 + pos % 4] =
-                                (float)(gg[i][0] * G4[j][0] + gg[i][1] * G4[j][1] + gg[i][2] * G4[j][2]);
-                        }
-                }
-            }
-            rc = upload(&c->uwino4[L], u4, err);
-            if (rc) return rc;
-        }
-    }
-    const int F = c->F;
-    c->att_type = w->attention_type;
-    if (c->att_type < LG_ATT_SPATIAL || c->att_type > LG_ATT_NONE) { *err = "lg_cnn_load: unknown attention_type"; return LG_ERR_INVALID; }
-    if (c->att_type == LG_ATT_SPATIAL || c->att_type == LG_ATT_HYBRID) {
-        if (!w->att_w || !w->att_b) { *err = "lg_cnn_load: missing spatial attention tensor"; return LG_ERR_INVALID; }
-        int rc = upload(&c->att_w, std::vector<float>(w->att_w, w->att_w + F), err);
-        if (rc) return rc;
-        c->att_b = w->att_b[0];
-    }
-    if (c->att_type == LG_ATT_CHANNEL || c->att_type == LG_ATT_HYBRID) {
-        if (!w->ca_w1 || !w->ca_b1 || !w->ca_w2 || !w->ca_b2) { *err = "lg_cnn_load: missing channel attention tensor"; return LG_ERR_INVALID; }
-        const int hid = F / 16;
-        int rc = upload(&c->ca_w1, std::vector<float>(w->ca_w1, w->ca_w1 + (size_t)hid * F), err);
-        if (!rc) rc = upload(&c->ca_b1, std::vector<float>(w->ca_b1, w->ca_b1 + hid), err);
-        if (!rc) rc = upload(&c->ca_w2, std::vector<float>(w->ca_w2, w->ca_w2 + (size_t)F * hid), err);
-        if (!rc) rc = upload(&c->ca_b2, std::vector<float>(w->ca_b2, w->ca_b2 + F), err);
-        if (rc) return rc;
-    }
-    const int dims[5] = {F, F, F / 2, F / 4, 1};
-    for (int L = 0; L < 4; L++) {
-        const int fin = dims[L], fout = dims[L + 1];
-        if (!w->fc_w[L] || !w->fc_b[L]) { *err = "lg_cnn_load: missing classifier tensor"; return LG_ERR_INVALID; }
-        std::vector<float> wt((size_t)fin * fout), bt(fout);
-        for (int o = 0; o < fout; o++) {
-            double sc = 1.0, sh = 0.0;
-            if (L < 3) {
-                if (!w->fbn_g[L] || !w->fbn_b[L] || !w->fbn_m[L] || !w->fbn_v[L]) {
-                    *err = "lg_cnn_load: missing classifier BN tensor";
-                    return LG_ERR_INVALID;
-                }
-                sc = (double)w->fbn_g[L][o] / sqrt((double)w->fbn_v[L][o] + (double)eps);
-                sh = (double)w->fbn_b[L][o] - (double)w->fbn_m[L][o] * sc;
-            }
-            bt[o] = (float)((double)w->fc_b[L][o] * sc + sh);
-            for (int i = 0; i < fin; i++) wt[(size_t)i * fout + o] = (float)((double)w->fc_w[L][(size_t)o * fin + i] * sc);
-        }
-        int rc = upload(&c->fcw[L], wt, err);
-        if (rc) return rc;
-        rc = upload(&c->fcb[L], bt, err);
-        if (rc) return rc;
-    }
-    {   // zeroed plane: padding channel of layer 0, unused staging slots
-        std::vector<float> z(4096, 0.0f);
-        int rc = upload(&c->zeros, z, err);
-        if (rc) return rc;
-    }
-    // A/B and test switches of the standard encoder, read when the model is loaded (not on the per-call path):
-    // LG_CNN_DIRECT=1 direct implicit GEMM for every layer; LG_CNN_WINO_MASK=<bits> bit L = layer L on Winograd
-    // LG_CNN_F23=1 the F(2x2,3x3) Winograd kernels instead of F(4x4,3x3)
-    c->use_f23 = getenv("LG_CNN_F23") != nullptr;
-    c->wino_mask = getenv("LG_CNN_DIRECT") ? 0 : 0x3f;
-    if (const char* e = getenv("LG_CNN_WINO_MASK")) c->wino_mask = atoi(e) & 0x3f;
-    c->loaded = true;
-    return LG_OK;
-}
-
-
-// ================================================================== trainer -> inference hand-off on the device
-// lg_cnn_upload's arithmetic, one thread per output element group: the same IEEE double operations in the same association order,
-// rounded once to float, so both loaders write the same bits.  fp contraction is off in every body: the host build has no FMA
-// and the device would otherwise fuse a * b + c.
-namespace {
-
-struct FoldConv {   // one encoder layer: PyTorch-layout tensors of the trainer, padded geometry of the inference kernels
-    const float *w, *b, *g, *be, *m, *v;
-    int cin, cout, cinp, coutp, cinp4;
-    float eps;
-};
-
-// scv = g / sqrt(v + eps) (eps: the float, promoted)
-__device__ __forceinline__ double lg_fold_scale(const float* g, const float* v, int co, float eps) {
-#pragma clang fp contract(off)
-    return (double)g[co] / sqrt((double)v[co] + (double)eps);
-}
-
-// bconv [coutp] and wconv [tap][cinp][coutp] (wconv = nullptr: not for this layer); thread = (ci, co), co fastest
-__global__ void lg_fold_direct_kernel(FoldConv a, float* __restrict__ bconv, float* __restrict__ wconv) {
-#pragma clang fp contract(off)
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= a.cinp * a.coutp) return;
-    const int co = t % a.coutp, ci = t / a.coutp;
-    const bool real = co < a.cout;
-    const double scv = real ? lg_fold_scale(a.g, a.v, co, a.eps) : 0.0;
-    if (ci == 0) bconv[co] = real ? (float)(((double)a.b[co] - (double)a.m[co]) * scv + (double)a.be[co]) : 0.0f;
-    if (!wconv) return;
-    const float* src = a.w + ((size_t)co * a.cin + ci) * 9;
-    for (int tap = 0; tap < 9; tap++)
-        wconv[((size_t)tap * a.cinp + ci) * a.coutp + co] = real && ci < a.cin ? (float)((double)src[tap] * scv) : 0.0f;
-}
-
-// uwino [ci/4][co/16][q][lane][4] and uwino4 [ci/4][co/64][(co%64)/16][pg][lane][4], lane = (ci%4)*16 + co%16: both orders are
-// (ci/4, co/16, lane) outside the position groups, so thread = (ci/4, co/16, lane) holds one (ci, co) pair and every float4 it
-// stores lies next to its neighbour lane's -- one full 1 KB line per wave and position group.
-// u2 = nullptr: layer 0 (no F(2x2) weights); its F(4x4) weights have cinp4 = 12 input planes.
-__global__ void lg_fold_wino_kernel(FoldConv a, float* __restrict__ u2, float* __restrict__ u4) {
-#pragma clang fp contract(off)
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int nb16 = a.coutp / 16;
-    if (t >= (a.cinp4 / 4) * nb16 * 64) return;
-    const int lane = t % 64, b16 = (t / 64) % nb16, k = t / (64 * nb16);
-    const int ci = 4 * k + lane / 16, co = 16 * b16 + lane % 16;
-    const bool real = ci < a.cin && co < a.cout;
-    double g[3][3];
-    if (real) {
-        const double scv = lg_fold_scale(a.g, a.v, co, a.eps);
-        const float* src = a.w + ((size_t)co * a.cin + ci) * 9;
-        for (int tap = 0; tap < 9; tap++) g[tap / 3][tap % 3] = (double)src[tap] * scv;
-    }
-    if (u2 && ci < a.cinp) {
-        float4* u = (float4*)(u2 + ((((size_t)k * nb16 + b16) * 4) * 64 + lane) * 4);
-        if (real) {
-            double gg[4][3];
-            for (int j = 0; j < 3; j++) {
-                gg[0][j] = g[0][j];
-                gg[1][j] = 0.5 * (g[0][j] + g[1][j] + g[2][j]);
-                gg[2][j] = 0.5 * (g[0][j] - g[1][j] + g[2][j]);
-                gg[3][j] = g[2][j];
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                u[64 * i] = make_float4((float)gg[i][0], (float)(0.5 * (gg[i][0] + gg[i][1] + gg[i][2])),
-                                        (float)(0.5 * (gg[i][0] - gg[i][1] + gg[i][2])), (float)gg[i][2]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++) u[64 * i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    {
-        constexpr double G4[6][3] = {{1.0 / 4, 0, 0},          {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                     {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-        // ((k * ncb + co/64) * 4 + (co%64)/16) = k * nb16 + b16
-        float4* u = (float4*)(u4 + ((((size_t)k * nb16 + b16) * 9) * 64 + lane) * 4);
-        if (real) {
-            double gg[6][3];
-#pragma unroll
-            for (int i = 0; i < 6; i++)
-#pragma unroll
-                for (int j = 0; j < 3; j++) gg[i][j] = G4[i][0] * g[0][j] + G4[i][1] * g[1][j] + G4[i][2] * g[2][j];
-            float o[36];
-#pragma unroll
-            for (int i = 0; i < 6; i++)
-#pragma unroll
-                for (int j = 0; j < 6; j++) o[6 * i + j] = (float)(gg[i][0] * G4[j][0] + gg[i][1] * G4[j][1] + gg[i][2] * G4[j][2]);
-#pragma unroll
-            for (int pg = 0; pg < 9; pg++) u[64 * pg] = make_float4(o[4 * pg], o[4 * pg + 1], o[4 * pg + 2], o[4 * pg + 3]);
-        } else {
-#pragma unroll
-            for (int pg = 0; pg < 9; pg++) u[64 * pg] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-}
-
-// classifier layer: fcw [in][out] (transposed) and fcb [out], BatchNorm1d folded where g is given; thread = (i, o), o fastest
-__global__ void lg_fold_fc_kernel(const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ g,
-                                  const float* __restrict__ be, const float* __restrict__ m, const float* __restrict__ v, float eps,
-                                  int fin, int fout, float* __restrict__ wt, float* __restrict__ bt) {
-#pragma clang fp contract(off)
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= fin * fout) return;
-    const int o = t % fout, i = t / fout;
-    double sc = 1.0, sh = 0.0;
-    if (g) {
-        sc = (double)g[o] / sqrt((double)v[o] + (double)eps);
-        sh = (double)be[o] - (double)m[o] * sc;
-    }
-    if (i == 0) bt[o] = (float)((double)b[o] * sc + sh);
-    wt[(size_t)i * fout + o] = (float)((double)w[(size_t)o * fin + i] * sc);
-}
-
 bool lg_head_supported(int F, int npix) {   // the instances of lg_head_kernel (LG_HEAD in lg_cnn_run_slice)
     return (npix == 16 && (F == 256 || F == 128 || F == 512)) || (npix == 4 && F == 512);
 }
-
-}  // namespace
-
-bool lg_cnn_weight_buffer(const LgCnn* c, int which, int layer, const float** p, size_t* n) {
-    *p = nullptr; *n = 0;
-    if (!c->loaded) return false;
-    const int F = c->F, hid = F / 16;
-    const int dims[5] = {F, F, F / 2, F / 4, 1};
-    const bool conv = layer >= 0 && layer < c->n_layers, fc = layer >= 0 && layer < 4;
-    const RtLayer& l = c->layers[conv ? layer : 0];
-    switch (which) {
-        case LG_CNNW_BCONV: if (conv) { *p = c->bconv[layer]; *n = l.coutp; } break;
-        case LG_CNNW_WCONV: if (conv) { *p = c->wconv[layer]; *n = (size_t)9 * l.cinp * l.coutp; } break;
-        case LG_CNNW_UWINO: if (conv) { *p = c->uwino[layer]; *n = (size_t)16 * l.cinp * l.coutp; } break;
-        case LG_CNNW_UWINO4: if (conv) { *p = c->uwino4[layer]; *n = (size_t)36 * (layer == 0 ? 12 : l.cinp) * l.coutp; } break;
-        case LG_CNNW_FCW: if (fc) { *p = c->fcw[layer]; *n = (size_t)dims[layer] * dims[layer + 1]; } break;
-        case LG_CNNW_FCB: if (fc) { *p = c->fcb[layer]; *n = dims[layer + 1]; } break;
-        case LG_CNNW_ATT_W: *p = c->att_w; *n = F; break;
-        case LG_CNNW_CA_W1: *p = c->ca_w1; *n = (size_t)hid * F; break;
-        case LG_CNNW_CA_B1: *p = c->ca_b1; *n = hid; break;
-        case LG_CNNW_CA_W2: *p = c->ca_w2; *n = (size_t)F * hid; break;
-        case LG_CNNW_CA_B2: *p = c->ca_b2; *n = F; break;
-        case LG_CNNW_ZEROS: *p = c->zeros; *n = 4096; break;
-        default: break;
-    }
-    if (!*p) *n = 0;
-    return *p != nullptr;
-}
-
-int lg_cnn_upload_from_trainer(LgCnn* c, const LgTrainView* v, hipStream_t s, std::string* err) {
-    // ---- the plan and the support decision of lg_cnn_upload, on a copy: nothing of *c is touched before the model is known to run
-    const float eps = v->bn_eps > 0.f ? v->bn_eps : 1e-5f;
-    const int nb = v->n_blocks;
-    if (nb < 1 || nb > 4) { *err = "lg_cnn_load: 1..4 encoder blocks"; return LG_ERR_UNSUPPORTED; }
-    RtLayer layers[8] = {};
-    int cin = 9, cinp = 10, wi = 32;
-    size_t per = 0;
-    for (int b = 0; b < nb; b++) {
-        const int f = v->filters[b], fp = (f + 63) / 64 * 64;
-        if (f < 16 || f > 512 || (f % 16) != 0) { *err = "lg_cnn_load: encoder filters must be multiples of 16 in [16, 512]"; return LG_ERR_UNSUPPORTED; }
-        layers[2 * b] = {cin, f, cinp, fp, wi, false};
-        layers[2 * b + 1] = {f, f, fp, fp, wi, true};
-        per = std::max(per, (size_t)fp * wi * wi);
-        cin = f; cinp = fp; wi /= 2;
-    }
-    const int n_layers = 2 * nb, F = v->filters[nb - 1], npix = wi * wi;
-    const bool standard = nb == 3 && v->filters[0] == 64 && v->filters[1] == 128 && v->filters[2] == 256;
-    if (layers[0].coutp != 64 && layers[0].coutp != 128) { *err = "lg_cnn_load: first stage wider than 128 channels"; return LG_ERR_UNSUPPORTED; }
-    for (int L = 1; L < n_layers; L++) {
-        const RtLayer& l = layers[L];
-        if (!wino_supported(l.cinp, l.coutp, l.wi, l.pool)) {
-            *err = "lg_cnn_load: encoder_filters outside the reference's configurations ([32,64,128], [64,128,256], "
-                   "[64,128,256,512], [128,256,512])";
-            return LG_ERR_UNSUPPORTED;
-        }
-    }
-    // (lg_cnn_upload leaves this one to the first forward; a hand-off refuses the model while the old one can still be kept)
-    if (!lg_head_supported(F, npix)) { *err = "lg_cnn_forward: unsupported classifier size"; return LG_ERR_UNSUPPORTED; }
-    if (v->att < LG_ATT_SPATIAL || v->att > LG_ATT_NONE) { *err = "lg_cnn_load: unknown attention_type"; return LG_ERR_INVALID; }
-    if (!v->P || !v->B || v->F != F) { *err = "lg_cnn_load: missing encoder tensor"; return LG_ERR_INVALID; }
-    const bool spatial = v->att == LG_ATT_SPATIAL || v->att == LG_ATT_HYBRID, channel = v->att == LG_ATT_CHANNEL || v->att == LG_ATT_HYBRID;
-    const int hid = F / 16;
-    const int dims[5] = {F, F, F / 2, F / 4, 1};
-
-    // ---- same geometry as the model in place: its buffers are rewritten where they are
-    bool same = c->loaded && c->n_layers == n_layers && c->att_type == v->att && c->zeros;
-    for (int L = 0; L < n_layers && same; L++) {
-        const RtLayer &x = c->layers[L], &y = layers[L];
-        same = x.cin == y.cin && x.cout == y.cout && x.cinp == y.cinp && x.coutp == y.coutp && x.wi == y.wi && x.pool == y.pool &&
-               c->bconv[L] && c->uwino4[L] && (L == 0 || c->uwino[L]) && (!(L == 0 || standard) || c->wconv[L]);
-    }
-    for (int L = 0; L < 4 && same; L++) same = c->fcw[L] && c->fcb[L];
-    if (same && spatial) same = c->att_w != nullptr;
-    if (same && channel) same = c->ca_w1 && c->ca_b1 && c->ca_w2 && c->ca_b2;
-    if (!same) {
-        lg_cnn_free(c);
-        c->n_layers = n_layers;
-        for (int L = 0; L < 8; L++) c->layers[L] = layers[L];
-        c->F = F; c->Fp = (F + 63) / 64 * 64; c->npix = npix;
-        c->act_per_patch = per;
-        c->standard = standard;
-        c->att_type = v->att;
-        c->att_b = 0.f;
-        bool ok = true;
-        auto A = [&](float** p, size_t n) {
-            if (ok && hipMalloc((void**)p, n * sizeof(float)) != hipSuccess) ok = false;
-            if (ok) c->handoff_allocs++;
-        };
-        for (int L = 0; L < n_layers; L++) {
-            const RtLayer& l = layers[L];
-            A(&c->bconv[L], l.coutp);
-            if (L == 0 || standard) A(&c->wconv[L], (size_t)9 * l.cinp * l.coutp);
-            if (L >= 1) A(&c->uwino[L], (size_t)16 * l.cinp * l.coutp);
-            A(&c->uwino4[L], (size_t)36 * (L == 0 ? 12 : l.cinp) * l.coutp);
-        }
-        if (spatial) A(&c->att_w, F);
-        if (channel) { A(&c->ca_w1, (size_t)hid * F); A(&c->ca_b1, hid); A(&c->ca_w2, (size_t)F * hid); A(&c->ca_b2, F); }
-        for (int L = 0; L < 4; L++) { A(&c->fcw[L], (size_t)dims[L] * dims[L + 1]); A(&c->fcb[L], dims[L + 1]); }
-        A(&c->zeros, 4096);
-        if (ok && hipMemsetAsync(c->zeros, 0, 4096 * sizeof(float), s) != hipSuccess) ok = false;
-        if (!ok) {
-            (void)hipGetLastError();
-            lg_cnn_free(c);
-            *err = "lg_cnn_load: device allocation/copy failed";
-            return LG_ERR_HIP;
-        }
-    }
-    c->loaded = false;   // until every launch below is in the stream
-
-    // ---- fold + transforms
-    for (int L = 0; L < n_layers; L++) {
-        const RtLayer& l = layers[L];
-        FoldConv a = {v->P + v->conv_w[L], v->P + v->conv_b[L], v->P + v->bn_g[L], v->P + v->bn_b[L], v->B + v->bn_m[L], v->B + v->bn_v[L],
-                      l.cin, l.cout, l.cinp, l.coutp, L == 0 ? 12 : l.cinp, eps};
-        hipLaunchKernelGGL(lg_fold_direct_kernel, dim3((unsigned)((l.cinp * l.coutp + 255) / 256)), dim3(256), 0, s, a, c->bconv[L],
-                           L == 0 || standard ? c->wconv[L] : nullptr);
-        hipLaunchKernelGGL(lg_fold_wino_kernel, dim3((unsigned)((a.cinp4 / 4 * (l.coutp / 16) * 64 + 255) / 256)), dim3(256), 0, s, a,
-                           L >= 1 ? c->uwino[L] : nullptr, c->uwino4[L]);
-    }
-    for (int L = 0; L < 4; L++) {
-        const bool bn = L < 3;
-        hipLaunchKernelGGL(lg_fold_fc_kernel, dim3((unsigned)((dims[L] * dims[L + 1] + 255) / 256)), dim3(256), 0, s, v->P + v->fc_w[L],
-                           v->P + v->fc_b[L], bn ? v->P + v->fbn_g[L] : nullptr, bn ? v->P + v->fbn_b[L] : nullptr,
-                           bn ? v->B + v->fbn_m[L] : nullptr, bn ? v->B + v->fbn_v[L] : nullptr, eps, dims[L], dims[L + 1], c->fcw[L],
-                           c->fcb[L]);
-    }
-    bool ok = hipGetLastError() == hipSuccess;
-    auto D2D = [&](float* dst, size_t off, size_t n) {
-        if (ok && hipMemcpyAsync(dst, v->P + off, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) ok = false;
-    };
-    float att_b = 0.f;
-    if (spatial) {
-        D2D(c->att_w, v->att_w, F);
-        // lg_head_kernel takes the bias by value: the one scalar that comes back to the host
-        if (ok && hipMemcpyAsync(&att_b, v->P + v->att_b, sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) ok = false;
-    }
-    if (channel) { D2D(c->ca_w1, v->ca_w1, (size_t)hid * F); D2D(c->ca_b1, v->ca_b1, hid); D2D(c->ca_w2, v->ca_w2, (size_t)F * hid); D2D(c->ca_b2, v->ca_b2, F); }
-    if (!ok || hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipGetLastError();
-        lg_cnn_free(c);   // half-written weights are no model
-        *err = "lg_cnn_load: device allocation/copy failed";
-        return LG_ERR_HIP;
-    }
-    if (spatial) c->att_b = att_b;
-    // the switches lg_cnn_upload reads when a model is loaded
-    c->use_f23 = getenv("LG_CNN_F23") != nullptr;
-    c->wino_mask = getenv("LG_CNN_DIRECT") ? 0 : 0x3f;
-    if (const char* e = getenv("LG_CNN_WINO_MASK")) c->wino_mask = atoi(e) & 0x3f;
-    c->loaded = true;
-    return LG_OK;
-}
-
 
 // haloed input patch: the 9 feature planes + 3 zero planes (layer 0 runs on the Winograd kernel in chunks of 4 channels)
 size_t lg_cnn_halo_patch_floats(void) { return (size_t)12 * lg_plane(32); }

@@ -113,7 +113,8 @@ class GraspPointSelector:
     def cnn_weights(self, which, layer=0):
         """Inspection: one weight buffer of the loaded CNN as the kernels read it (lg_debug_cnn_weights; `which`: a key of
         _lib.CNNW), float32 numpy array, empty when the model has no such buffer.  'allocs': the number of weight buffers
-        load_from_trainer has allocated on this selector so far (an int; an in-place refresh adds none)."""
+        set_cnn_state_dict and load_from_trainer have allocated on this selector so far (an int; an in-place refresh by
+        load_from_trainer adds none)."""
         n = C.c_int64()
         code = _lib.CNNW[which]
         check(self._h, lib.lg_debug_cnn_weights(self._h, code, int(layer), None, 0, C.byref(n)), "lg_debug_cnn_weights")

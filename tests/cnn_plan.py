@@ -17,7 +17,7 @@ MAX_SLICE = 8192   # lg_cnn_run's max_slice
 
 
 def model_layers(filters=(64, 128, 256)):
-    """(cin, cout, width) of every F(4x4) layer of lg_cnn_upload's layer plan: channels padded to the 64-channel granule,
+    """(cin, cout, width) of every F(4x4) layer of lg_cnn_plan's layer plan: channels padded to the 64-channel granule,
     layer 0 on 12 haloed input planes (the 9 features + 3 zero planes)."""
     out, cin, wi = [], 12, 32
     for f in filters:

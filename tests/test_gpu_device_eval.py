@@ -2,7 +2,12 @@
 (lg_eval_logits, lg_cnn_evaluate; GraspPointSelector.load_from_trainer / evaluate, GraspTrainer.evaluate, fit(device_eval=True)).
 
 The hand-off's contract is bit-identity with the host loader (lg_cnn_load on trainer.state_dict()): every buffer the kernels
-read is compared with np.array_equal, and so are the logits.  The metrics' contract is the host twin (lg_eval_logits_host,
+read is compared with np.array_equal, and so are the logits.  Both entries run one fold (csrc/lg_cnn_load.hip: the host loader
+stages its tensors on the device and runs what the hand-off runs), so their bit-identity follows from the shared path and
+checks the staging and the two entries' plumbing; the bits themselves are pinned by an independent numpy float64 reference
+(tests/cnn_fold_ref.py, proved in tests/test_cnn_fold_ref.py) in test_host_loader_equals_fold_reference.  The loader's
+contract through the raw C-ABI (return codes, messages, what a refused load leaves) is test_loader_contract_through_the_c_abi.
+The metrics' contract is the host twin (lg_eval_logits_host,
 tests/test_eval_host.py checks that one against torch float64): equal counts, loss within 1e-12 * max(1, |ref|) -- the device's
 and the host's exp / log1p differ in ulps only."""
 import ctypes as C
@@ -16,6 +21,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import synthetic_inputs as S  # noqa: E402
 from oracle import lg_oracle as O  # noqa: E402
+from tests import cnn_fold_ref  # noqa: E402
 from tests.test_eval_host import host_eval  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -108,6 +114,87 @@ def test_handoff_equals_host_loader(att, filt):
     assert b.ml_predictor is not None
     assert_same_model(a, b, filt, att)
     assert_same_logits(a, b, state)
+
+
+@pytest.mark.parametrize("att,filt", MODELS)
+def test_host_loader_equals_fold_reference(att, filt):
+    """Every folded / transformed buffer lg_cnn_load leaves on the device equals the numpy float64 reference rounded once, bit
+    for bit; the model has exactly the buffers the reference lists."""
+    state = make_state(att, filt)
+    ref = cnn_fold_ref.fold_reference(state)
+    sel = selector()
+    sel.set_cnn_state_dict(state)
+    for which, layers in (("bconv", 8), ("wconv", 8), ("uwino", 8), ("uwino4", 8), ("fcw", 4), ("fcb", 4)):
+        for layer in range(layers):
+            got = sel.cnn_weights(which, layer)
+            exp = ref.get((which, layer), np.empty(0, np.float32))
+            assert got.shape == exp.shape, (which, layer, got.shape, exp.shape)
+            diff = int((got.view(np.uint32) != exp.view(np.uint32)).sum())
+            print(which, layer, got.size, "floats,", diff, "differ")
+            assert np.array_equal(got.view(np.uint32), exp.view(np.uint32)), (which, layer, diff, got.size)
+
+
+def _hand_packed(filters, att_code, seed=2):
+    """lg_cnn_weights of an encoder cnn.pack_state_dict refuses, filled field by field -> (struct, keepalive)."""
+    from leafgrasp_amd._lib import LgCnnWeights
+    att = {0: "spatial", 1: "channel", 2: "hybrid", 3: "none"}[att_code]
+    state = S.cnn_closed_form_params(seed=seed, attention_type=att, filters=filters)
+    keep = {k: np.ascontiguousarray(v, np.float32) for k, v in state.items()}
+    ptr = lambda k: keep[k].ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    w = LgCnnWeights()
+    w.n_blocks, w.attention_type, w.bn_eps = len(filters), att_code, 1e-5
+    for b, f in enumerate(filters):
+        w.filters[b] = f
+        for j, (conv, bn) in enumerate(((0, 1), (3, 4))):
+            L = 2 * b + j
+            w.conv_w[L], w.conv_b[L] = ptr(f"encoder.{b}.{conv}.weight"), ptr(f"encoder.{b}.{conv}.bias")
+            w.bn_g[L], w.bn_b[L] = ptr(f"encoder.{b}.{bn}.weight"), ptr(f"encoder.{b}.{bn}.bias")
+            w.bn_m[L], w.bn_v[L] = ptr(f"encoder.{b}.{bn}.running_mean"), ptr(f"encoder.{b}.{bn}.running_var")
+    assert att_code == 0, "spatial attention only"
+    w.att_w, w.att_b = ptr("attention.0.weight"), ptr("attention.0.bias")
+    for k, idx in enumerate((0, 4, 8, 12)):
+        w.fc_w[k], w.fc_b[k] = ptr(f"classifier.{idx}.weight"), ptr(f"classifier.{idx}.bias")
+        if k < 3:
+            w.fbn_g[k], w.fbn_b[k] = ptr(f"classifier.{idx + 1}.weight"), ptr(f"classifier.{idx + 1}.bias")
+            w.fbn_m[k], w.fbn_v[k] = ptr(f"classifier.{idx + 1}.running_mean"), ptr(f"classifier.{idx + 1}.running_var")
+    return w, keep
+
+
+def test_loader_contract_through_the_c_abi():
+    """lg_cnn_load through the raw C-ABI: it starts from scratch (a refused load leaves no model), judges the geometry before
+    the tensors and the attention type, and leaves a classifier size without a head kernel to the first forward."""
+    from leafgrasp_amd._lib import LG_ERR_INVALID, LG_ERR_NO_MODEL, LG_ERR_UNSUPPORTED, LG_OK, lib
+    from leafgrasp_amd.cnn import pack_state_dict
+    sel = selector()
+    h = sel._h
+    x, logit = patches(1, 21), torch.zeros(1, dtype=torch.float32, device=DEV)
+    torch.cuda.synchronize()
+    forward = lambda: lib.lg_cnn_forward(h, x.data_ptr(), 1, logit.data_ptr(), None)  # noqa: E731
+    message = lambda: lib.lg_last_error(h).decode()  # noqa: E731
+    state = make_state("spatial", (64, 128, 256))
+
+    # 1. a refused load frees the model that was loaded
+    w, keep = pack_state_dict(state)
+    assert lib.lg_cnn_load(h, C.byref(w)) == LG_OK and forward() == LG_OK
+    w.n_blocks = 5
+    assert lib.lg_cnn_load(h, C.byref(w)) == LG_ERR_UNSUPPORTED
+    assert forward() == LG_ERR_NO_MODEL
+    # 2. a null encoder tensor
+    w, keep = pack_state_dict(state)
+    w.bn_g[3] = None
+    assert lib.lg_cnn_load(h, C.byref(w)) == LG_ERR_INVALID
+    assert "missing encoder tensor" in message()
+    # 3. two blocks [32, 64]: the kernels take the encoder, lg_head_kernel has no instance for 64 filters on 8 x 8 pixels
+    w, keep = _hand_packed((32, 64), 0)
+    assert lib.lg_cnn_load(h, C.byref(w)) == LG_OK, message()
+    assert forward() == LG_ERR_UNSUPPORTED
+    assert "unsupported classifier size" in message()
+    # 4. geometry is judged before the attention type
+    w, keep = pack_state_dict(state)
+    w.attention_type = 7
+    w.filters[1] = 100
+    assert lib.lg_cnn_load(h, C.byref(w)) == LG_ERR_UNSUPPORTED
+    del keep
 
 
 def test_refresh_in_place_after_a_training_step():
