@@ -395,8 +395,8 @@ int lg_debug_dt_search_form(lg_handle h, int32_t* algo);
    H, W >= 16, else 1.  Forcing 5 or 6 gives the same answer whatever the batch; forcing 1 gives 1. */
 int lg_dt_form_host(int forced, int n, int H, int W);
 /* *n = frames of the last lg_score_maps / lg_select_grasp* call that the device orientation kernel handed back (more runs than
-   its scratch holds, LG_ORIENT_CAP) and the host threads analysed; 0 where the host analyses every frame anyway
-   (LG_HOST_ORIENT).
+   its scratch holds: LG_ORIENT_CAP at lg_create, one cap for the handle's life) and the host threads analysed; 0 where the
+   host analyses every frame anyway (LG_HOST_ORIENT at lg_create).
    The small results of a call -- every frame's orientation and status word, the near-tile offsets, the result rows -- are
    written by the kernels straight into the handle's pinned host buffers through their device aliases and read by the host
    behind the events it waits for anyway; LG_DIRECT_HOST=0 at lg_create (or an allocation without an alias): they come back by
@@ -445,8 +445,16 @@ int lg_border_line_max(const int32_t* prof, int n, int lo, int len, uint32_t* ou
 /* off[0 .. B] = first entry of every frame's near tiles in the list the last lg_select_grasp* call on this handle launched its
    plane kernel on (off[0] = 0, off[B] = the list's length; frame b has off[b + 1] - off[b] near tiles).  cap >= B + 1.
    LG_ERR_INVALID when that call did not take the near launch (planes or validity taken back, LG_FINAL_NEAR=0, LG_SUBBATCH,
-   LG_NO_SKIP, LG_FINAL_PERSIST / LG_FINAL_TPW) or cap is too small.  Launches nothing. */
+   LG_NO_SKIP, LG_FINAL_PERSIST / LG_FINAL_TPW, each as the handle found it at lg_create) or cap is too small.  Launches nothing. */
 int lg_debug_near_tiles(lg_handle h, int32_t* off, int cap);
+/* The experiment switches as text, one "NAME=value\n" line per switch ("Experiment switches", has the rows).
+   lg_options_text (host only: no device, no handle): the environment as it is now, through the parser of `which` -- 0 a
+   handle's switches (lg_create), 1 a model's (lg_cnn_load*), 2 a trainer's (lg_train_create).  lg_debug_options: the values the
+   handle stored at lg_create, which hold for its life.  A presence-only switch prints 0 / 1, an unset LG_FINAL_PERSIST /
+   LG_FINAL_TPW -1, LG_CNN_DIRECT shows as LG_CNN_WINO_MASK=0 and LOCAL_WORLD_SIZE in LG_HOST_THREADS.  buf[cap] takes the text,
+   cut to fit and always terminated; returns the length of the whole text, LG_ERR_INVALID for a bad argument. */
+int lg_options_text(int which, char* buf, int cap);
+int lg_debug_options(lg_handle h, char* buf, int cap);
 /* *patches = how many patches the last lg_select_grasp* call on this handle put through the CNN (0 without a model;
    B * top_k where every candidate is scored: lg_select_grasp_candidates*, LG_CNN_PRUNE=0).  Synchronises the device. */
 int lg_debug_cnn_scored(lg_handle h, int64_t* patches);

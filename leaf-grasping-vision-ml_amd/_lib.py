@@ -121,6 +121,8 @@ SYMBOLS = {
     "lg_format_grasp_results": (C.c_int, [_VP, C.c_int, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "lg_debug_dt_form": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int32)]),
     "lg_debug_orient_redo": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
+    "lg_options_text": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
+    "lg_debug_options": (C.c_int, [_VP, C.c_char_p, C.c_int]),
     "lg_debug_dt_search_form": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "lg_dt_form_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "lg_near_tile_rect": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),

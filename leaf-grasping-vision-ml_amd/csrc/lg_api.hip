@@ -2,7 +2,6 @@
 // the side-stream work beside the sweeps (orientation, border maxima, stem bits, bit-row export), per-kernel event timing.  No exceptions cross the boundary.
 #include <math.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -11,10 +10,8 @@
 #include <string>
 #include <atomic>
 #include <memory>
-#include <sched.h>
 #include <condition_variable>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "lg_cnn.h"
@@ -23,6 +20,7 @@
 #include "lg_leaf.h"
 #include "lg_internal.h"
 #include "lg_midrib.h"
+#include "lg_options.h"
 #include "lg_orient.h"
 #include "lg_pool.h"
 
@@ -36,13 +34,6 @@ struct LgProfSlot {
     int launches = 0;
     double total_ms = 0.0;
 };
-
-// list entries per workgroup of the near launch (lg_launch_final; LG_FINAL_NEAR=n overrides).  256 frames of 1080p, plane kernel
-// alone: 1 / 2 / 4 / 8 entries 0.275 / 0.273 / 0.305 / 0.328 ms (profiles/NOTES_near_tiles.md).  The launch applies at every batch
-// size: the enumeration kernel (then in front of the orientation kernel, with a copy) did not lengthen a call of 1 or 32 frames.
-#ifndef LG_FINAL_NEAR_TPW
-#define LG_FINAL_NEAR_TPW 1
-#endif
 
 struct lg_ctx {
     int device = 0;
@@ -92,7 +83,6 @@ struct lg_ctx {
     unsigned long long* bits_host_dev = nullptr;  // device-side alias of bits_host (zero-copy export)
     LgWin* win_host = nullptr;                 // pinned copy of the sweep windows / bounding boxes
     float* ws_maps[LG_NUM_MAPS] = {nullptr};
-    float* ws_maps_base[LG_NUM_MAPS] = {nullptr};  // allocation bases (ws_maps[i] = base + i * skew)
     uint8_t* ws_valid = nullptr;
     int32_t *cand_xy = nullptr, *cand_n = nullptr;
     float *cand_info = nullptr, *patches = nullptr, *logits = nullptr;
@@ -101,7 +91,6 @@ struct lg_ctx {
     int32_t* surv_list = nullptr;             // [B * K] patch slot -> frame * K + candidate, per sub-batch (lg_survivors_kernel)
     int32_t* surv_slot = nullptr;             // [B * K] candidate -> patch slot of its sub-batch, -1: pruned
     int32_t* surv_count = nullptr;            // [B] patches of sub-batch k (one sub-batch by default)
-    bool opt_cnn_prune = true;                // LG_CNN_PRUNE=0: every candidate's patch goes through the CNN (A/B, tests)
     long long last_scored = 0;                // lg_debug_cnn_scored: patches of the last call, when the host knows them;
     int last_scored_subs = 0;                 //   > 0: the sum of surv_count[0 .. last_scored_subs) instead
     // lg_debug_cnn_survivors: the shape of the last lg_select_grasp* call that ran the CNN (last_cnn_B = 0: none) -- frames,
@@ -120,37 +109,15 @@ struct lg_ctx {
     LgLeafProf* leaf_prof = nullptr;   // per-kernel times of the leaf stage (lg_profile_enable)
     LgOrientWs* orient = nullptr;   // device-side orientation scratch (lg_orient.hip)
     hipEvent_t ev_orient = nullptr, ev_side = nullptr, ev_search = nullptr;
-    int opt_dt_algo = 0;            // LG_DT_SEARCH_ALGO=1: one-level row search at every batch size; 5: seed row pairs + stencil bands;
-                                    // 6: one two-wave register sweep per frame; 0: by batch size (lg_dt_form, lg_dt.h)
     int last_dt_algo = 0;           // lg_debug_dt_search_form: the form the row search of the last call took (0: no search was queued)
-    int opt_dt_band_p = 16, opt_dt_band_e = 4;   // LG_DT_BAND_P=12 | 16 | 24 | 32: rows from one seed pair of form 5 to the next;
-                                    // LG_DT_BAND_E=2 | 4: columns per lane of its band kernel (experiments, tests)
-    int opt_dt_search = 2;          // LG_DT_SEARCH=0: d_in by the two sweeps for every frame; 1: by the row search wherever it applies;
-                                    // 2 (default): per frame, the search while the batch's estimated search work stays below the sweeps' latency
     int prof_on = 0;  // 0 off, 1 every kernel (event pairs on the stream), 2 only launches that stamp their own events
     std::vector<LgProfSlot> prof;
-    int host_threads = 8;
     LgPool* pool = nullptr;
-    // experiment switches, read ONCE at lg_create (never on the per-call path)
-    int opt_subbatch = 0;        // LG_SUBBATCH=n: sub-batch multi-stream pipeline inside lg_select_grasp (0 = off)
-    bool opt_trace = false;      // LG_TRACE: per-call timeline on stderr
-    int opt_no_skip = 0;         // LG_NO_SKIP=1: lg_final_kernel without the constant-tile fast path (dense-path roofline);
-                                 //            =3: also without the wave-level off-leaf shortcut
-    int opt_final_near = LG_FINAL_NEAR_TPW;   // LG_FINAL_NEAR=0: lg_final_kernel walks every tile in sparse mode too (the launch before the
-                                 //            near launch; A/B, tests); =n: near launch with n list entries per workgroup
-    bool opt_defer_planes = true;   // LG_DEFER_PLANES=0: sparse calls store and read all six feature planes, as before the deferred mode (A/B, tests)
+    LgOptions opt;               // the experiment switches, read ONCE at lg_create (never on the per-call path): lg_options.h
     long long last_patch_floats = 0;   // lg_debug_patch: floats of h->patches the last lg_select_grasp* call with the CNN could write (0: none)
-    bool opt_nt_stores = false;  // LG_NT_STORES: non-temporal plane stores (measured slower)
-    int opt_side_tail = 1;         // LG_SIDE_TAIL=0: frame-border maxima + stem bits after the sweeps on the caller's stream (round 1); 1: on the
-                                   // side stream behind the orientation kernel; 2: on a third stream
-    int opt_stem_algo = 1;         // LG_STEM_ALGO=0: stem bits by the per-row kernel (A/B, tests); 1: two chains of nested spans
-    bool opt_direct_host = true;   // LG_DIRECT_HOST=0: the small results come back by hipMemcpyAsync (A/B, tests)
     bool export_pending = false;   // this call's bit-row export has not been queued yet (enq_export)
     std::string orient_note;       // why the device-side orientation scratch could not be set up (host analysis is used then)
     std::atomic<bool> busy{false}; // one call in flight per handle (SURVEY 8b "Threading"): a concurrent second call gets LG_ERR_BUSY
-    hipStream_t s_cnn = nullptr;   // LG_CNN_CUS=n: the CNN runs on a stream of its own restricted to n CUs (experiment: room for a second
-    hipEvent_t ev_cnn0 = nullptr, ev_cnn1 = nullptr;   // batch's memory-bound kernels beside it, bench.py --inflight)
-    bool opt_host_orient = false;  // LG_HOST_ORIENT: contour analysis of every frame on the host threads (the round-1 path)
     LgMidribWs* midrib = nullptr;  // lg_clahe / lg_detect_midrib scratch (lg_midrib.hip)
     void* eval_ws = nullptr;       // lg_eval_logits / lg_cnn_evaluate: result, chunk rows and (evaluate without logits_out) the logits
     size_t eval_cap = 0;
@@ -243,7 +210,7 @@ hipError_t dev_alloc(T** p, size_t n) {
 void free_ws(lg_ctx* h) {
     auto F = [](void* p) { if (p) hipFree(p); };
     F(h->tmp); F(h->bits); F(h->stem); F(h->tilekeys); F(h->tile_state); F(h->maxfix); F(h->win); F(h->fp_dev);
-    for (int i = 0; i < LG_NUM_MAPS; i++) { F(h->ws_maps_base[i]); h->ws_maps_base[i] = h->ws_maps[i] = nullptr; }
+    for (int i = 0; i < LG_NUM_MAPS; i++) { F(h->ws_maps[i]); h->ws_maps[i] = nullptr; }
     F(h->ws_valid); F(h->cand_xy); F(h->cand_n); F(h->cand_info); F(h->patches); F(h->logits);
     F(h->surv_keep); F(h->surv_list); F(h->surv_slot); F(h->surv_count);
     F(h->near_off); h->near_off = nullptr; h->last_near_B = 0; h->last_iso_B = 0;
@@ -283,8 +250,8 @@ int ensure_ws(lg_ctx* h, int B, int H, int W, int K) {
     LG_HIP(h, hipHostMalloc((void**)&h->win_host, sizeof(LgWin) * nB));
     LG_HIP(h, hipHostMalloc((void**)&h->bits_host, sizeof(unsigned long long) * words));
     // device-side alias of the pinned image: lg_export_rows_kernel posts only the bounding-box bits into it.
-    // LG_EXPORT_MEMCPY=1 (A/B) or an unmapped allocation: whole-batch hipMemcpyAsync instead.
-    if (getenv("LG_EXPORT_MEMCPY") || hipHostGetDevicePointer((void**)&h->bits_host_dev, h->bits_host, 0) != hipSuccess)
+    // An unmapped allocation: whole-batch hipMemcpyAsync instead.
+    if (hipHostGetDevicePointer((void**)&h->bits_host_dev, h->bits_host, 0) != hipSuccess)
         h->bits_host_dev = nullptr;   // fall back to a full-batch hipMemcpyAsync
     LG_HIP(h, dev_alloc(&h->ws_valid, px));   // validity plane for callers that do not want it back
     LG_HIP(h, dev_alloc(&h->cand_xy, (size_t)nB * nK * 2));
@@ -300,18 +267,18 @@ int ensure_ws(lg_ctx* h, int B, int H, int W, int K) {
     LG_HIP(h, dev_alloc(&h->surv_count, (size_t)nB));
     LG_HIP(h, dev_alloc(&h->res_dev, (size_t)nB));
     LG_HIP(h, hipHostMalloc((void**)&h->res_host, sizeof(lg_grasp_result) * nB));
-    if (h->opt_direct_host) {
+    if (h->opt.direct_host) {
         if (hipHostGetDevicePointer((void**)&h->near_off_host_dev, h->near_off_host, 0) != hipSuccess) h->near_off_host_dev = nullptr;
         if (hipHostGetDevicePointer((void**)&h->fp_host_dev, h->fp_host, 0) != hipSuccess) h->fp_host_dev = nullptr;
         if (hipHostGetDevicePointer((void**)&h->res_host_dev, h->res_host, 0) != hipSuccess) h->res_host_dev = nullptr;
         (void)hipGetLastError();   // (a refused alias only means the copy is made)
     }
-    if (!h->opt_host_orient && H <= 16384 && W <= 8192) {
+    if (!h->opt.host_orient && H <= 16384 && W <= 8192) {
         // no device-side scratch (allocation, or the LDS request on a part with less of it): the host contour analysis of
         // every frame is a complete path of its own -- scoring goes on, the reason stays readable in orient_note
         std::string err;
-        // (LG_ORIENT_FAIL, read here once per workspace: makes the set-up fail -- the test of this hand-over)
-        if (getenv("LG_ORIENT_FAIL") || lg_orient_ensure(h->orient, nB, H, &err)) {
+        // (LG_ORIENT_FAIL makes the set-up fail -- the test of this hand-over)
+        if (h->opt.orient_fail || lg_orient_ensure(h->orient, nB, H, h->opt.orient_cap, &err)) {
             h->orient_note = err.empty() ? "orientation scratch: LG_ORIENT_FAIL is set" : err;
             lg_orient_free(h->orient);
             (void)hipGetLastError();   // the failed allocation's error is sticky until read: it must not fail the call that goes on without it
@@ -325,11 +292,7 @@ int ensure_ws(lg_ctx* h, int B, int H, int W, int K) {
 
 int ensure_ws_map(lg_ctx* h, int i) {  // internal plane when the caller does not want map i
     if (h->ws_maps[i]) return LG_OK;
-    // LG_PLANE_SKEW=<floats>: plane i starts i * skew floats into its allocation, so that the eight planes' equal pixel
-    // offsets do not land on the same HBM channel (experiment; 0 = off)
-    static const size_t skew = getenv("LG_PLANE_SKEW") ? (size_t)atoi(getenv("LG_PLANE_SKEW")) / 4 * 4 : 0;
-    LG_HIP(h, dev_alloc(&h->ws_maps_base[i], (size_t)h->capB * h->capH * h->capW + LG_NUM_MAPS * skew));
-    h->ws_maps[i] = h->ws_maps_base[i] + (size_t)i * skew;
+    LG_HIP(h, dev_alloc(&h->ws_maps[i], (size_t)h->capB * h->capH * h->capW));
     return LG_OK;
 }
 
@@ -419,54 +382,8 @@ int lg_create(int device, lg_handle* out) {
         delete h;
         return LG_ERR_HIP;
     }
-    // host workers: this process's share of the CPUs it may run on (one process per GPU: LOCAL_WORLD_SIZE ranks split the
-    // node), at most 16
-    unsigned hw = std::thread::hardware_concurrency();
-    {
-        cpu_set_t set;
-        CPU_ZERO(&set);
-        if (sched_getaffinity(0, sizeof(set), &set) == 0 && CPU_COUNT(&set) > 0) hw = (unsigned)CPU_COUNT(&set);
-    }
-    unsigned ranks = 1;
-    if (const char* e = getenv("LOCAL_WORLD_SIZE")) ranks = (unsigned)std::max(1, atoi(e));
-    h->host_threads = (int)std::max(1u, std::min((hw ? hw : 1u) / ranks, 16u));
-    if (const char* e = getenv("LG_HOST_THREADS")) h->host_threads = std::max(1, atoi(e));
-    if (const char* e = getenv("LG_SUBBATCH")) h->opt_subbatch = std::max(1, atoi(e));
-    h->opt_trace = getenv("LG_TRACE") != nullptr;
-    if (const char* e = getenv("LG_NO_SKIP")) h->opt_no_skip = std::max(1, atoi(e)) & 3;   // (both bits leave the results unchanged)
-    if (const char* e = getenv("LG_FINAL_NEAR")) h->opt_final_near = std::max(0, std::min(64, atoi(e)));
-    if (getenv("LG_FINAL_PERSIST") || getenv("LG_FINAL_TPW")) h->opt_final_near = 0;   // launch-shape experiments of the full tile walk
-    h->opt_nt_stores = getenv("LG_NT_STORES") != nullptr;
-    h->opt_host_orient = getenv("LG_HOST_ORIENT") != nullptr;
-    if (const char* e = getenv("LG_CNN_PRUNE")) h->opt_cnn_prune = atoi(e) != 0;
-    if (const char* e = getenv("LG_DEFER_PLANES")) h->opt_defer_planes = atoi(e) != 0;
-    if (const char* e = getenv("LG_DT_SEARCH")) h->opt_dt_search = std::max(0, std::min(2, atoi(e)));
-    if (const char* e = getenv("LG_DT_SEARCH_ALGO")) {
-        const int f = atoi(e);
-        if (f == 0 || f == LG_DT_FORM_ROWS || f == LG_DT_FORM_BANDS || f == LG_DT_FORM_SWEEP) h->opt_dt_algo = f;
-    }
-    if (const char* e = getenv("LG_DT_BAND_P")) { const int p = atoi(e); if (p == 12 || p == 16 || p == 24 || p == 32) h->opt_dt_band_p = p; }
-    if (const char* e = getenv("LG_DT_BAND_E")) { const int v = atoi(e); if (v == 2 || v == 4) h->opt_dt_band_e = v; }
-    if (const char* e = getenv("LG_SIDE_TAIL")) h->opt_side_tail = std::max(0, std::min(2, atoi(e)));
-    if (const char* e = getenv("LG_STEM_ALGO")) h->opt_stem_algo = atoi(e) != 0;
-    if (const char* e = getenv("LG_DIRECT_HOST")) h->opt_direct_host = atoi(e) != 0;
-    if (const char* e = getenv("LG_CNN_CUS")) {
-        const int n = atoi(e);
-        int total = 0;
-        hipDeviceGetAttribute(&total, hipDeviceAttributeMultiprocessorCount, device);
-        if (n >= 8 && n < total) {
-            // the CU mask's bits are dealt round-robin to the XCDs: the first n bits = n / 8 CUs on each of the 8 XCDs
-            uint32_t mask[16] = {0};
-            for (int i = 0; i < n / 8 * 8; i++) mask[i >> 5] |= 1u << (i & 31);
-            if (hipExtStreamCreateWithCUMask(&h->s_cnn, (total + 31) / 32, mask) == hipSuccess &&
-                hipEventCreateWithFlags(&h->ev_cnn0, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&h->ev_cnn1, hipEventDisableTiming) == hipSuccess)
-                h->cnn.max_cus = n / 8 * 8;
-            else
-                h->s_cnn = nullptr;
-        }
-    }
-    h->pool = new (std::nothrow) LgPool(h->host_threads - 1);  // the calling thread is the last worker
+    h->opt = lg_options_from_env();
+    h->pool = new (std::nothrow) LgPool(h->opt.host_threads - 1);  // the calling thread is the last worker
     h->leaf_prof = lg_leaf_prof_new();
     *out = h;
     return LG_OK;
@@ -502,10 +419,8 @@ int lg_destroy(lg_handle h) {
         for (auto e : p.ev) hipEventDestroy(e);
     for (auto e : h->ev_pool) hipEventDestroy(e);
     if (h->ev_begin) hipEventDestroy(h->ev_begin);
-    for (hipStream_t q : {h->s_dt[0], h->s_dt[1], h->s_main, h->s_topk, h->s_cnn})
+    for (hipStream_t q : {h->s_dt[0], h->s_dt[1], h->s_main, h->s_topk})
         if (q) hipStreamDestroy(q);
-    if (h->ev_cnn0) hipEventDestroy(h->ev_cnn0);
-    if (h->ev_cnn1) hipEventDestroy(h->ev_cnn1);
     if (h->ev_prep) hipEventDestroy(h->ev_prep);
     if (h->ev_copy) hipEventDestroy(h->ev_copy);
     if (h->copy_stream) hipStreamDestroy(h->copy_stream);
@@ -792,6 +707,11 @@ int lg_debug_orient_redo(lg_handle h, int32_t* n) {
     return LG_OK;
 }
 
+int lg_debug_options(lg_handle h, char* buf, int cap) {
+    if (!h) return LG_ERR_INVALID;
+    return lg_options_print(h->opt, buf, cap);   // (written once, by lg_create: no call in flight changes it)
+}
+
 int lg_debug_dt_form(lg_handle h, int frame, int32_t form[2]) {
     if (!h || !form || frame < 0 || frame >= h->capB || !h->win) return LG_ERR_INVALID;
     LG_ENTER(h);
@@ -914,7 +834,7 @@ int enq_tail(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
         lg_make_stem_plan(se, &sp);
         ProfScope ps(h, "stem", s);
         lg_launch_stem_bits(h->bits + off * words, h->stem + off * words, h->win + off, n, pl.H, pl.W, pl.WW,
-                            third ? pl.H - third : 0, se, h->opt_stem_algo ? &sp : nullptr, s);
+                            third ? pl.H - third : 0, se, h->opt.stem_algo ? &sp : nullptr, s);
     }
     return LG_OK;
 }
@@ -938,7 +858,7 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
     }
     {
         ProfScope ps(h, "bbox", s);
-        lg_launch_window(h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, h->opt_dt_search, s);
+        lg_launch_window(h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, h->opt.dt_search, s);
     }
     LG_HIP(h, hipEventRecord(ev_prep, s));
     LG_HIP(h, hipStreamWaitEvent(h->copy_stream, ev_prep, 0));
@@ -968,7 +888,7 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
         }
         LG_HIP(h, hipEventRecord(h->ev_orient, h->copy_stream));
     }
-    if (h->opt_side_tail) {   // beside the sweeps (latency bound, two workgroups per CU), not behind them: 0.3 ms per 256 frames;
+    if (h->opt.side_tail) {   // beside the sweeps (latency bound, two workgroups per CU), not behind them: 0.3 ms per 256 frames;
         // LG_SIDE_TAIL=2 puts them on a third stream whatever the batch, so that orientation -> border -> stem is not one chain as
         // long as the sweeps themselves -- measured slower at 256 frames (9.76-9.94 vs 9.56-9.77 ms per step, three alternating runs;
         // again with form 5 of the search, whose chain is the shorter one: 2.196, 2.199 vs 2.135, 2.162 ms, NOTES_dt_bands; and
@@ -982,7 +902,7 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
         // stream were the longest chain between the bit rows and the plane kernel of a single-frame call (0.22 ms; the row search
         // beside them takes 0.10).  Up to 32 frames the border maxima and the stem bits go to a stream of their own (s_dt[0]; the
         // search uses s_dt[1]).
-        const bool own_tail = h->opt_subbatch == 0 && (h->opt_side_tail == 2 || n <= 32);
+        const bool own_tail = h->opt.subbatch == 0 && (h->opt.side_tail == 2 || n <= 32);
         hipStream_t ts = own_tail ? h->s_dt[0] : h->copy_stream;
         if (ts != h->copy_stream) LG_HIP(h, hipStreamWaitEvent(ts, ev_prep, 0));
         const int rc = enq_tail(h, pl, off, n, ts);
@@ -1019,13 +939,13 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
     hipStream_t ss = (s == h->s_dt[0] || s == h->s_dt[1]) ? s : h->s_dt[1];
     h->last_dt_algo = 0;
     h->last_iso_B = 0;   // (the sweeps' scratch held the fields of an earlier label-aware call)
-    if (h->opt_dt_search) {
+    if (h->opt.dt_search) {
         if (ss != s) LG_HIP(h, hipStreamWaitEvent(ss, h->ev_prep, 0));
         {
             ProfScope ps(h, "dt_hrun", ss);
             lg_launch_hrun(h->bits + off * words, h->tmp + 2 * off * px, h->win + off, n, pl.H, pl.W, pl.WW, ss);
         }
-        const int form = lg_dt_form(h->opt_dt_algo, n, pl.H, pl.W);
+        const int form = lg_dt_form(h->opt.dt_algo, n, pl.H, pl.W);
         h->last_dt_algo = form;
         const unsigned long long* bits = h->bits + off * words;
         uint32_t *tmp = h->tmp + 2 * off * px, *maxfix = h->maxfix + LG_MF * (size_t)off;
@@ -1034,14 +954,14 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
         {
             ProfScope ps(h, "dt_search", ss);   // the one-level search, the seed rows, or the whole box by the register sweep
             switch (form) {
-                case LG_DT_FORM_BANDS: lg_launch_dt_seeds(bits, tmp, dist, maxfix, win, n, pl.H, pl.W, pl.WW, h->opt_dt_band_p, ss); break;
+                case LG_DT_FORM_BANDS: lg_launch_dt_seeds(bits, tmp, dist, maxfix, win, n, pl.H, pl.W, pl.WW, h->opt.dt_band_p, ss); break;
                 case LG_DT_FORM_SWEEP: lg_launch_dt_sweep(tmp, dist, maxfix, win, n, pl.H, pl.W, ss); break;
                 default: lg_launch_dt_rows(bits, tmp, dist, maxfix, win, n, pl.H, pl.W, pl.WW, ss); break;
             }
         }
         if (form == LG_DT_FORM_BANDS) {
             ProfScope ps(h, "dt_band", ss);     // the rows between the seed pairs
-            lg_launch_dt_bands(bits, tmp, dist, maxfix, win, n, pl.H, pl.W, pl.WW, h->opt_dt_band_p, h->opt_dt_band_e, ss);
+            lg_launch_dt_bands(bits, tmp, dist, maxfix, win, n, pl.H, pl.W, pl.WW, h->opt.dt_band_p, h->opt.dt_band_e, ss);
         }
         if (ss != s) LG_HIP(h, hipEventRecord(h->ev_search, ss));
     }
@@ -1056,8 +976,8 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
         lg_launch_dt(true, pl.mask + off * px, h->tmp + 2 * off * px, pl.maps[LG_MAP_DISTANCE] + off * px,
                      h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, (uint32_t)pl.P.chamfer_init_dist0, s);
     }
-    if (h->opt_dt_search && ss != s) LG_HIP(h, hipStreamWaitEvent(s, h->ev_search, 0));
-    if (!h->opt_side_tail) return enq_tail(h, pl, off, n, s);
+    if (h->opt.dt_search && ss != s) LG_HIP(h, hipStreamWaitEvent(s, h->ev_search, 0));
+    if (!h->opt.side_tail) return enq_tail(h, pl, off, n, s);
     return LG_OK;
 }
 
@@ -1109,7 +1029,7 @@ int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upl
     const int H = pl.H, W = pl.W;
     const lg_params& P = pl.P;
     if (h->orient) LG_HIP(h, hipStreamWaitEvent(s, h->ev_orient, 0));   // fp_dev was written on the side stream
-    if (h->opt_side_tail) LG_HIP(h, hipStreamWaitEvent(s, h->ev_side, 0));  // maxfix (d_out border) and the stem bits
+    if (h->opt.side_tail) LG_HIP(h, hipStreamWaitEvent(s, h->ev_side, 0));  // maxfix (d_out border) and the stem bits
     if (upload_fp) LG_HIP(h, hipMemcpyAsync(h->fp_dev + off, h->fp_host + off, sizeof(LgFrameParams) * n, hipMemcpyHostToDevice, s));
     LgFinalArgs a;
     memset(&a, 0, sizeof(a));
@@ -1144,14 +1064,15 @@ int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upl
     a.iso_ramp_step = (H > 1) ? (P.iso_ramp_bottom - P.iso_ramp_top) / (float)(H - 1) : 0.0f;
     gaussian1d(P.gaussian_size, a.k1);
     a.gauss_r = P.gaussian_size / 2;
-    a.no_skip = h->opt_no_skip;
-    a.persist = 0;   // (lg_launch_final: the tile walk stays an experiment switch)
-    a.nt_stores = h->opt_nt_stores ? 1 : 0;  // measured: non-temporal plane stores are slower here (0.57 vs 0.50 ms)
+    a.no_skip = h->opt.no_skip;
+    a.persist = h->opt.final_persist;   // (lg_launch_final: the tile walk and the tiles per workgroup stay experiment switches)
+    a.tpw = h->opt.final_tpw;
+    a.nt_stores = 0;
     if (pl.near) {   // (one sub-batch: off = 0, n = B)
         LG_HIP(h, hipEventSynchronize(h->ev_near));   // near_off_host is written (the kernel ended long ago: it follows the bit-row pass)
         a.near_off = h->near_off;
         a.near_total = h->near_off_host[n];
-        a.near_tpw = h->opt_final_near;
+        a.near_tpw = h->opt.final_near;
     }
     {
         ProfScope ps(h, "final", s, true);
@@ -1382,7 +1303,7 @@ int lg_clahe(lg_handle h, const uint8_t* src, int B, int H, int W, double clip_l
     LG_HIP(h, hipSetDevice(h->device));
     const int ntiles = tiles_x * tiles_y;
     std::string err;
-    if (lg_midrib_ensure(h->midrib, B, H, W, ntiles, false, false, &err)) return fail(h, LG_ERR_NOMEM, err.c_str());
+    if (lg_midrib_ensure(h->midrib, B, H, W, ntiles, false, false, h->opt.orient_cap, &err)) return fail(h, LG_ERR_NOMEM, err.c_str());
     LG_HIP(h, hipMemsetAsync(h->midrib->hist, 0, sizeof(int) * (size_t)B * ntiles * 256, s));
     {
         ProfScope ps(h, "clahe_hist", s);
@@ -1411,8 +1332,8 @@ int lg_detect_midrib(lg_handle h, const uint8_t* image, int C, const uint8_t* ma
     LG_HIP(h, hipSetDevice(h->device));
     const int ntiles = 64, WW = (W + 63) / 64;
     std::string err;
-    const bool dev_orient = !h->opt_host_orient && H <= 16384 && W <= 8192;   // lg_leaf_orientation's condition (ensure_ws)
-    if (lg_midrib_ensure(h->midrib, B, H, W, ntiles, true, dev_orient, &err)) return fail(h, LG_ERR_NOMEM, err.c_str());
+    const bool dev_orient = !h->opt.host_orient && H <= 16384 && W <= 8192;   // lg_leaf_orientation's condition (ensure_ws)
+    if (lg_midrib_ensure(h->midrib, B, H, W, ntiles, true, dev_orient, h->opt.orient_cap, &err)) return fail(h, LG_ERR_NOMEM, err.c_str());
     LgMidribWs* m = h->midrib;
     // CLAHE(clipLimit=3.0, tileGridSize=(8,8)) of the masked gray (:834-843): histograms and LUTs; the enhanced image itself is
     // evaluated by the walk at its samples only
@@ -1835,11 +1756,11 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     // The CNN on the candidates that can still win only (the result row needs no other; the candidates entry reports an ML
     // score for every candidate and scores them all).  Either way no item of the CNN is split: a patch's logit then does not
     // depend on how many patches run beside it, and the rows of both entries, pruned or not, are equal bit for bit.
-    const bool prune = use_cnn && !cands && h->opt_cnn_prune && lg_cnn_counts_on_device(&h->cnn);
+    const bool prune = use_cnn && !cands && h->opt.cnn_prune && lg_cnn_counts_on_device(&h->cnn);
     h->last_scored = use_cnn ? (long long)B * P.top_k : 0;
     h->last_scored_subs = 0;
     h->last_cnn_B = 0;
-    pl.defer = pl.sparse && h->opt_defer_planes;
+    pl.defer = pl.sparse && h->opt.defer_planes;
     // all eight planes are needed when the CNN rescoring runs and the planes are not deferred (deferred: flatness, which the
     // gather still reads); otherwise only distance + traditional
     for (int i = 0; i < LG_NUM_MAPS; i++)
@@ -1863,11 +1784,11 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
     // Measured on MI355X (B=128, 1080p): SB=32 is 14.8 ms/step vs 11.5 ms unpiped -- the chain
     // D(0)->F(0)->T(0) must drain before the first CNN launch, and D's latency does not shrink with SB.
     // Kept for experiments (LG_SUBBATCH=n in the environment when the handle is created); the default is one sub-batch.
-    if (h->opt_subbatch > 0 && !pl.label_aware) SB = h->opt_subbatch;   // (the label-aware transforms reuse the sweeps' scratch: one sub-batch)
+    if (h->opt.subbatch > 0 && !pl.label_aware) SB = h->opt.subbatch;   // (the label-aware transforms reuse the sweeps' scratch: one sub-batch)
     const int nsub = (B + SB - 1) / SB;
     const bool piped = nsub > 1;
     std::vector<LgFinalArgs> fargs((size_t)nsub);   // the plane launches' arguments, for the deferred gather
-    pl.near = pl.sparse && h->opt_final_near > 0 && h->opt_subbatch == 0 && h->opt_no_skip == 0;
+    pl.near = pl.sparse && h->opt.final_near > 0 && h->opt.subbatch == 0 && h->opt.no_skip == 0;
     h->last_near_B = 0;
     hipStream_t sD[2] = {piped ? h->s_dt[0] : s, piped ? h->s_dt[1] : s};
     hipStream_t sM = piped ? h->s_main : s, sT = piped ? h->s_topk : s;
@@ -1903,26 +1824,16 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
                                  pl.defer ? &fargs[k] : nullptr, pl.label_aware ? &iso_fields : nullptr);
             }
             std::string err;
-            hipStream_t sC = sM;
-            if (h->s_cnn) {   // experiment: the CNN on its CU-masked stream, ordered after the gather and before the copy-back
-                sC = h->s_cnn;
-                LG_HIP(h, hipEventRecord(h->ev_cnn0, sM));
-                LG_HIP(h, hipStreamWaitEvent(sC, h->ev_cnn0, 0));
-            }
             {
-                ProfScope ps(h, "cnn", sC);
-                int r2 = lg_cnn_run(&h->cnn, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, n * K, h->logits + (size_t)off * K, sC, &err,
+                ProfScope ps(h, "cnn", sM);
+                int r2 = lg_cnn_run(&h->cnn, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, n * K, h->logits + (size_t)off * K, sM, &err,
                                     false, count);
                 if (r2) return fail(h, r2, err.c_str());
-            }
-            if (h->s_cnn) {
-                LG_HIP(h, hipEventRecord(h->ev_cnn1, sC));
-                LG_HIP(h, hipStreamWaitEvent(sM, h->ev_cnn1, 0));
             }
         }
         return LG_OK;
     };
-    const bool trace = h->opt_trace;
+    const bool trace = h->opt.trace;
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_start = now();
     hipEvent_t tev[6] = {nullptr};

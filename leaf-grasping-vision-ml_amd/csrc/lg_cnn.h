@@ -36,7 +36,6 @@ bool lg_head_supported(int F, int npix);                     // the instances of
 // here: a slot the table does not list for them is null.
 struct LgCnn : LgCnnPlan {
     bool loaded = false;
-    int max_cus = 0;              // > 0: the persistent conv kernels take this many workgroups (CUs) instead of all (LG_CNN_CUS experiment)
     float* wconv[8] = {nullptr};  // packed [ky][kx][cin_pad][cout], BN folded (layer 0; all layers of the standard model)
     float* bconv[8] = {nullptr};
     float* uwino[8] = {nullptr};  // Winograd F(2x2,3x3) weights [cin][cout][16] (layers 1..)

@@ -1305,7 +1305,6 @@ bool launch_wino_rt(int cin, int cout, int wi, bool pool, bool out_halo, const f
 }
 
 #define LG_WINO4_L0_SHAPES(X) X(12, 64, 32, false) X(12, 128, 32, false)
-// max_cus > 0: workgroups (= CUs) the persistent F(4x4) kernels may take (LgCnn::max_cus, the LG_CNN_CUS experiment)
 // workgroups of the persistent F(4x4) kernels, at most (= CUs; a multiple of 8 so every XCD gets the same number)
 static int lg_w4_num_cu() {
     static const int num_cu = [] {
@@ -1318,14 +1317,13 @@ static int lg_w4_num_cu() {
 constexpr size_t LG_W4_KPART_FLOATS = 16 * 512 * 4;   // partial outputs of one workgroup (lg_wino4_kernel, split items)
 
 bool launch_wino4_rt(int cin, int cout, int wi, bool pool, bool out_halo, const float* in, const float* U4, const float* bias,
-                     float* out, int N, int max_cus, float* kpart, unsigned* kflag, unsigned* kerr, hipStream_t s,
+                     float* out, int N, float* kpart, unsigned* kflag, unsigned* kerr, hipStream_t s,
                      bool allow_split = true, const int* n_dev = nullptr, int n_off = 0) {
     const int tp = (wi / 4) * (wi / 4);
     const int ntb = tp >= 32 ? N * (tp / 32) : (N + 32 / tp - 1) / (32 / tp);
     // persistent: one 512-thread workgroup per CU (140-156 KB of LDS each)
-    const int num_cu = lg_w4_num_cu();
+    const int cus = lg_w4_num_cu();
     const long long items8 = (long long)((ntb + 7) / 8) * (cout / 64);   // items per XCD
-    const int cus = max_cus > 0 ? std::max(8, std::min(num_cu, max_cus / 8 * 8)) : num_cu;
     // Left-over items (fewer items than workgroups, or a last round that fills only some of them) are split along the input
     // channels over P workgroups each -- when that pays: the parts' exchange costs ~18 (P = 4) to ~26 us (P = 8), a part saves
     // (1 - 1/P) of an item's cin / 4 chunks of ~1.1 us (measured per layer at 20 and 640 patches, profiles/r04_cnn_split_items.txt:
@@ -1453,7 +1451,7 @@ static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int 
     }
     // layer 0: the F(4x4,3x3) kernel on 12 input planes (3 chunks); the direct 9-channel kernel with LG_CNN_DIRECT / _F23 / mask bit 0 clear
     if (!c->use_f23 && (c->wino_mask & 1) &&
-        launch_wino4_rt(12, c->layers[0].coutp, 32, false, true, x, c->uwino4[0], c->bconv[0], c->act[0], N, c->max_cus, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off)) {
+        launch_wino4_rt(12, c->layers[0].coutp, 32, false, true, x, c->uwino4[0], c->bconv[0], c->act[0], N, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off)) {
         // (a shape the F(4x4) table lacks falls through to the direct kernel instead of leaving act[0] unwritten)
     } else if (c->layers[0].coutp == 64) launch_conv0<64>(x, c, c->act[0], N, s);
     else launch_conv0<128>(x, c, c->act[0], N, s);
@@ -1465,7 +1463,7 @@ static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int 
         const RtLayer& l = c->layers[L];                                                                            \
         if (!(wmask & (1 << L))) launch_conv<L, KC, PP, CP>(cur, c, c->act[L], N, s);                               \
         else if (c->use_f23) launch_wino_rt(l.cinp, l.coutp, l.wi, l.pool, L != 5, cur, c->uwino[L], c->bconv[L], c->act[L], N, s); \
-        else launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L != 5, cur, c->uwino4[L], c->bconv[L], c->act[L], N, c->max_cus, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off); \
+        else launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L != 5, cur, c->uwino4[L], c->bconv[L], c->act[L], N, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off); \
         cur = c->act[L];                                                                                            \
     } while (0)
         LG_LAYER(1, 8, 4, 1);   // 64 -> 64, pool -> 16x16
@@ -1478,7 +1476,7 @@ static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int 
         for (int L = 1; L < c->n_layers; L++) {
             const RtLayer& l = c->layers[L];
             const bool okl = c->use_f23 ? launch_wino_rt(l.cinp, l.coutp, l.wi, l.pool, L + 1 < c->n_layers, cur, c->uwino[L], c->bconv[L], c->act[L], N, s)
-                                        : launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L + 1 < c->n_layers, cur, c->uwino4[L], c->bconv[L], c->act[L], N, c->max_cus, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off);
+                                        : launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L + 1 < c->n_layers, cur, c->uwino4[L], c->bconv[L], c->act[L], N, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off);
             if (!okl) {
                 *err = "lg_cnn_forward: unsupported layer shape";
                 return LG_ERR_UNSUPPORTED;

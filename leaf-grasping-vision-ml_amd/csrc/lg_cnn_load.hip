@@ -3,9 +3,9 @@
 // PyTorch-layout tensors come from; everything after that -- plan, allocation, BatchNorm fold, Winograd transforms, fragment
 // orders, load-time switches -- is build_weights() below, once.
 #include "lg_cnn.h"
+#include "lg_options.h"
 
 #include <math.h>
-#include <stdlib.h>
 
 #include <algorithm>
 #include <vector>
@@ -260,9 +260,9 @@ int build_weights(LgCnn* c, const LgCnnPlan& p, const LgTrainView* v, hipStream_
     // A/B and test switches of the standard encoder, read when a model is loaded (not on the per-call path):
     // LG_CNN_DIRECT=1 direct implicit GEMM for every layer; LG_CNN_WINO_MASK=<bits> bit L = layer L on Winograd
     // LG_CNN_F23=1 the F(2x2,3x3) Winograd kernels instead of F(4x4,3x3)
-    c->use_f23 = getenv("LG_CNN_F23") != nullptr;
-    c->wino_mask = getenv("LG_CNN_DIRECT") ? 0 : 0x3f;
-    if (const char* e = getenv("LG_CNN_WINO_MASK")) c->wino_mask = atoi(e) & 0x3f;
+    const LgCnnOptions o = lg_cnn_options_from_env();
+    c->use_f23 = o.f23;
+    c->wino_mask = o.wino_mask;
     c->loaded = true;
     return LG_OK;
 }

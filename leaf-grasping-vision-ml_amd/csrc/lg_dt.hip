@@ -7,7 +7,6 @@
 #include <limits.h>
 #include <algorithm>
 #include <type_traits>
-#include <stdlib.h>
 
 // ============================================================================ wave helpers of the distance transform
 __device__ __forceinline__ int lg_dpp_row_shr(int old, int v, int n) {
@@ -94,11 +93,8 @@ void lg_launch_window(const uint32_t* mf, LgWin* win, int B, int H, int W, int s
     int nw = 0;
     const int wc = lg_dt_geometry(W, &nw);
     // mode 2: search while sum over the frames of area^1.5 <= LG_SEARCH_BUDGET * rows of the tallest window: 0.69 ms for 256
-    // benchmark leaves of 100 k pixels in either form (anchors + bands; sweeps: ~1.6 us per row).  LG_DT_SEARCH_BUDGET=<x>
-    // replaces the constant (experiments).
-    static const float env_budget = getenv("LG_DT_SEARCH_BUDGET") ? (float)atof(getenv("LG_DT_SEARCH_BUDGET")) : 0.0f;
-    hipLaunchKernelGGL(lg_window_kernel, dim3(1), dim3(1024), 0, s, mf, win, B, H, W, wc, nw, search_mode,
-                       env_budget > 0.0f ? env_budget : LG_SEARCH_BUDGET);
+    // benchmark leaves of 100 k pixels in either form (anchors + bands; sweeps: ~1.6 us per row).
+    hipLaunchKernelGGL(lg_window_kernel, dim3(1), dim3(1024), 0, s, mf, win, B, H, W, wc, nw, search_mode, LG_SEARCH_BUDGET);
 }
 
 // ============================================================================ max d_out outside the sweep window
@@ -464,12 +460,8 @@ static void lg_dt_launch_t(bool bwd, const uint8_t* mask, uint32_t* tmp, float* 
 
 // threads x columns-per-thread of the sweep workgroup for width W: returns 64 * E, *waves = T / 64 (0: unsupported)
 int lg_dt_geometry(int W, int* waves) {
-    static const int force_e = getenv("LG_DT_E") ? atoi(getenv("LG_DT_E")) : 0;
     int T, E;
-    if (force_e == 8) {
-        E = 8;
-        T = W <= 512 ? 64 : W <= 1024 ? 128 : W <= 2048 ? 256 : W <= 4096 ? 512 : W <= 8192 ? 1024 : 0;
-    } else if (W <= 2048) {
+    if (W <= 2048) {
         E = 4;
         T = W <= 256 ? 64 : W <= 512 ? 128 : W <= 1024 ? 256 : 512;
     } else {
@@ -484,17 +476,6 @@ int lg_launch_dt(bool bwd, const uint8_t* mask, uint32_t* tmp, float* dist_out, 
                  int H, int W, uint32_t init0, hipStream_t s) {
     // threads * E columns must cover the row.  E = 4 keeps the per-row dependency chain short (best up to
     // 2048 columns: 0.70/0.82 ms vs 0.82/0.91 ms at 1080p); at 4K 512x8 beats 1024x4 (2.04/2.54 vs 2.65/3.12 ms).
-    // LG_DT_E=8 forces 8 columns per thread (experiments).
-    static const int force_e = getenv("LG_DT_E") ? atoi(getenv("LG_DT_E")) : 0;
-    if (force_e == 8) {
-        if (W <= 512) lg_dt_launch_t<64, 8>(bwd, mask, tmp, dist_out, maxfix, win, B, H, W, init0, s);
-        else if (W <= 1024) lg_dt_launch_t<128, 8>(bwd, mask, tmp, dist_out, maxfix, win, B, H, W, init0, s);
-        else if (W <= 2048) lg_dt_launch_t<256, 8>(bwd, mask, tmp, dist_out, maxfix, win, B, H, W, init0, s);
-        else if (W <= 4096) lg_dt_launch_t<512, 8>(bwd, mask, tmp, dist_out, maxfix, win, B, H, W, init0, s);
-        else if (W <= 8192) lg_dt_launch_t<1024, 8>(bwd, mask, tmp, dist_out, maxfix, win, B, H, W, init0, s);
-        else return -1;
-        return 0;
-    }
     if (W <= 256) lg_dt_launch_t<64, 4>(bwd, mask, tmp, dist_out, maxfix, win, B, H, W, init0, s);
     else if (W <= 512) lg_dt_launch_t<128, 4>(bwd, mask, tmp, dist_out, maxfix, win, B, H, W, init0, s);
     else if (W <= 1024) lg_dt_launch_t<256, 4>(bwd, mask, tmp, dist_out, maxfix, win, B, H, W, init0, s);
@@ -1214,12 +1195,10 @@ void lg_launch_hrun(const unsigned long long* bits, uint32_t* tmp, const LgWin* 
     hipLaunchKernelGGL(lg_hrun_kernel, dim3(8u * G * ((B + 7) / 8)), dim3(256), 0, s, bits, win, tmp, H, W, WW, G, B);
 }
 // The row, seed and band kernels take the same arguments and the same grid: G workgroups per frame, dealt to the XCDs as
-// lg_frame_of_block expects.  LG_DT_SEARCH_G=<G> replaces every launcher's own G (experiments).
+// lg_frame_of_block expects.
 template <class K>
 static void lg_launch_search(K kernel, int G, const unsigned long long* bits, uint32_t* tmp, float* dist_out, uint32_t* maxfix,
                              const LgWin* win, int B, int H, int W, int WW, hipStream_t s) {
-    static const int g_env = getenv("LG_DT_SEARCH_G") ? atoi(getenv("LG_DT_SEARCH_G")) : 0;
-    if (g_env > 0) G = g_env;
     hipLaunchKernelGGL(kernel, dim3(8u * (unsigned)((B + 7) / 8) * G), dim3(256), 0, s, bits, win, tmp, dist_out, maxfix, H, W, WW,
                        lg_dt_geometry(W, nullptr), G, B);
 }

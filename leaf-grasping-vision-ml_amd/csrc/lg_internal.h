@@ -423,9 +423,10 @@ struct LgFinalArgs {
     float k1[7];  // separable 1-D Gaussian: 2 * gauss_r + 1 taps, sigma = size / 6 (image_processor.py:25-32)
     int gauss_r;    // radius of that Gaussian: 0..3 (lg_params.gaussian_size 1, 3, 5, 7)
     int no_skip;    // bit 0: tile-level constant path off, bit 1: wave-level off-leaf shortcut off (LG_NO_SKIP; same results, A/B timing)
-    int nt_stores;  // 0: plain stores (default); 1: non-temporal plane stores (LG_NT_STORES=1; measured slower)
-    int persist;    // 1: resident workgroups walk the tiles (lg_launch_final); 0: one workgroup per tile
-    int tpw;        // > 0: consecutive tiles per workgroup (set by lg_launch_final)
+    int nt_stores;  // always 0: plain plane stores (1: non-temporal, measured slower; no switch selects it any more, the kernel's text
+                    // stays as measured: profiles/NOTES_options.md, section 3)
+    int persist;    // from the caller, LgOptions::final_persist: resident workgroups per CU that walk the tiles (< 0: the mode's default)
+    int tpw;        // > 0: consecutive tiles per workgroup (from the caller LgOptions::final_tpw; lg_launch_final leaves what the kernel reads)
     // near launch (sparse mode): the workgroups take the entries of the batch's list of near tiles (lg_near_tiles) instead of
     // every tile; the far tiles' keys and state bytes were written by lg_launch_near_tiles.  null: every tile
     const int32_t* near_off;   // [B + 1] DEVICE: first list entry of every frame, near_off[B] = near_total

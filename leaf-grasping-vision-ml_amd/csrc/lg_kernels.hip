@@ -944,23 +944,21 @@ void lg_launch_final(const LgFinalArgs& a_in, hipStream_t s, hipEvent_t ev_start
     long long total = (long long)a_in.tiles_x * a_in.tiles_y * a_in.B;   // < 2^31: tiles_x * tiles_y <= 8192 (make_plan), B is an int count of frames that fit in memory
     // Launch form.  Dense mode: one workgroup per tile by default (sparse mode: LG_FINAL_SPARSE_TPW above): on real frames
     // most tiles take the constant path and the dispatcher's own load balancing beats a fixed stride (2.71 vs 3.12 ms per 256
-    // frames).  LG_FINAL_PERSIST=n (or a.persist): n resident
+    // frames).  LG_FINAL_PERSIST=n (a.persist): n resident
     // workgroups per CU (a multiple of 8 workgroups, so that blockIdx % 8 stays the XCD) walk the tiles.  With every tile on
     // the stencil path the walk measured 5 % faster on three boxes (2.10 vs 2.21 ms per 128 frames; its arithmetic alone 1.14
     // vs 1.42 ms) and 25 % SLOWER on a fourth, faster one (2.28-2.33 vs 1.80-1.87 ms): a wave's loads for its next tile queue
     // behind its own plane stores (vmcnt retires in order), which costs more the faster the memory side is.  Off by default.
-    static const int persist_env = getenv("LG_FINAL_PERSIST") ? atoi(getenv("LG_FINAL_PERSIST")) : -1;
     static const int cus = [] {
         int dev = 0, n = 256;
         hipGetDevice(&dev);
         hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
         return n;
     }();
-    const int per_cu = persist_env >= 0 ? persist_env : (a_in.persist ? LG_FINAL_WPE : a_in.sparse ? LG_FINAL_SPARSE_PERSIST : 0);
+    const int per_cu = a_in.persist >= 0 ? a_in.persist : a_in.sparse ? LG_FINAL_SPARSE_PERSIST : 0;
     const int resident = per_cu > 0 ? std::max(8, cus * per_cu / 8 * 8) : 0;
-    // LG_FINAL_TPW=n: n consecutive tiles per workgroup (experiment: 2 / 4 / 8 change the benchmark launch by -1 / +1 / +3 %,
+    // LG_FINAL_TPW=n (a.tpw): n consecutive tiles per workgroup (experiment: 2 / 4 / 8 change the benchmark launch by -1 / +1 / +3 %,
     // the dense launch within the noise: the workgroup launch rate is not what limits either)
-    static const int tpw_env = getenv("LG_FINAL_TPW") ? atoi(getenv("LG_FINAL_TPW")) : -1;
     LgFinalArgs a = a_in;
     // Near launch (a.near_off; the caller offers it in sparse mode only and never beside the experiment switches above): the
     // list of near tiles takes the place of the tile grid, near_tpw consecutive entries per workgroup.  An empty list launches
@@ -975,7 +973,7 @@ void lg_launch_final(const LgFinalArgs& a_in, hipStream_t s, hipEvent_t ev_start
         a.near_tpw = std::max(1, a.near_tpw);
     }
     const bool walk = !near && resident && total > 2ll * resident;
-    a.tpw = walk ? 0 : std::max(0, tpw_env >= 0 ? tpw_env : a.sparse ? LG_FINAL_SPARSE_TPW : 0);
+    a.tpw = walk ? 0 : std::max(0, a_in.tpw >= 0 ? a_in.tpw : a.sparse ? LG_FINAL_SPARSE_TPW : 0);
     const int tpw = near ? a.near_tpw : a.tpw;
     const long long per_xcd = (total + 7) / 8;
     const unsigned grid = (unsigned)(walk ? resident : tpw > 1 ? 8 * ((per_xcd + tpw - 1) / tpw) : total);

@@ -31,6 +31,9 @@
 #define LGL_ACC_LDS 256      // slots whose sums are aggregated in LDS (beyond: global atomics)
 #define LGL_RUN 16           // consecutive pixels per thread (run-length aggregation before atomics)
 #define LGL_QCAP 65536       // survivor list capacity of the branch-and-bound pass (entries per frame and list)
+#ifndef LG_LEAF_ABLATE       // timing ablation builds only (tools/leaf_ablate.sh; wrong results by design), the kernels' `ablate` argument:
+#define LG_LEAF_ABLATE 0     // k_accumulate without 1 its list stores, 2 its accumulator atomics, 4 the ray sum; 8 k_hist without its
+#endif                       // histogram atomics.  (An argument, not a constant: profiles/NOTES_options.md, section 3)
 
 namespace {
 
@@ -1132,15 +1135,13 @@ int lg_leaf_run_batch(LgLeafWs*& w, const int16_t* labels, const float* depth, i
     const int WW = (W + 63) / 64;
     // streaming passes: grid-stride workgroups per frame; fewer per frame for large batches (every workgroup ends with a
     // flush of its LDS accumulators / 64 KB histogram into global atomics)
-    static const int gx_budget = getenv("LG_LEAF_GX") ? atoi(getenv("LG_LEAF_GX")) : 2048;   // workgroups per batch of the streaming passes
-    const int gx = std::max(16, std::min(256, gx_budget / B));
+    const int gx = std::max(16, std::min(256, 2048 / B));   // 2048 workgroups per batch of the streaming passes
     const dim3 grid(gx, B);
     // list segments: workgroup x of a frame meets at most ceil(runs / (gx * 256)) steps of 256 runs of 16 pixels (k_accumulate
     // walks tiles of 4 x 16 runs: the run count is the padded one)
     const long long nruns_acc = (long long)(((W + LGL_RUN - 1) / LGL_RUN + 3) / 4) * ((H + 15) / 16) * 64;
     const unsigned segcap = (unsigned)((nruns_acc + (long long)gx * 256 - 1) / ((long long)gx * 256)) * 256u * LGL_RUN;
     const size_t comp_stride = (size_t)segcap * gx;          // <= H * W + gx * 4096 entries per frame
-    static const int ablate = getenv("LG_LEAF_ABLATE") ? atoi(getenv("LG_LEAF_ABLATE")) : 0;   // timing experiments only (wrong results)
     hipMemsetAsync(w->pres, 0, nb * 512 * 8, s);
     hipMemsetAsync(w->acc, 0, nb * sizeof(LeafAcc) * LGL_MAXL, s);
     hipMemsetAsync(w->first_leaf, 0xFF, nb * 8, s);
@@ -1165,7 +1166,7 @@ int lg_leaf_run_batch(LgLeafWs*& w, const int16_t* labels, const float* depth, i
     hipLaunchKernelGGL(k_prefix, dim3(B), dim3(64), 0, s, w->pres, w->pre, w->nlab);
     {
         LeafProfScope ps(prof, "leaf_accumulate", s);
-        hipLaunchKernelGGL(k_accumulate, grid, dim3(256), 0, s, labels, depth, H, W, w->pres, w->pre, cx, cy, f, w->acc, w->comp, w->comp_n, comp_stride, segcap, ablate);
+        hipLaunchKernelGGL(k_accumulate, grid, dim3(256), 0, s, labels, depth, H, W, w->pres, w->pre, cx, cy, f, w->acc, w->comp, w->comp_n, comp_stride, segcap, LG_LEAF_ABLATE);
     }
     // exact medians: ranks from the areas, 4 radix passes over the leaf-pixel list, successor for even counts
     hipLaunchKernelGGL(k_seed, dim3(LGL_MAXL / 256, B), dim3(256), 0, s, w->acc, w->st, w->maxpass);
@@ -1173,7 +1174,7 @@ int lg_leaf_run_batch(LgLeafWs*& w, const int16_t* labels, const float* depth, i
         {
             LeafProfScope ps(prof, "leaf_hist", s);
             hipLaunchKernelGGL(k_hist<16>, grid, dim3(256), 0, s, w->comp, w->comp_n, comp_stride, segcap, w->nlab, w->st, w->maxpass, pass, w->hist,
-                               w->above, ablate);
+                               w->above, LG_LEAF_ABLATE);
         }
         LeafProfScope ps(prof, "leaf_select", s);
         hipLaunchKernelGGL(k_select, dim3(16, B), dim3(256), 0, s, w->st, w->hist, w->nlab, w->maxpass, pass, w->above, w->succ);

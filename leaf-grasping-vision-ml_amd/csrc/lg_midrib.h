@@ -104,7 +104,7 @@ struct LgMidribWs {
     LgOrientWs* orient = nullptr;   // device contour analysis (null: host analysis of every frame)
 };
 // hist / lut for B * ntiles tiles; with frames != 0 also the per-frame buffers of lg_detect_midrib for B frames of H x W
-int lg_midrib_ensure(LgMidribWs*& w, int B, int H, int W, int ntiles, bool frames, bool device_orient, std::string* err);
+int lg_midrib_ensure(LgMidribWs*& w, int B, int H, int W, int ntiles, bool frames, bool device_orient, int orient_cap, std::string* err);
 void lg_midrib_free(LgMidribWs*& w);
 
 // kernels (lg_midrib.hip).  C == 0: src is gray [B][H][W]; C == 3 / 4: src is the image [B][H][W][C], gray is computed from it

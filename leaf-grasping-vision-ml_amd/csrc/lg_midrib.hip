@@ -286,7 +286,7 @@ void lg_midrib_free(LgMidribWs*& w) {
     w = nullptr;
 }
 
-int lg_midrib_ensure(LgMidribWs*& w, int B, int H, int W, int ntiles, bool frames, bool device_orient, std::string* err) {
+int lg_midrib_ensure(LgMidribWs*& w, int B, int H, int W, int ntiles, bool frames, bool device_orient, int orient_cap, std::string* err) {
     if (!w) w = new LgMidribWs();
     hipError_t rc = hipSuccess;
     auto A = [&](hipError_t r) { if (rc == hipSuccess) rc = r; };
@@ -325,7 +325,7 @@ int lg_midrib_ensure(LgMidribWs*& w, int B, int H, int W, int ntiles, bool frame
     }
     if (device_orient) {
         // no device scratch: the host contour analysis of every frame gives the same values (lg_leaf_orientation's hand-off)
-        if (lg_orient_ensure(w->orient, B, H, nullptr)) {
+        if (lg_orient_ensure(w->orient, B, H, orient_cap, nullptr)) {
             lg_orient_free(w->orient);
             (void)hipGetLastError();
         }

@@ -23,7 +23,8 @@ struct LgOrientWs {
     int* h_status_dev = nullptr;    // device-side alias of h_status (null: the pinned allocation is not mapped)
 };
 
-int lg_orient_ensure(LgOrientWs*& w, int B, int H, std::string* err);
+// cap: runs per frame the scratch holds (LgOptions::orient_cap), taken when the scratch is built
+int lg_orient_ensure(LgOrientWs*& w, int B, int H, int cap, std::string* err);
 void lg_orient_free(LgOrientWs*& w);
 // frames [off, off + n) of the scratch; bits / win / fp point at frame `off`.  Writes fp[i] (sin, cos, theta, has_angle),
 // out and status; a frame with status 1 has fp[i].has_angle = 0 and must be analysed on the host.

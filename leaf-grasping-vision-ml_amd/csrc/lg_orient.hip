@@ -19,7 +19,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <algorithm>
 #include <string>
@@ -549,14 +548,13 @@ void lg_orient_free(LgOrientWs*& w) {
     w = nullptr;
 }
 
-int lg_orient_ensure(LgOrientWs*& w, int B, int H, std::string* err) {
+int lg_orient_ensure(LgOrientWs*& w, int B, int H, int cap, std::string* err) {
     if (w && B <= w->capB && H == w->H) return LG_OK;
     const int nB = std::max(B, w ? w->capB : 0);
     hipDeviceSynchronize();
     lg_orient_free(w);
     w = new LgOrientWs();
-    const char* e = getenv("LG_ORIENT_CAP");   // runs per frame held by the scratch (tests lower it to reach the host hand-off)
-    w->cap = e ? std::max(16, std::min(atoi(e), 16384)) : 16384;
+    w->cap = cap;
     const size_t nb = (size_t)nB;
     hipError_t rc = hipSuccess;
     auto A = [&](hipError_t r) { if (rc == hipSuccess) rc = r; };

@@ -18,7 +18,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <stdlib.h>
 
 #include <algorithm>
 #include <map>
@@ -28,6 +27,7 @@
 
 #include "../../include/leafgrasp.h"
 #include "lg_cnn.h"
+#include "lg_options.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -1133,9 +1133,10 @@ int lg_train_create(int device, int n_blocks, const int32_t* filters, int attent
     tr->hp = (AdamHp*)hp;
     A(&sd, 2);
     tr->seed_dev = (uint64_t*)sd;
-    if (const char* e = getenv("LG_TRAIN_GRAPH")) tr->use_graph = atoi(e) != 0;
-    if (const char* e = getenv("LG_TRAIN_CONV_SMALL")) tr->conv_small_below = atoi(e);
-    if (const char* e = getenv("LG_TRAIN_CONV_SPLIT")) tr->conv_split_below = atoi(e);
+    const LgTrainOptions o = lg_train_options_from_env();
+    tr->use_graph = o.graph;
+    tr->conv_small_below = o.conv_small_below;
+    tr->conv_split_below = o.conv_split_below;
     if (rc == LG_OK && hipStreamCreateWithFlags(&tr->stream, hipStreamNonBlocking) != hipSuccess) rc = LG_ERR_HIP;
     if (rc == LG_OK && hipStreamCreateWithFlags(&tr->stream_w, hipStreamNonBlocking) != hipSuccess) rc = LG_ERR_HIP;
     for (int k = 0; k < 8 && rc == LG_OK; k++)
@@ -1160,7 +1161,7 @@ int lg_train_create(int device, int n_blocks, const int32_t* filters, int attent
     // but each of the ~12 stream hops of a step costs ~15 us (0.65 vs 0.67 ms at batch 16), and how ROCm maps a process's
     // streams to its few hardware queues depends on how many streams exist when these two are created: for 2 of 9 probed
     // counts (tests/tools/streams_probe.py) the two-stream step was 2.2-2.5x slower.
-    if (const char* e = getenv("LG_TRAIN_STREAMS")) tr->side_stream = atoi(e) == 2;
+    tr->side_stream = o.streams == 2;
     *out = tr;
     return LG_OK;
 }

@@ -264,6 +264,14 @@ class GraspPointSelector:
             raise RuntimeError(lib.lg_last_error(self._h).decode())
         return int(algo.value)
 
+    def options(self):
+        """Inspection: the experiment switches as this handle found them when it was created (lg_debug_options), name -> int."""
+        buf = C.create_string_buffer(4096)
+        n = lib.lg_debug_options(self._h, buf, len(buf))
+        if not 0 < n < len(buf):
+            raise RuntimeError(f"lg_debug_options -> {n}")
+        return {k: int(v) for k, v in (ln.split("=") for ln in buf.value.decode().splitlines())}
+
     def cnn_scored(self):
         """Inspection: how many patches the last select_grasp_point(s) / select_grasp_candidates call put through the CNN --
         the candidates that could still beat candidate 0 (lg_cnn_candidate_cannot_win), or every one (B * top_k) for the

@@ -100,8 +100,7 @@ def device_plan(cin, cout, wi, n_host, n_dev, num_cu):
     """(R, rem, idle workgroups) of one layer of a slice with n_host <= MAX_SLICE patch slots of which n_dev <= n_host hold a
     patch.  The grid is the unsplit host plan's (fewer items than workgroups shrink it to one workgroup per item); ntb, the
     item list, R and rem follow from n_dev; no item is split (P = 1); a workgroup without an item leaves at once (idle).
-    num_cu is what the launcher may take: all CUs of a default handle (its max_cus clamp, the LG_CNN_CUS experiment, is not
-    restated here)."""
+    num_cu is what the launcher takes: all CUs of the device."""
     assert 0 <= n_dev <= n_host <= MAX_SLICE
     items8 = -(-_ntb(wi, n_host) // 8) * (cout // 64)
     gx = min(num_cu // 8, items8)

@@ -154,8 +154,8 @@ def _b(*parts):
 
 
 class _Env:
-    """the options a handle reads at lg_create (LG_ORIENT_CAP: when its workspace is built, in its first call), set for the time of
-    the creation and of every step on the handle, and put back"""
+    """the options a handle reads at lg_create (all of them, LG_ORIENT_CAP too: lg_debug_options), set for the time of the creation
+    and of every step on the handle, and put back"""
 
     def __init__(self, env):
         self.env = dict(env or ())

@@ -40,7 +40,7 @@ def handles(request):
     assert torch.cuda.is_available()
     keys = ("LG_DIRECT_HOST", "LG_ORIENT_CAP")
     old = {k: os.environ.get(k) for k in keys}
-    try:   # the options are read when a handle is created (LG_ORIENT_CAP: when its workspace is)
+    try:   # the options are read when a handle is created (LG_ORIENT_CAP too: one cap for the handle's life)
         for k in keys:
             os.environ.pop(k, None)
         if request.param:

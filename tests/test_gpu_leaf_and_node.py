@@ -309,7 +309,7 @@ def test_orientation_device_equals_host(L, cap, monkeypatch):
     host = L.GraspPointSelector("cuda:0", load_model=False)
     monkeypatch.delenv("LG_HOST_ORIENT")
     if cap:
-        monkeypatch.setenv("LG_ORIENT_CAP", cap)
+        monkeypatch.setenv("LG_ORIENT_CAP", cap)   # (read at lg_create: the handle keeps this cap for life)
     dev = L.GraspPointSelector("cuda:0", load_model=False)
     n_found = 0
     for k, m in enumerate(_orientation_cases()):
@@ -351,7 +351,7 @@ def test_orientation_in_the_batched_path(L, monkeypatch):
     monkeypatch.setenv("LG_HOST_ORIENT", "1")
     host = L.GraspPointSelector("cuda:0", load_model=False)
     monkeypatch.delenv("LG_HOST_ORIENT")
-    monkeypatch.setenv("LG_ORIENT_CAP", "2048")
+    monkeypatch.setenv("LG_ORIENT_CAP", "2048")   # (read at lg_create)
     dev = L.GraspPointSelector("cuda:0", load_model=False)
     out = []
     for sel in (host, dev):

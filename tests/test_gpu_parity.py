@@ -997,3 +997,37 @@ def test_launch_forms_of_the_plane_kernel_give_the_same_planes(env):
                         "-k", sel], env=dict(os.environ, **env), cwd=repo, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout and "failed" not in r.stdout
+
+
+def test_launch_forms_belong_to_the_handle(L, monkeypatch):
+    """LG_FINAL_PERSIST / LG_FINAL_TPW are read when a handle is created and stay with it: four handles of one process, each
+    created under its own setting and all called with the environment restored, hold their own values and write the same
+    planes and validity, byte for byte (the default handle against the oracle: the tests above)."""
+    settings = [{}, {"LG_FINAL_PERSIST": "3"}, {"LG_FINAL_PERSIST": "8"}, {"LG_FINAL_TPW": "4"}]
+    sels = []
+    for env in settings:
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        sels.append(L.GraspPointSelector(torch.device("cuda:0"), load_model=False))
+        for k in env:
+            monkeypatch.delenv(k)
+    assert "LG_FINAL_PERSIST" not in os.environ and "LG_FINAL_TPW" not in os.environ
+    for s, env in zip(sels, settings):
+        o = s.options()
+        assert o["LG_FINAL_PERSIST"] == int(env.get("LG_FINAL_PERSIST", -1)) and o["LG_FINAL_TPW"] == int(env.get("LG_FINAL_TPW", -1))
+        assert o["LG_FINAL_NEAR"] == (0 if env else 1)   # either switch turns the near launch off
+    for H, W in ((35, 130), (96, 320)):
+        frames = [O.synthetic_scene(H, W, 40 + i) for i in range(3)]
+        masks = np.stack([(f[0] == 1).astype(np.uint8) for f in frames])
+        masks[1] = 0   # one empty mask
+        assert masks[0].any() and masks[2].any()
+        depths = np.stack([f[1] for f in frames])
+        got = []
+        for s in sels:
+            s.set_camera_params(frames[0][2])
+            maps, valid, _ = s.score_maps(torch.from_numpy(masks).cuda(), torch.from_numpy(depths).cuda())
+            got.append(({k: v.cpu().numpy() for k, v in maps.items()}, valid.cpu().numpy()))
+        for (maps, valid), env in zip(got[1:], settings[1:]):
+            for k in maps:
+                assert maps[k].tobytes() == got[0][0][k].tobytes(), (env, H, W, k)
+            assert valid.tobytes() == got[0][1].tobytes(), (env, H, W)
