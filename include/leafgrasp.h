@@ -25,6 +25,7 @@
  *                      (scripts/utils/ml_grasp_optimizer/model.py:101-128), load_ml_model :43-57
  *   lg_select_grasp    GraspPointSelector.select_grasp_point :184-253 (whole path, batched)
  *   lg_select_grasp_candidates   the per-candidate log lines of its selection loop :210-236, every candidate ranked
+ *   lg_select_grasp_ml   the commented-out "grasp point based on only ML model" select_grasp_point :290-390 (batched)
  *   lg_harvest_patches / lg_negative_masks / lg_leaf_contour   EnhancedGraspDataCollector's patch extraction and
  *                      negative-region helpers (scripts/utils/ml_grasp_optimizer/data_collector.py:91-173,426-490)
  *   lg_leaf_stats      the per-leaf passes of OptimalLeafSelector.select_optimal_leaf
@@ -279,6 +280,69 @@ int lg_rank_grasp_candidates(const double* trad, const double* comb, const int32
    score.  lg_select_grasp does not put such a candidate's patch through the CNN (LG_CNN_PRUNE=0 at lg_create: it does). */
 int lg_ml_combined_score(double logit, double trad, double* ml, double* confidence, double* combined);
 int lg_cnn_candidate_cannot_win(double trad_i, double trad_0);
+
+/* ---- ML-only grasp selection: the "grasp point based on only ML model" form of select_grasp_point that the reference keeps
+   commented out beside the live one (scripts/utils/grasp_point_selector.py:290-390): the seven planes, a walk over the leaf's
+   pixels, GraspPointCNN on each sampled pixel's 32 x 32 window, the best score -- or the mask centroid when nothing could be
+   scored.  Per frame, n = the number of set mask pixels; sample order is row-major (np.where order).
+   Sampling  LG_ML_SAMPLE_NTH (the reference's, :310-320): step = max(1, n / target) in integers, the samples are leaf pixels
+             number 0, step, 2 step, ... below n -- at most 2 target - 1 of them (max_samples must hold that many).
+             LG_ML_SAMPLE_GRID (the score as a map over the leaf): the leaf pixels with x % stride == 0 && y % stride == 0,
+             stride in 1..64.  A frame with more such pixels than max_samples overflows: found = 0, n_samples[b] = -(their
+             number), no rows; the other frames of the call are unaffected and the call returns LG_OK.
+             max_samples in 1..65536 is the row length of `samples`; chunk in 0..8192 = patches per gather + CNN pass (0:
+             the library's default, 1024) -- results do not depend on it.
+   Border    (:326-328, both modes) a sample with y < 16 || y >= H - 16 || x < 16 || x >= W - 16 stays in the table with scored
+             = 0 and is not put through the CNN.  This is the commented code's rule, not get_ml_score's torch.bool rule: x ==
+             W - 16 is skipped here and lg_params.mask_is_bool plays no part.  A scored window never needs replicate padding.
+   Features  those of the live get_ml_score (:59-143), i.e. what lg_gather_patches and lg_cnn_forward compute: min-max
+             normalisation per window, the raw mask channel, NaN propagation as lg_cnn_forward documents it.  The commented
+             block's un-normalised patches are not reproduced.
+   Values    logit, and ml_score = lg_ml_combined_score's ml = tanh(3 sigmoid(logit)) / 2 + 1/2 rounded to float.  scored = 1: the
+             sample went through the CNN (no model loaded: every row has scored = 0).  Unscored rows carry NaN in both; rows
+             past the frame's samples are zeros.
+   Pick      the first sample in order whose logit is strictly greater than every earlier scored sample's (:364, score >
+             best_score): the first occurrence of the largest logit.  A NaN logit never wins.  The reference compares the
+             float32 sigmoid; the logit orders the samples the same way except where that sigmoid saturates or two logits
+             collide in it, where the reference keeps the earlier sample and this keeps the larger logit.
+   Fallback  (:368-378) no model loaded, no scored sample, or only NaN logits: the pick is the centroid (sum x / n, sum y / n),
+             truncated, from exact 64-bit integer sums (torch's float32 mean() may round differently on a large leaf); ml_used
+             = 0, best_score = NaN.  Empty mask: found = 0 (the reference's int(nan) raises and ends in its None triple).
+   Result    x, y = the pick; X, Y, Z, has_pre, pX, pY, pZ by the code lg_select_grasp runs for its pick; n_candidates = the
+             samples that went through the CNN; ml_used = 1: a CNN score picked; best_score = the pick's ml_score or NaN;
+             theta as lg_select_grasp.
+   lg_select_grasp_ml_labels: mask[b] = labels[b] == leaf_ids[b] as lg_select_grasp_labels; lg_params.label_aware passes
+   through as there (channel 5 and the pre-grasp clearance); lg_select_grasp_ml rejects it (lg_label_aware_check).
+   samples: HOST [B][max_samples] or NULL; n_samples: HOST [B] or NULL.  Synchronises `stream` before returning.  The device
+   builds the table from the mask's bit rows without atomics: it is the same on every run and equals
+   lg_ml_sample_points_host's, which runs the same code on the host (no device, no handle): xy [cap][2], scored [cap], *n = the
+   samples (GRID with more than min(cap, max_samples) of them: -(their number), nothing written), sums = {sum x, sum y, area}
+   over the set pixels; any output pointer but n may be NULL.  LG_ERR_INVALID for a bad argument, NTH included when min(cap,
+   max_samples) < 2 target - 1. */
+enum { LG_ML_SAMPLE_NTH = 0, LG_ML_SAMPLE_GRID = 1 };
+typedef struct lg_ml_sampling {
+    int32_t mode, target, stride, max_samples, chunk;   /* chunk: patches per gather+CNN pass, 0 = library default */
+} lg_ml_sampling;
+typedef struct lg_ml_sample {
+    int32_t x, y, scored;
+    float logit, ml_score;
+} lg_ml_sample;   /* 20 bytes */
+/* NTH, target 100, stride 8, max_samples 4096, chunk 0 */
+void lg_default_ml_sampling(lg_ml_sampling* s);
+int lg_select_grasp_ml(lg_handle h, const float* depth, const uint8_t* mask, int B, int H, int W, const lg_params* p,
+                       const lg_ml_sampling* sampling, lg_grasp_result* results, lg_ml_sample* samples, int32_t* n_samples,
+                       void* stream);
+int lg_select_grasp_ml_labels(lg_handle h, const float* depth, const int16_t* labels, const int32_t* leaf_ids, int B, int H, int W,
+                              const lg_params* p, const lg_ml_sampling* sampling, lg_grasp_result* results, lg_ml_sample* samples,
+                              int32_t* n_samples, void* stream);
+int lg_ml_sample_points_host(const uint64_t* bits, int H, int W, int WW, const lg_ml_sampling* sampling, int32_t* xy,
+                             int32_t* scored, int cap, int32_t* n, int64_t sums[3]);
+/* Where the gather of lg_select_grasp_ml* finds the five planes it does not read from the plane kernel's stores: form 1 = it
+   computes them at the pixels of every window (deferred planes, what lg_select_grasp does), 2 = the plane kernel stores all
+   seven on the leaf's tiles once and the gather reads them; 0 = by the library's rule (form 1; profiles/NOTES_ml_select.md has the
+   measurement; LG_DEFER_PLANES=0 at lg_create: form 2).  Holds for the handle's later calls.
+   *last (may be NULL) = the form the last lg_select_grasp_ml* call on this handle took, 0: none yet.  Same results either way. */
+int lg_debug_ml_planes(lg_handle h, int form, int32_t* last);
 
 /* The node's result message of every frame (leaf_grasp_node_v3.py:170-176: "x,y,X,Y,Z[,pX,pY,pZ]", each number as Python's
    str() prints it -- the shortest decimal string of the float32 value as a double), '\n'-terminated, one line per frame in

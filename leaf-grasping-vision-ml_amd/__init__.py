@@ -10,7 +10,7 @@ from ._lib import LgParams as ScoreParams  # every constant of the path (SURVEY 
 from ._lib import default_params  # noqa: F401
 from .confidence_manager import ConfidenceManager
 from .data_collector import EnhancedGraspDataCollector
-from .grasp_point_selector import GRASP_CANDIDATE_DTYPE, GraspPointSelector, clahe
+from .grasp_point_selector import GRASP_CANDIDATE_DTYPE, ML_SAMPLE_DTYPE, GraspPointSelector, clahe
 from .hybrid_grasp_selector import HybridGraspSelector
 from .hybrid_selector import HybridSelector
 from .image_processor import ImageProcessor
@@ -19,4 +19,4 @@ from .node_harness import LeafGraspHarness
 
 __all__ = ["GraspPointSelector", "ImageProcessor", "HybridSelector", "ConfidenceManager", "ScoreParams",
            "default_params", "MAP_NAMES", "LIB_PATH", "LgError", "OptimalLeafSelector", "HybridGraspSelector",
-           "LeafGraspHarness", "EnhancedGraspDataCollector", "clahe", "GRASP_CANDIDATE_DTYPE"]
+           "LeafGraspHarness", "EnhancedGraspDataCollector", "clahe", "GRASP_CANDIDATE_DTYPE", "ML_SAMPLE_DTYPE"]

@@ -50,6 +50,20 @@ class LgGraspCandidate(C.Structure):
                 ("pX", C.c_float), ("pY", C.c_float), ("pZ", C.c_float)]
 
 
+LG_ML_SAMPLE_NTH, LG_ML_SAMPLE_GRID = 0, 1
+
+
+class LgMlSampling(C.Structure):
+    """lg_ml_sampling: how lg_select_grasp_ml* picks the leaf pixels it scores (chunk 0 = the library's default)."""
+    _fields_ = [("mode", C.c_int32), ("target", C.c_int32), ("stride", C.c_int32), ("max_samples", C.c_int32),
+                ("chunk", C.c_int32)]
+
+
+class LgMlSample(C.Structure):
+    """lg_ml_sample: one row of the sample table of lg_select_grasp_ml* (20 bytes)."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("scored", C.c_int32), ("logit", C.c_float), ("ml_score", C.c_float)]
+
+
 class LgTrainHparams(C.Structure):
     """lg_train_hparams; defaults = scripts/train_model.py:221-222,256."""
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
@@ -100,6 +114,14 @@ SYMBOLS = {
                                              C.POINTER(LgGraspResult), C.POINTER(LgGraspCandidate), _VP]),
     "lg_select_grasp_candidates_labels": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(LgParams), C.POINTER(LgGraspResult), C.POINTER(LgGraspCandidate), _VP]),
+    "lg_default_ml_sampling": (None, [C.POINTER(LgMlSampling)]),
+    "lg_select_grasp_ml": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(LgParams), C.POINTER(LgMlSampling),
+                                     C.POINTER(LgGraspResult), _VP, C.POINTER(C.c_int32), _VP]),
+    "lg_select_grasp_ml_labels": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(LgParams),
+                                            C.POINTER(LgMlSampling), C.POINTER(LgGraspResult), _VP, C.POINTER(C.c_int32), _VP]),
+    "lg_ml_sample_points_host": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(LgMlSampling), _VP, _VP, C.c_int,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "lg_debug_ml_planes": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int32)]),
     "lg_rank_grasp_candidates": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
     "lg_ml_combined_score": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double)]),

@@ -20,6 +20,7 @@
 #include "lg_leaf.h"
 #include "lg_internal.h"
 #include "lg_midrib.h"
+#include "lg_mlsel.h"
 #include "lg_options.h"
 #include "lg_orient.h"
 #include "lg_pool.h"
@@ -121,6 +122,22 @@ struct lg_ctx {
     LgMidribWs* midrib = nullptr;  // lg_clahe / lg_detect_midrib scratch (lg_midrib.hip)
     void* eval_ws = nullptr;       // lg_eval_logits / lg_cnn_evaluate: result, chunk rows and (evaluate without logits_out) the logits
     size_t eval_cap = 0;
+    // lg_select_grasp_ml*: the sample table and what follows it (lg_mlsel.h), grown on the first call that needs more; the
+    // patches of one gather + CNN pass (haloed planes, halo zeroed at allocation); the sample rows; the chunk counts
+    LgMlBuffers ml = {};
+    size_t ml_cap_BM = 0, ml_cap_BH = 0;
+    int ml_cap_B = 0;
+    float* ml_patches = nullptr;
+    int ml_patches_cap = 0;
+    lg_ml_sample* ml_rows = nullptr;
+    size_t ml_rows_cap = 0;
+    int32_t* ml_counts_host = nullptr;    // pinned [B][2]: n, n_scored per frame
+    int32_t* ml_chunk_host = nullptr;     // pinned: patches of every chunk, and their device copy
+    int32_t* ml_chunk_dev = nullptr;
+    size_t ml_chunk_cap = 0;
+    hipEvent_t ev_ml = nullptr;           // behind the table kernels and the copy of the counts
+    int ml_planes = 0;                    // lg_debug_ml_planes: 0 by rule, 1 deferred, 2 stored
+    int ml_last_form = 0;
 };
 
 namespace {
@@ -306,6 +323,21 @@ void gaussian1d(int size, float* k1) {
     for (int i = 0; i < size; i++) k1[i] = (float)(e[i] / s);
 }
 
+void ml_free(lg_ctx* h) {
+    auto F = [](void* p) { if (p) hipFree(p); };
+    LgMlBuffers& m = h->ml;
+    F(m.frames); F(m.row_pre); F(m.xy); F(m.scored); F(m.slot_local); F(m.list); F(m.slot); F(m.counts); F(m.n_frame); F(m.logits);
+    F(m.pick_n); F(m.pick_xy); F(m.pick_info); F(m.pick_meta);
+    m = LgMlBuffers{};
+    h->ml_cap_BM = h->ml_cap_BH = 0; h->ml_cap_B = 0;
+    F(h->ml_patches); h->ml_patches = nullptr; h->ml_patches_cap = 0;
+    F(h->ml_rows); h->ml_rows = nullptr; h->ml_rows_cap = 0;
+    F(h->ml_chunk_dev); h->ml_chunk_dev = nullptr;
+    if (h->ml_counts_host) hipHostFree(h->ml_counts_host);
+    if (h->ml_chunk_host) hipHostFree(h->ml_chunk_host);
+    h->ml_counts_host = h->ml_chunk_host = nullptr; h->ml_chunk_cap = 0;
+}
+
 void parallel_for(lg_ctx* h, int n, const std::function<void(int)>& fn) {
     if (h->pool && n > 1) h->pool->run(n, fn);
     else
@@ -407,6 +439,8 @@ int lg_destroy(lg_handle h) {
     if (h->cand_rows_host) hipHostFree(h->cand_rows_host);
     lg_cnn_free(&h->cnn);
     if (h->eval_ws) hipFree(h->eval_ws);
+    ml_free(h);
+    if (h->ev_ml) hipEventDestroy(h->ev_ml);
     lg_leaf_free(h->leaf);
     lg_leaf_prof_free(h->leaf_prof);
     lg_orient_free(h->orient);
@@ -1676,9 +1710,8 @@ int lg_rank_grasp_candidates(const double* trad, const double* comb, const int32
     return LG_OK;
 }
 
-static int lg_select_grasp_labels_impl(lg_handle h, const float* depth, const int16_t* labels, const int32_t* leaf_ids, int B,
-                                       int H, int W, const lg_params* pin, float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid,
-                                       lg_grasp_result* results, lg_grasp_candidate* cands, void* stream_) {
+// The labels entries' staging: room for the 0 / 1 mask the bit-row pass derives from the labels, the frames' leaf ids on the device
+static int labels_stage(lg_handle h, const int16_t* labels, const int32_t* leaf_ids, int B, int H, int W, void* stream_) {
     if (!labels || !leaf_ids || B < 1 || H < 1 || W < 1) return fail(h, LG_ERR_INVALID, "lg_select_grasp_labels: null or empty input");
     LG_HIP(h, hipSetDevice(h->device));
     const size_t need = (size_t)B * H * W;
@@ -1700,6 +1733,14 @@ static int lg_select_grasp_labels_impl(lg_handle h, const float* depth, const in
     }
     memcpy(h->ids_host, leaf_ids, sizeof(int32_t) * B);   // (the previous call on this handle has been synchronised: one call in flight)
     LG_HIP(h, hipMemcpyAsync(h->ids_dev, h->ids_host, sizeof(int32_t) * B, hipMemcpyHostToDevice, (hipStream_t)stream_));
+    return LG_OK;
+}
+
+static int lg_select_grasp_labels_impl(lg_handle h, const float* depth, const int16_t* labels, const int32_t* leaf_ids, int B,
+                                       int H, int W, const lg_params* pin, float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid,
+                                       lg_grasp_result* results, lg_grasp_candidate* cands, void* stream_) {
+    const int rc = labels_stage(h, labels, leaf_ids, B, H, W, stream_);
+    if (rc) return rc;
     return lg_select_grasp_impl(h, depth, h->mask_ws, labels, B, H, W, pin, out_maps, out_valid, results, cands, stream_);
 }
 
@@ -1958,6 +1999,311 @@ static int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* 
         fprintf(stderr, "[lg] B=%d enq1 %.3f | wait bits %.3f | orient %.3f | enq2 %.3f | gpu wait %.3f | post %.3f ms\n", B,
                 t_enq1 - t_start, t_copy - t_enq1, t_orient - t_copy, t_enq2 - t_orient, t_sync - t_enq2, now() - t_sync);
     return LG_OK;
+}
+
+// ============================================================================ ML-only grasp selection (lg_mlsel.h)
+void lg_default_ml_sampling(lg_ml_sampling* s) {
+    if (!s) return;
+    s->mode = LG_ML_SAMPLE_NTH; s->target = 100; s->stride = 8; s->max_samples = 4096; s->chunk = 0;
+}
+
+// The table of one frame on the host: row counts and their prefix over every row, then lg_ml_locate per sample -- the functions
+// lg_ml_rows_kernel and lg_ml_table_kernel call (the device walks the bounding-box rows only; the other rows count nothing).
+int lg_ml_sample_points_host(const uint64_t* bits_, int H, int W, int WW, const lg_ml_sampling* sp, int32_t* xy, int32_t* scored,
+                             int cap, int32_t* n, int64_t sums[3]) {
+    if (!bits_ || !n || H < 1 || W < 1 || WW != (W + 63) / 64 || cap < 1 || lg_ml_sampling_error(sp)) return LG_ERR_INVALID;
+    lg_ml_sampling s = *sp;
+    if (cap < s.max_samples) s.max_samples = cap;
+    if (lg_ml_sampling_error(&s)) return LG_ERR_INVALID;   // (NTH: the 2 target - 1 samples must fit)
+    const unsigned long long* bits = (const unsigned long long*)bits_;
+    LgMlFrame f;
+    memset(&f, 0, sizeof(f));
+    f.y0 = 0; f.rows = H; f.w0 = 0; f.w1 = WW - 1;
+    std::vector<int32_t> pre((size_t)H);
+    int run = 0;
+    for (int y = 0; y < H; y++) {
+        pre[y] = run;
+        const bool on = lg_ml_row_sampled(s.mode, s.stride, y);
+        for (int w = 0; w < WW; w++) {
+            const unsigned long long v = bits[(size_t)y * WW + w];
+            const int c = lg_ml_popc(v);
+            f.area += c;
+            f.sx += (long long)c * (64 * w) + lg_ml_index_sum(v);
+            f.sy += (long long)c * y;
+            if (on) run += lg_ml_popc(v & lg_ml_pattern(s.mode, s.stride, w));
+        }
+    }
+    f.total = run;
+    lg_ml_frame_counts(s, &f);
+    *n = f.n;
+    if (sums) { sums[0] = f.sx; sums[1] = f.sy; sums[2] = f.area; }
+    for (int i = 0; i < f.n; i++) {
+        int x, y, sc;
+        lg_ml_locate(bits, H, W, WW, s, f, pre.data(), i, &x, &y, &sc);
+        if (xy) { xy[2 * i] = x; xy[2 * i + 1] = y; }
+        if (scored) scored[i] = sc;
+    }
+    return LG_OK;
+}
+
+int lg_debug_ml_planes(lg_handle h, int form, int32_t* last) {
+    if (!h || form < 0 || form > 2) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    h->ml_planes = form;
+    if (last) *last = h->ml_last_form;
+    return LG_OK;
+}
+
+static int ml_ensure(lg_ctx* h, int B, int H, int M, int chunk, bool want_rows) {
+    const size_t BM = (size_t)B * M, BH = (size_t)B * H;
+    if (BM > h->ml_cap_BM || BH > h->ml_cap_BH || B > h->ml_cap_B) {
+        hipDeviceSynchronize();
+        const size_t nBM = std::max(BM, h->ml_cap_BM), nBH = std::max(BH, h->ml_cap_BH);
+        const int nB = std::max(B, h->ml_cap_B);
+        {
+            auto F = [](void* p) { if (p) hipFree(p); };
+            LgMlBuffers& m = h->ml;
+            F(m.frames); F(m.row_pre); F(m.xy); F(m.scored); F(m.slot_local); F(m.list); F(m.slot); F(m.counts); F(m.n_frame); F(m.logits);
+            F(m.pick_n); F(m.pick_xy); F(m.pick_info); F(m.pick_meta);
+            m = LgMlBuffers{};
+            if (h->ml_counts_host) hipHostFree(h->ml_counts_host);
+            h->ml_counts_host = nullptr;
+            h->ml_cap_BM = h->ml_cap_BH = 0; h->ml_cap_B = 0;
+        }
+        LgMlBuffers& m = h->ml;
+        LG_HIP(h, dev_alloc(&m.frames, (size_t)nB));
+        LG_HIP(h, dev_alloc(&m.row_pre, nBH));
+        LG_HIP(h, dev_alloc(&m.xy, nBM * 2));
+        LG_HIP(h, dev_alloc(&m.scored, nBM));
+        LG_HIP(h, dev_alloc(&m.slot_local, nBM));
+        LG_HIP(h, dev_alloc(&m.list, nBM));
+        LG_HIP(h, dev_alloc(&m.slot, nBM));
+        LG_HIP(h, dev_alloc(&m.counts, (size_t)nB * 2));
+        LG_HIP(h, dev_alloc(&m.n_frame, (size_t)nB));
+        LG_HIP(h, dev_alloc(&m.logits, nBM));
+        LG_HIP(h, dev_alloc(&m.pick_n, (size_t)nB));
+        LG_HIP(h, dev_alloc(&m.pick_xy, (size_t)nB * 2));
+        LG_HIP(h, dev_alloc(&m.pick_info, (size_t)nB * 2));
+        LG_HIP(h, dev_alloc(&m.pick_meta, (size_t)nB * 4));
+        LG_HIP(h, hipHostMalloc((void**)&h->ml_counts_host, sizeof(int32_t) * 2 * nB));
+        h->ml_cap_BM = nBM; h->ml_cap_BH = nBH; h->ml_cap_B = nB;
+    }
+    const size_t n_chunks = (BM + chunk - 1) / chunk;
+    if (n_chunks > h->ml_chunk_cap) {
+        hipDeviceSynchronize();
+        if (h->ml_chunk_dev) hipFree(h->ml_chunk_dev);
+        if (h->ml_chunk_host) hipHostFree(h->ml_chunk_host);
+        h->ml_chunk_dev = nullptr; h->ml_chunk_host = nullptr; h->ml_chunk_cap = 0;
+        LG_HIP(h, dev_alloc(&h->ml_chunk_dev, n_chunks));
+        LG_HIP(h, hipHostMalloc((void**)&h->ml_chunk_host, sizeof(int32_t) * n_chunks));
+        h->ml_chunk_cap = n_chunks;
+    }
+    if (chunk > h->ml_patches_cap) {
+        hipDeviceSynchronize();
+        if (h->ml_patches) hipFree(h->ml_patches);
+        h->ml_patches = nullptr; h->ml_patches_cap = 0;
+        const size_t fl = (size_t)chunk * lg_cnn_halo_patch_floats();
+        LG_HIP(h, dev_alloc(&h->ml_patches, fl));
+        LG_HIP(h, hipMemset(h->ml_patches, 0, fl * sizeof(float)));   // the halos and the three spare planes stay zero
+        h->ml_patches_cap = chunk;
+    }
+    if (want_rows && BM > h->ml_rows_cap) {
+        hipDeviceSynchronize();
+        if (h->ml_rows) hipFree(h->ml_rows);
+        h->ml_rows = nullptr; h->ml_rows_cap = 0;
+        LG_HIP(h, dev_alloc(&h->ml_rows, BM));
+        h->ml_rows_cap = BM;
+    }
+    if (!h->ev_ml) LG_HIP(h, hipEventCreateWithFlags(&h->ev_ml, hipEventDisableTiming));
+    return LG_OK;
+}
+
+// lg_select_grasp_impl's front (bit rows, distance transform, orientation, the sparse near-tile plane launch) without top-k;
+// then the sample table's scored windows through the gather and the CNN in chunks, the pick, lg_finish_kernel on the one-point list.
+static int lg_select_grasp_ml_impl(lg_handle h, const float* depth, const uint8_t* mask, const int16_t* labels, int B, int H, int W,
+                                   const lg_params* pin, const lg_ml_sampling* sp, lg_grasp_result* results, lg_ml_sample* samples,
+                                   int32_t* n_samples, void* stream_) {
+    if (!results) return fail(h, LG_ERR_INVALID, "lg_select_grasp_ml: results is null");
+    lg_ml_sampling S;
+    if (sp) S = *sp; else lg_default_ml_sampling(&S);
+    if (const char* why = lg_ml_sampling_error(&S)) return fail(h, LG_ERR_INVALID, (std::string("lg_select_grasp_ml: ") + why).c_str());
+    Plan pl;
+    int rc = make_plan(h, pl, depth, mask, B, H, W, pin, nullptr, nullptr, "lg_select_grasp_ml");
+    if (rc) return rc;
+    pl.labels = labels;
+    if (lg_label_aware_check(&pl.P, labels ? 1 : 0))
+        return fail(h, LG_ERR_INVALID, "lg_select_grasp_ml: label_aware needs the label image (lg_select_grasp_ml_labels)");
+    if ((size_t)B * S.max_samples > 0x7fffffffull) return fail(h, LG_ERR_INVALID, "lg_select_grasp_ml: B * max_samples must stay below 2^31");
+    pl.label_aware = pl.P.label_aware != 0;
+    pl.sparse = true;
+    const lg_params& P = pl.P;
+    const int M = S.max_samples, chunk = S.chunk > 0 ? S.chunk : LG_ML_DEFAULT_CHUNK;
+    hipStream_t s = (hipStream_t)stream_;
+    LG_HIP(h, hipSetDevice(h->device));
+    rc = ensure_ws(h, B, H, W, std::max(P.top_k, 1));
+    if (rc) return rc;
+    rc = ml_ensure(h, B, H, M, chunk, samples != nullptr);
+    if (rc) return rc;
+    h->last_iso_B = 0;
+    if (pl.label_aware) {   // workspace of the mode, as lg_select_grasp_impl
+        const size_t words = (size_t)B * H * pl.WW;
+        if (words > h->iso_words_cap || B > h->iso_B_cap) {
+            hipDeviceSynchronize();
+            if (h->iso_others) hipFree(h->iso_others);
+            if (h->iso_dil) hipFree(h->iso_dil);
+            if (h->iso_mf) hipFree(h->iso_mf);
+            h->iso_others = h->iso_dil = nullptr; h->iso_mf = nullptr; h->iso_words_cap = 0; h->iso_B_cap = 0;
+            if (hipMalloc((void**)&h->iso_others, sizeof(unsigned long long) * words) != hipSuccess ||
+                hipMalloc((void**)&h->iso_dil, sizeof(unsigned long long) * 2 * words) != hipSuccess ||
+                hipMalloc((void**)&h->iso_mf, sizeof(uint32_t) * LG_ISO_MF * B) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(h, LG_ERR_NOMEM, "lg_select_grasp_ml_labels: label-aware workspace");
+            }
+            h->iso_words_cap = words; h->iso_B_cap = B;
+        }
+    }
+    const bool use_cnn = h->cnn.loaded;
+    // Where the gather finds sdf, approach, isolation, accessibility and stem: computed at every window's pixels (deferred), or
+    // stored once by the plane kernel on the leaf's tiles.  Overlapping GRID windows recompute a pixel up to (32 / stride)^2
+    // times in the deferred form, yet at 1080p the gather takes the same time either way (GRID / 8, 32 frames, 46296 windows:
+    // 1.265 against 1.269 ms; NTH / 100: 0.108 against 0.111) and the score-only plane kernel is the cheaper one (0.034 against
+    // 0.046 ms): deferred always, which also keeps five planes out of the workspace (profiles/NOTES_ml_select.md).
+    const int form = h->ml_planes ? h->ml_planes : h->opt.defer_planes ? 1 : 2;
+    pl.defer = form == 1;
+    h->ml_last_form = form;
+    h->last_scored = 0; h->last_scored_subs = 0; h->last_cnn_B = 0; h->last_patch_floats = 0; h->last_near_B = 0;
+    for (int i = 0; i < LG_NUM_MAPS; i++)
+        if ((use_cnn && (!pl.defer || i == LG_MAP_FLATNESS)) || i == LG_MAP_DISTANCE || i == LG_MAP_TRADITIONAL) {
+            rc = ensure_ws_map(h, i);
+            if (rc) return rc;
+            pl.maps[i] = h->ws_maps[i];
+        }
+    pl.valid = h->ws_valid;
+    pl.near = h->opt.final_near > 0 && h->opt.subbatch == 0 && h->opt.no_skip == 0;
+    const size_t px = (size_t)H * W;
+    (void)px;
+    const LgMlBuffers& m = h->ml;
+    rc = enq_prep(h, pl, 0, B, s, h->ev_prep);
+    if (rc) return rc;
+    // the table needs the bit rows and the bounding boxes only: it runs in front of the distance transform and the host reads
+    // its counts behind ev_ml, after everything up to the plane kernel has been queued
+    {
+        ProfScope ps(h, "ml_rows", s);
+        lg_launch_ml_rows(h->bits, h->win, S, m, B, H, W, pl.WW, s);
+    }
+    {
+        ProfScope ps(h, "ml_table", s);
+        lg_launch_ml_table(h->bits, S, m, B, H, W, pl.WW, s);
+    }
+    {
+        ProfScope ps(h, "ml_list", s);
+        lg_launch_ml_list(S, m, B, s);
+    }
+    LG_HIP(h, hipMemcpyAsync(h->ml_counts_host, m.counts, sizeof(int32_t) * 2 * B, hipMemcpyDeviceToHost, s));
+    LG_HIP(h, hipEventRecord(h->ev_ml, s));
+    rc = enq_dt(h, pl, 0, B, s);
+    if (rc) return rc;
+    const LgIsoFields iso_fields = {h->tmp, h->iso_mf};
+    if (pl.label_aware) {
+        {
+            ProfScope ps(h, "iso_dilate", s);
+            lg_launch_iso_dilate(h->iso_others, h->iso_dil, h->iso_mf, B, H, W, pl.WW, s);
+        }
+        {
+            ProfScope ps(h, "iso_sweeps", s);
+            if (lg_launch_iso_sweeps(h->iso_dil, h->tmp, h->iso_mf, B, H, W, pl.WW, (uint32_t)P.chamfer_init_dist0, s))
+                return fail(h, LG_ERR_UNSUPPORTED, "label_aware: width");
+        }
+    }
+    bool upload_fp = true;
+    rc = finish_orient(h, pl, 0, B, &upload_fp);
+    if (rc) return rc;
+    LgFinalArgs fargs;
+    rc = enq_final(h, pl, 0, B, s, upload_fp, &fargs);
+    if (rc) return rc;
+    if (pl.label_aware && pl.maps[LG_MAP_ISOLATION]) {   // stored planes: the current leaf's pixels
+        ProfScope ps(h, "iso_plane", s);
+        lg_launch_iso_plane(iso_fields, h->bits, h->win, pl.maps[LG_MAP_ISOLATION], B, H, W, pl.WW, P.iso_w_close, P.iso_w_wide,
+                            fargs.iso_ramp_top, fargs.iso_ramp_step, s);
+    }
+    LG_HIP(h, hipEventSynchronize(h->ev_ml));   // (the table kernels ended long ago: they follow the bit-row pass)
+    long long total = 0;
+    for (int b = 0; b < B; b++) total += h->ml_counts_host[2 * b + 1];
+    if (use_cnn && total > 0) {
+        const int n_chunks = (int)((total + chunk - 1) / chunk);
+        for (int c = 0; c < n_chunks; c++) h->ml_chunk_host[c] = (int32_t)std::min<long long>(chunk, total - (long long)c * chunk);
+        LG_HIP(h, hipMemcpyAsync(h->ml_chunk_dev, h->ml_chunk_host, sizeof(int32_t) * n_chunks, hipMemcpyHostToDevice, s));
+        const float* mp[LG_NUM_MAPS];
+        for (int i = 0; i < LG_NUM_MAPS; i++) mp[i] = pl.maps[i];
+        for (int c = 0; c < n_chunks; c++) {
+            const int nc = h->ml_chunk_host[c];
+            {
+                // patch slot j of the pass takes list entry c * chunk + j = frame * M + sample; the grid covers nc slots
+                ProfScope ps(h, "gather", s);
+                lg_launch_gather(depth, mask, mp, h->tile_state, P.flat_scale, (nc + M - 1) / M, H, W, M, m.xy, m.n_frame, h->ml_patches,
+                                 true, s, m.list + (size_t)c * chunk, h->ml_chunk_dev + c, pl.defer ? &fargs : nullptr,
+                                 pl.label_aware && pl.defer ? &iso_fields : nullptr);
+            }
+            std::string err;
+            {
+                // no item split (a logit does not depend on what runs beside it), exactly nc patches
+                ProfScope ps(h, "cnn", s);
+                const int r2 = lg_cnn_run(&h->cnn, h->ml_patches, true, nc, m.logits + (size_t)c * chunk, s, &err, false, nullptr);
+                if (r2) return fail(h, r2, err.c_str());
+            }
+        }
+        h->last_scored = total;
+    }
+    {
+        ProfScope ps(h, "ml_pick", s);
+        lg_launch_ml_pick(depth, m, M, B, H, W, use_cnn ? 1 : 0, s);
+    }
+    lg_grasp_result* const res_out = h->res_host_dev ? h->res_host_dev : h->res_dev;
+    {
+        LgFinishArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.cand_n = m.pick_n; fa.cand_xy = m.pick_xy; fa.cand_info = m.pick_info; fa.logits = nullptr; fa.slot = nullptr; fa.slot_frames = B;
+        fa.bits2 = pl.label_aware ? h->iso_others : nullptr;
+        fa.fp = h->fp_dev; fa.bits = h->bits; fa.out = res_out;
+        fa.B = B; fa.H = H; fa.W = W; fa.WW = pl.WW; fa.K = 1; fa.use_cnn = 0; fa.mask_is_bool = P.mask_is_bool;
+        fa.cx = P.cx; fa.cy = P.cy; fa.f = P.f;
+        lg_make_se_spans(2 * P.pregrasp_clearance + 1, &fa.se);
+        ProfScope ps(h, "finish", s);
+        lg_launch_finish(fa, s);
+    }
+    {
+        ProfScope ps(h, "ml_rows_out", s);
+        lg_launch_ml_rows_out(m, M, B, use_cnn ? 1 : 0, res_out, samples ? h->ml_rows : nullptr, s);
+    }
+    if (!h->res_host_dev)
+        LG_HIP(h, hipMemcpyAsync(h->res_host, h->res_dev, sizeof(lg_grasp_result) * B, hipMemcpyDeviceToHost, s));
+    if (samples) LG_HIP(h, hipMemcpyAsync(samples, h->ml_rows, sizeof(lg_ml_sample) * (size_t)B * M, hipMemcpyDeviceToHost, s));
+    LG_HIP(h, hipStreamSynchronize(s));
+    LG_HIP(h, hipGetLastError());
+    if (use_cnn && lg_cnn_take_error(&h->cnn)) return fail(h, LG_ERR_HIP, "lg_select_grasp_ml: a split CNN item did not receive its parts");
+    memcpy(results, h->res_host, sizeof(lg_grasp_result) * B);
+    if (n_samples)
+        for (int b = 0; b < B; b++) n_samples[b] = h->ml_counts_host[2 * b];
+    if (pl.near) h->last_near_B = B;
+    if (pl.label_aware) { h->last_iso_B = B; h->last_iso_H = H; h->last_iso_W = W; }
+    return LG_OK;
+}
+
+int lg_select_grasp_ml(lg_handle h, const float* depth, const uint8_t* mask, int B, int H, int W, const lg_params* pin,
+                       const lg_ml_sampling* sampling, lg_grasp_result* results, lg_ml_sample* samples, int32_t* n_samples, void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    return lg_select_grasp_ml_impl(h, depth, mask, nullptr, B, H, W, pin, sampling, results, samples, n_samples, stream_);
+}
+
+int lg_select_grasp_ml_labels(lg_handle h, const float* depth, const int16_t* labels, const int32_t* leaf_ids, int B, int H, int W,
+                              const lg_params* pin, const lg_ml_sampling* sampling, lg_grasp_result* results, lg_ml_sample* samples,
+                              int32_t* n_samples, void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    const int rc = labels_stage(h, labels, leaf_ids, B, H, W, stream_);
+    if (rc) return rc;
+    return lg_select_grasp_ml_impl(h, depth, h->mask_ws, labels, B, H, W, pin, sampling, results, samples, n_samples, stream_);
 }
 
 }  // extern "C"

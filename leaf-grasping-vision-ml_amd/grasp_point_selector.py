@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import LG_NUM_MAPS, MAP_NAMES, LgGraspCandidate, LgGraspResult, LgParams, check, lib
+from ._lib import LG_NUM_MAPS, MAP_NAMES, LgGraspCandidate, LgGraspResult, LgMlSample, LgMlSampling, LgParams, check, lib
 from ._log import logerr, loginfo, logwarn
 from .cnn import pack_state_dict
 from .image_processor import flatness_config
@@ -27,6 +27,9 @@ assert _RESULT_DTYPE.itemsize == C.sizeof(LgGraspResult)
 GRASP_CANDIDATE_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.float32) for n, t in LgGraspCandidate._fields_])
 assert GRASP_CANDIDATE_DTYPE.itemsize == C.sizeof(LgGraspCandidate)
 _ML_FIELDS = ("ml_score", "ml_confidence", "combined")
+# lg_ml_sample rows (select_grasp_points_ml_batch(return_samples=True) returns a [B, max_samples] array of this dtype)
+ML_SAMPLE_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.float32) for n, t in LgMlSample._fields_])
+assert ML_SAMPLE_DTYPE.itemsize == C.sizeof(LgMlSample) == 20
 
 _VP = C.c_void_p
 
@@ -569,6 +572,114 @@ class GraspPointSelector:
         except Exception as e:  # noqa: BLE001
             logerr(f"Error in grasp point selection: {str(e)}")
             return None, None, None
+
+    # ------------------------------------------------------------------ ML-only selection (:290-390, the commented-out form)
+    @staticmethod
+    def ml_sampling(mode="nth", target=100, stride=8, max_samples=None, chunk=0):
+        """An lg_ml_sampling: mode 'nth' (every step-th leaf pixel, step = max(1, n // target): the reference's walk) or 'grid'
+        (the leaf pixels with x % stride == 0 and y % stride == 0).  max_samples: rows of the sample table per frame, default
+        2 * target - 1 for 'nth' (all it can produce) and 4096 for 'grid' (a frame with more grid pixels overflows alone)."""
+        modes = {"nth": _lib.LG_ML_SAMPLE_NTH, "grid": _lib.LG_ML_SAMPLE_GRID}
+        if mode not in modes:
+            raise ValueError(f"sampling mode must be 'nth' or 'grid' (got {mode!r})")
+        if max_samples is None:
+            max_samples = max(1, 2 * int(target) - 1) if mode == "nth" else 4096
+        return LgMlSampling(modes[mode], int(target), int(stride), int(max_samples), int(chunk))
+
+    def ml_planes(self, form=0):
+        """Inspection / experiments (lg_debug_ml_planes): where the ML-only gather finds its planes from the next call on -- 0 by
+        the library's rule, 1 computed at every window (deferred), 2 stored once by the plane kernel.  Returns the form the last
+        ML-only call took (0: none yet).  Same results either way."""
+        last = C.c_int32()
+        check(self._h, lib.lg_debug_ml_planes(self._h, int(form), C.byref(last)), "lg_debug_ml_planes")
+        return int(last.value)
+
+    def _ml_finish(self, call, B, sampling, return_samples):
+        s = sampling if sampling is not None else self.ml_sampling()
+        res = (LgGraspResult * B)()
+        rows = np.zeros((B, s.max_samples), ML_SAMPLE_DTYPE) if return_samples else None
+        counts = np.zeros(B, np.int32)
+        with torch.cuda.device(self.device):
+            call(C.byref(s), res, rows.ctypes.data if return_samples else None, counts.ctypes.data_as(C.POINTER(C.c_int32)))
+        self.last_results = res
+        return res, rows, counts
+
+    def select_grasp_points_ml_batch(self, leaf_masks, depth_tensors, sampling=None, return_samples=False, image_processor=None):
+        """The ML-only selection for B frames (lg_select_grasp_ml): the CNN over sampled leaf pixels, the best logit or the mask
+        centroid.  sampling: ml_sampling(...), default the reference's every-step-th walk with target 100.  Returns the triples
+        as select_grasp_points_batch does; with return_samples also a [B, max_samples] array of ML_SAMPLE_DTYPE (x, y, scored,
+        logit, ml_score; unscored rows NaN, rows past a frame's samples zero) and the frames' sample counts (int32 [B]; a
+        'grid' frame with more samples than max_samples: -(their number), and no triple).  Bad input raises."""
+        m, d, is_bool = self._prep_inputs(leaf_masks, depth_tensors)
+        B, H, W = m.shape
+        p = LgParams.from_buffer_copy(self._sync_params(image_processor))
+        p.mask_is_bool = 1 if is_bool else 0
+        res, rows, counts = self._ml_finish(
+            lambda s, r, rw, cn: check(self._h, lib.lg_select_grasp_ml(self._h, d.data_ptr(), m.data_ptr(), B, H, W, C.byref(p), s, r, rw,
+                                                                       cn, self._stream()), "lg_select_grasp_ml"),
+            B, sampling, return_samples)
+        out = _triples(res, B)
+        return (out, rows, counts) if return_samples else out
+
+    def select_grasp_points_ml_for_leaves(self, label_tensors, leaf_ids, depth_tensors, sampling=None, return_samples=False,
+                                          image_processor=None, label_aware=False):
+        """select_grasp_points_ml_batch(label_tensors == leaf_ids[:, None, None], depth_tensors) through the labels entry
+        (lg_select_grasp_ml_labels), as select_grasp_points_for_leaves: a None leaf id gives the (None, None, None) triple;
+        label_aware=True lets channel 5 and the pre-grasp clearance see the other leaves."""
+        lab = label_tensors
+        if not (torch.is_tensor(lab) and lab.dtype == torch.int16 and lab.is_cuda and lab.dim() == 3 and lab.is_contiguous()):
+            raise ValueError("label_tensors must be a contiguous [B,H,W] int16 tensor on the device")
+        d = depth_tensors.to(self.device, torch.float32).contiguous()
+        if d.shape != lab.shape:
+            raise ValueError(f"labels {tuple(lab.shape)} and depth {tuple(d.shape)} must both be [B,H,W]")
+        B, H, W = lab.shape
+        p = LgParams.from_buffer_copy(self._sync_params(image_processor))
+        p.mask_is_bool = 1
+        p.label_aware = 1 if label_aware else 0
+        ids = (C.c_int32 * B)(*[(-(1 << 30)) if i is None else int(i) for i in leaf_ids])
+        res, rows, counts = self._ml_finish(
+            lambda s, r, rw, cn: check(self._h, lib.lg_select_grasp_ml_labels(self._h, d.data_ptr(), lab.data_ptr(), ids, B, H, W,
+                                                                              C.byref(p), s, r, rw, cn, self._stream()),
+                                       "lg_select_grasp_ml_labels"),
+            B, sampling, return_samples)
+        for b, i in enumerate(leaf_ids):
+            if i is None:
+                res[b].found = 0
+        out = _triples(res, B)
+        return (out, rows, counts) if return_samples else out
+
+    def select_grasp_point_ml(self, leaf_mask, depth_tensor, image_processor=None, pcl_data=None):
+        """The reference's "grasp point based on only ML model" select_grasp_point (:290-390), reference signature.  Never raises:
+        errors are logged and give (None, None, None); pcl_data as in select_grasp_point."""
+        try:
+            res = self.select_grasp_points_ml_batch(leaf_mask, depth_tensor, image_processor=image_processor)[0]
+            if res[0] is None:
+                logwarn("No grasp point found (empty mask)")
+            elif pcl_data is not None:
+                raise AttributeError("'GraspPointSelector' object has no attribute 'width'")   # (see select_grasp_point)
+            return res
+        except Exception as e:  # noqa: BLE001
+            logerr(f"Error in grasp point selection: {str(e)}")
+            return None, None, None
+
+    def ml_score_map(self, leaf_mask, depth_tensor, stride=8, image_processor=None, max_samples=65536):
+        """The model's score as a map over one leaf: (map, samples) -- map a [H,W] float32 device tensor holding ml_score at
+        every scored grid pixel (x % stride == 0, y % stride == 0, on the leaf, off the 16-pixel border band) and NaN elsewhere;
+        samples the frame's rows of ML_SAMPLE_DTYPE.  A leaf with more grid pixels than max_samples raises."""
+        s = self.ml_sampling("grid", stride=stride, max_samples=max_samples)
+        _, rows, counts = self.select_grasp_points_ml_batch(leaf_mask, depth_tensor, sampling=s, return_samples=True,
+                                                            image_processor=image_processor)
+        if counts[0] < 0:
+            raise ValueError(f"ml_score_map: {-int(counts[0])} grid pixels, more than max_samples = {max_samples}")
+        rows = rows[0, :int(counts[0])]
+        H, W = (leaf_mask.shape[-2], leaf_mask.shape[-1])
+        out = torch.full((H, W), float("nan"), dtype=torch.float32, device=self.device)
+        sc = rows[rows["scored"] != 0]
+        if len(sc):
+            yi = torch.from_numpy(sc["y"].astype(np.int64)).to(self.device)
+            xi = torch.from_numpy(sc["x"].astype(np.int64)).to(self.device)
+            out[yi, xi] = torch.from_numpy(np.ascontiguousarray(sc["ml_score"])).to(self.device)
+        return out, rows
 
     # ------------------------------------------------------------------ small host-side helpers kept for callers
     def get_3d_grasp_point(self, grasp_point_2d, depth_tensor, pcl_data=None):  # :152-180

@@ -12,8 +12,11 @@ from .leaf_scorer import OptimalLeafSelector
 
 
 class LeafGraspHarness:
-    def __init__(self, height=1080, width=1440, device="cuda:0", load_model=True, label_aware=False):
+    def __init__(self, height=1080, width=1440, device="cuda:0", load_model=True, label_aware=False, ml_only=False):
         self.height, self.width = height, width
+        # True: the grasp step is the ML-only selection (select_grasp_point_ml / lg_select_grasp_ml_labels: the CNN over sampled
+        # leaf pixels, grasp_point_selector.py:290-390) instead of the traditional candidates rescored by the CNN.
+        self.ml_only = bool(ml_only)
         # True: the batch path's grasp selection sees the other leaves of the label image (lg_params.label_aware: the isolation
         # map and the pre-grasp clearance).  The single-frame path follows the node and hands over one leaf's mask.
         self.label_aware = bool(label_aware)
@@ -77,8 +80,8 @@ class LeafGraspHarness:
             if leaf_id is None:
                 return None
             optimal_mask = mask_tensor == leaf_id
-            p2, p3, pre = self.grasp_selector.select_grasp_point(optimal_mask, depth_tensor, self.image_processor,
-                                                                 pcl_data=None)
+            select = self.grasp_selector.select_grasp_point_ml if self.ml_only else self.grasp_selector.select_grasp_point
+            p2, p3, pre = select(optimal_mask, depth_tensor, self.image_processor, pcl_data=None)
             if p2 is None:
                 return None
             return self.format_result(p2, p3, pre)
@@ -149,8 +152,9 @@ class LeafGraspHarness:
             return
         if mask_t.dtype == torch.int16 and mask_t.is_contiguous() and depth_t.is_contiguous():
             # the comparison inside the library's first pass over the labels (frames without a leaf get an empty mask there)
-            self.grasp_selector.select_grasp_points_for_leaves(mask_t, ids, depth_t, image_processor=self.image_processor,
-                                                               label_aware=self.label_aware)
+            select = (self.grasp_selector.select_grasp_points_ml_for_leaves if self.ml_only
+                      else self.grasp_selector.select_grasp_points_for_leaves)
+            select(mask_t, ids, depth_t, image_processor=self.image_processor, label_aware=self.label_aware)
             rows = range(B)
         else:
             if self.label_aware:
@@ -161,7 +165,8 @@ class LeafGraspHarness:
             else:
                 sel = torch.tensor(keep, device=self.device)
                 optimal, dep = mask_t.index_select(0, sel) == idt, depth_t.index_select(0, sel)
-            self.grasp_selector.select_grasp_points_batch(optimal, dep, image_processor=self.image_processor)
+            select = self.grasp_selector.select_grasp_points_ml_batch if self.ml_only else self.grasp_selector.select_grasp_points_batch
+            select(optimal, dep, image_processor=self.image_processor)
             rows = keep
         # the messages of the whole chunk in one native call (format_result's strings, character for character: Python's float
         # repr costs 0.24 ms per 128 frames -- a third of a millisecond the device waits for)

@@ -1,0 +1,377 @@
+"""ML-only grasp selection on the device (lg_select_grasp_ml*, lg_mlsel.hip) against the oracle composed in tests/ml_select_ref.py:
+the sample table (device == host function == NumPy, bit for bit), every scored sample's logit against the float64 oracle network
+(1e-4, the project's CNN tolerance), the pick (first maximum of the call's own logits; the oracle's pick where the oracle's best
+logit leads its runner-up by more than 2e-4), the 3-D and pre-grasp point, the fallbacks, independence of batch, stride, chunk and
+overflow, one handle across entry points, and one full-size frame.  Closed-form CNN weights, O.synthetic_scene, 160 x 224 frames
+unless a test says otherwise.  Scenes (seed, leaf) were chosen with the oracle alone: SCENES' margins are asserted below."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+from oracle import lg_oracle as O  # noqa: E402
+from tests import label_aware_ref as LR  # noqa: E402
+from tests import ml_select_ref as R  # noqa: E402
+from tests import test_ml_sampling_host as TH  # noqa: E402
+
+H, W = 160, 224
+TOL = 1e-4          # the project's CNN tolerance (device float32 network against the float64 oracle)
+MARGIN = 2e-4       # device and oracle may each be off by TOL
+# (seed, leaf): an interior leaf, one that crosses the 16-pixel border band, another interior one
+SCENES = {"interior": (1, 1), "crossing": (5, 3), "second": (2, 3)}
+IN_BAND = (0, 2)    # a leaf wholly inside the border band: nothing can be scored
+MODES = {"nth": dict(mode=R.NTH, target=100), "grid": dict(mode=R.GRID, stride=8)}
+
+
+@pytest.fixture(scope="module")
+def L():
+    import leafgrasp_amd
+
+    assert torch.cuda.is_available()
+    return leafgrasp_amd
+
+
+@pytest.fixture(scope="module")
+def sel(L):
+    s = L.GraspPointSelector(torch.device("cuda:0"), load_model=False)
+    s.set_cnn_state_dict(R.params())
+    return s
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _case(name, mode):
+    seed, leaf = SCENES[name] if name in SCENES else name
+    return R.case(seed, H, W, leaf, **MODES[mode])
+
+
+def _sampling(sel, mode, **kw):
+    m = MODES[mode]
+    return sel.ml_sampling(mode, target=m.get("target", 100), stride=m.get("stride", 8), **kw)
+
+
+def _run(sel, masks, depths, P, sampling):
+    """-> (triples, rows [B, M], counts [B], result rows as a copy of the bytes)"""
+    sel.set_camera_params(P)
+    tri, rows, counts = sel.select_grasp_points_ml_batch(_dev(np.stack(masks)), _dev(np.stack(depths)), sampling=sampling,
+                                                         return_samples=True)
+    return tri, rows, counts, bytes(sel.last_results)
+
+
+def _results(sel):
+    from leafgrasp_amd.grasp_point_selector import _RESULT_DTYPE
+    return np.frombuffer(bytes(sel.last_results), dtype=_RESULT_DTYPE)
+
+
+def _assert_table(rows, count, mask, mode_kw, host=True):
+    """device rows == NumPy (and == the host function)"""
+    n, xy, scored, sums = R.table(np.asarray(mask), **mode_kw)
+    assert count == n
+    k = max(n, 0)
+    if n > 0:
+        assert np.array_equal(rows["x"][:n], xy[:, 0]) and np.array_equal(rows["y"][:n], xy[:, 1])
+        assert np.array_equal(rows["scored"][:n], scored)
+        assert np.isnan(rows["logit"][:n][scored == 0]).all() and np.isnan(rows["ml_score"][:n][scored == 0]).all()
+        assert not np.isnan(rows["logit"][:n][scored == 1]).any()
+    assert not rows[k:].tobytes().strip(b"\0")   # rows past the samples are zeros
+    if host:
+        s = TH.sampling(mode_kw["mode"], target=mode_kw.get("target", 100), stride=mode_kw.get("stride", 8), max_samples=len(rows))
+        rc, hn, hxy, hsc, hsums = TH.host_table(np.asarray(mask, np.uint8), s)
+        assert rc == 0 and hn == n and list(sums) == hsums
+        if n > 0:
+            assert np.array_equal(hxy[:n], xy) and np.array_equal(hsc[:n], scored)
+
+
+def _first_max(rows, n):
+    lg = np.where(rows["scored"][:n] != 0, rows["logit"][:n].astype(np.float64), np.nan)
+    return R.first_max(lg)
+
+
+# ---------------------------------------------------------------------------------------------------- 1. sample table
+@pytest.mark.parametrize("mode", ["nth", "grid"])
+@pytest.mark.parametrize("shape", [(96, 136), (160, 224), (1100, 72)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_sample_table(sel, shape, mode):
+    h, w = shape
+    ms = TH.masks_for(h, w)
+    masks = [ms["blob"], ms["area0"], ms["crossing"]]   # three areas, one of them empty
+    assert len({int(m.sum()) for m in masks}) == 3 and int(masks[1].sum()) == 0
+    _, depth, P = O.synthetic_scene(h, w, 3)
+    tri, rows, counts, _ = _run(sel, masks, [depth] * 3, P, _sampling(sel, mode, max_samples=1024))
+    for b in range(3):
+        _assert_table(rows[b], counts[b], masks[b], MODES[mode])
+    assert tri[1] == (None, None, None) and tri[0][0] is not None and tri[2][0] is not None
+    res = _results(sel)
+    for b in range(3):
+        n = max(int(counts[b]), 0)
+        assert res["n_candidates"][b] == int(rows["scored"][b, :n].sum())
+
+
+# ---------------------------------------------------------------------------------------------------- 2. logits, 3. pick, 4. triple
+@pytest.mark.parametrize("mode", ["nth", "grid"])
+def test_logits_pick_and_triple_match_the_oracle(sel, mode):
+    cases = [_case(k, mode) for k in SCENES]
+    for c in cases:   # from the oracle alone: the best logit leads, so the pick is decided within the tolerance
+        assert c["margin"] > MARGIN, c["margin"]
+        assert c["pick"] >= 0
+    P = cases[0]["P"]
+    assert all(np.array_equal(c["P"], P) for c in cases)
+    tri, rows, counts, _ = _run(sel, [c["mask"] for c in cases], [c["depth"] for c in cases], P, _sampling(sel, mode))
+    res = _results(sel)
+    for b, c in enumerate(cases):
+        n = c["n"]
+        _assert_table(rows[b], counts[b], c["mask"], MODES[mode])
+        sc = c["scored"] == 1
+        err = np.abs(rows["logit"][b, :n][sc].astype(np.float64) - c["logits"][sc])
+        print(f"{mode} frame {b}: {int(sc.sum())} scored, max |logit - oracle| = {err.max():.3g}")
+        assert err.max() <= TOL
+        ml = np.array([O.RefGraspPointSelector.ml_post(v) for v in c["logits"][sc]])
+        assert np.abs(rows["ml_score"][b, :n][sc].astype(np.float64) - ml).max() <= TOL
+        # the pick: the first maximum of the call's own logits, and the oracle's
+        pick = _first_max(rows[b], n)
+        assert pick == c["pick"]
+        x, y = int(c["xy"][pick, 0]), int(c["xy"][pick, 1])
+        assert tri[b][0] == (x, y)
+        assert res["found"][b] == 1 and res["ml_used"][b] == 1 and res["n_candidates"][b] == int(sc.sum())
+        assert res["best_score"][b] == rows["ml_score"][b, pick]
+        g3 = c["ref"].get_3d_grasp_point((x, y), c["depth"])
+        pre = c["ref"].calculate_pre_grasp_point(g3, np.ascontiguousarray(c["mask"], np.uint8))
+        np.testing.assert_allclose(tri[b][1], g3, rtol=1e-5)
+        np.testing.assert_allclose(tri[b][2], pre, rtol=1e-5)
+
+
+@functools.lru_cache(maxsize=None)
+def _label_case():
+    """two leaves close enough for the label-aware isolation and the pre-grasp clearance to see the other one"""
+    labels = LR.blob_labels(H, W, [(2, 150, 70, 30, 40), (1, 95, 85, 45, 35)])
+    _, depth, P = O.synthetic_scene(H, W, 4)
+    ref = LR.LabelAwareRef(labels, 1, cnn=None)
+    ref.set_camera_params(P)
+    n, xy, scored, sums = R.table(ref.current, R.NTH, target=100)
+    logits = R.oracle_logits(ref, ref.current, depth, xy, scored)
+    return dict(labels=labels, depth=depth, P=P, ref=ref, n=n, xy=xy, scored=scored, logits=logits, pick=R.first_max(logits),
+                margin=R.margin(logits))
+
+
+def test_label_aware_frame(sel):
+    c = _label_case()
+    assert c["margin"] > MARGIN and c["ref"].others.any()
+    sel.set_camera_params(c["P"])
+    tri, rows, counts = sel.select_grasp_points_ml_for_leaves(_dev(c["labels"][None]), [1], _dev(c["depth"][None]),
+                                                              sampling=sel.ml_sampling("nth"), return_samples=True, label_aware=True)
+    n, sc = c["n"], c["scored"] == 1
+    assert counts[0] == n and np.array_equal(rows["scored"][0, :n], c["scored"])
+    assert np.abs(rows["logit"][0, :n][sc].astype(np.float64) - c["logits"][sc]).max() <= TOL
+    pick = _first_max(rows[0], n)
+    assert pick == c["pick"]
+    x, y = int(c["xy"][pick, 0]), int(c["xy"][pick, 1])
+    assert tri[0][0] == (x, y)
+    g3 = c["ref"].get_3d_grasp_point((x, y), c["depth"])
+    np.testing.assert_allclose(tri[0][1], g3, rtol=1e-5)
+    np.testing.assert_allclose(tri[0][2], c["ref"].calculate_pre_grasp_point(g3, c["ref"].current), rtol=1e-5)
+    with pytest.raises(Exception):   # the mask entry rejects the mode
+        p = sel.params
+        p.label_aware = 1
+        try:
+            sel.select_grasp_points_ml_batch(_dev(c["ref"].current[None]), _dev(c["depth"][None]))
+        finally:
+            p.label_aware = 0
+
+
+# ---------------------------------------------------------------------------------------------------- 5. fallbacks
+def _centroid_triple(c, tri, res, b=0):
+    cx, cy = R.centroid(c["sums"])
+    assert tri[b][0] == (cx, cy)
+    assert res["found"][b] == 1 and res["ml_used"][b] == 0 and np.isnan(res["best_score"][b])
+    g3 = c["ref"].get_3d_grasp_point((cx, cy), c["depth"])
+    np.testing.assert_allclose(tri[b][1], g3, rtol=1e-5)
+    np.testing.assert_allclose(tri[b][2], c["ref"].calculate_pre_grasp_point(g3, np.ascontiguousarray(c["mask"], np.uint8)), rtol=1e-5)
+
+
+def test_fallback_without_a_model(L):
+    plain = L.GraspPointSelector(torch.device("cuda:0"), load_model=False)
+    c = _case("interior", "nth")
+    tri, rows, counts, _ = _run(plain, [c["mask"]], [c["depth"]], c["P"], plain.ml_sampling("nth"))
+    res = _results(plain)
+    _centroid_triple(c, tri, res)
+    assert counts[0] == c["n"] and res["n_candidates"][0] == 0
+    assert np.array_equal(rows["x"][0, :c["n"]], c["xy"][:, 0]) and not rows["scored"][0].any()
+    assert np.isnan(rows["logit"][0, :c["n"]]).all()
+
+
+def test_fallback_leaf_in_the_border_band_and_empty_mask(sel):
+    c = _case(IN_BAND, "nth")
+    assert c["n"] > 0 and not c["scored"].any()
+    empty = np.zeros((H, W), bool)
+    tri, rows, counts, _ = _run(sel, [c["mask"], empty], [c["depth"]] * 2, c["P"], _sampling(sel, "nth"))
+    res = _results(sel)
+    _centroid_triple(c, tri, res)
+    assert res["n_candidates"][0] == 0 and counts[0] == c["n"]
+    assert tri[1] == (None, None, None) and res["found"][1] == 0 and counts[1] == 0
+
+
+@functools.lru_cache(maxsize=None)
+def _hole_case():
+    """the interior scene with one NaN depth pixel on the leaf: from the oracle alone, which samples turn NaN"""
+    c = _case("interior", "nth")
+    ys, xs = np.nonzero(c["mask"])
+    k = len(ys) // 3
+    hx, hy = int(xs[k]), int(ys[k])
+    depth = c["depth"].copy()
+    depth[hy, hx] = np.nan
+    bad = R.oracle_logits(c["ref"], c["mask"], depth, c["xy"], c["scored"])
+    nan = np.isnan(bad) & (c["scored"] == 1)
+    holds = (np.abs(hx - c["xy"][:, 0] + 0.5) <= 16) & (np.abs(hy - c["xy"][:, 1] + 0.5) <= 16)   # hole inside [x-16, x+16) x [y-16, y+16)
+    assert (holds & (c["scored"] == 1) <= nan).all()           # every window that holds the hole is NaN
+    assert nan.any() and (~nan & (c["scored"] == 1)).sum() >= 2  # some turn NaN, some stay
+    keep = ~nan & (c["scored"] == 1)
+    assert np.array_equal(bad[keep], c["logits"][keep])        # the oracle's other logits do not move
+    return c, depth, nan, keep
+
+
+def test_nan_depth_on_the_leaf(sel):
+    c, depth, nan, keep = _hole_case()
+    n = c["n"]
+    _, clean, _, _ = _run(sel, [c["mask"]], [c["depth"]], c["P"], _sampling(sel, "nth"))
+    tri, rows, counts, _ = _run(sel, [c["mask"]], [depth], c["P"], _sampling(sel, "nth"))
+    assert np.array_equal(np.isnan(rows["logit"][0, :n]) & (c["scored"] == 1), nan)      # exactly those samples
+    assert rows["logit"][0, :n][keep].tobytes() == clean["logit"][0, :n][keep].tobytes()  # the rest: the clean frame's bits
+    assert np.array_equal(rows["scored"][0, :n], c["scored"])
+    pick = _first_max(rows[0], n)
+    assert pick >= 0 and not nan[pick]                                                    # a NaN never wins
+    assert tri[0][0] == (int(c["xy"][pick, 0]), int(c["xy"][pick, 1]))
+    # every window poisoned: the centroid
+    allnan = np.full_like(c["depth"], np.nan)
+    tri, rows, counts, _ = _run(sel, [c["mask"]], [allnan], c["P"], _sampling(sel, "nth"))
+    res = _results(sel)
+    assert np.isnan(rows["logit"][0, :n]).all()
+    assert tri[0][0] == R.centroid(c["sums"]) and res["ml_used"][0] == 0 and res["found"][0] == 1
+    assert res["n_candidates"][0] == int(c["scored"].sum())
+
+
+# ---------------------------------------------------------------------------------------------------- 6. independence
+@pytest.mark.parametrize("mode", ["nth", "grid"])
+def test_a_frame_alone_and_in_a_batch(sel, mode):
+    cs = [_case(k, mode) for k in SCENES]
+    s = _sampling(sel, mode)
+    _, rows3, counts3, res3 = _run(sel, [c["mask"] for c in cs], [c["depth"] for c in cs], cs[0]["P"], s)
+    for b, c in enumerate(cs):
+        _, rows1, counts1, res1 = _run(sel, [c["mask"]], [c["depth"]], c["P"], s)
+        assert counts1[0] == counts3[b]
+        assert rows1[0].tobytes() == rows3[b].tobytes()
+        assert res1 == res3[b * len(res1):(b + 1) * len(res1)]
+
+
+def test_stride_8_is_a_subset_of_stride_4(sel):
+    c = _case("interior", "grid")
+    _, r8, n8, _ = _run(sel, [c["mask"]], [c["depth"]], c["P"], sel.ml_sampling("grid", stride=8))
+    _, r4, n4, _ = _run(sel, [c["mask"]], [c["depth"]], c["P"], sel.ml_sampling("grid", stride=4))
+    at4 = {(int(r["x"]), int(r["y"])): r for r in r4[0, :n4[0]]}
+    assert n8[0] > 0 and n4[0] > n8[0]
+    for r in r8[0, :n8[0]]:
+        assert at4[(int(r["x"]), int(r["y"]))].tobytes() == r.tobytes()
+
+
+@pytest.mark.parametrize("mode", ["nth", "grid"])
+def test_chunk_does_not_matter(sel, mode):
+    cs = [_case(k, mode) for k in SCENES]
+    out = []
+    for chunk in (0, 7, 64):
+        _, rows, counts, res = _run(sel, [c["mask"] for c in cs], [c["depth"] for c in cs], cs[0]["P"], _sampling(sel, mode, chunk=chunk))
+        out.append((rows.tobytes(), counts.tobytes(), res))
+    assert out[0] == out[1] == out[2]
+
+
+def test_grid_overflow_of_one_frame(sel):
+    a, b = _case("interior", "grid"), _case("crossing", "grid")
+    full = np.ones((H, W), bool)
+    need = len(range(0, H, 8)) * len(range(0, W, 8))
+    s = sel.ml_sampling("grid", stride=8, max_samples=64)
+    assert max(a["n"], b["n"]) <= 64 < need
+    tri, rows, counts, res = _run(sel, [a["mask"], full, b["mask"]], [a["depth"], a["depth"], b["depth"]], a["P"], s)
+    assert counts[1] == -need and tri[1] == (None, None, None) and not rows[1].tobytes().strip(b"\0")
+    tri2, rows2, counts2, res2 = _run(sel, [a["mask"], b["mask"]], [a["depth"], b["depth"]], a["P"], s)
+    k = len(res2) // 2
+    assert rows[0].tobytes() == rows2[0].tobytes() and rows[2].tobytes() == rows2[1].tobytes()
+    assert res[:k] == res2[:k] and res[2 * k:] == res2[k:]
+    assert (counts[0], counts[2]) == (counts2[0], counts2[1]) == (a["n"], b["n"])
+
+
+def test_both_plane_forms_give_the_same_rows(sel):
+    """deferred planes (computed at every window) and stored planes (written once by the plane kernel): the same floats"""
+    cs = [_case(k, "grid") for k in SCENES]
+    out = {}
+    try:
+        for form in (1, 2):
+            sel.ml_planes(form)
+            for mode in ("nth", "grid"):
+                _, rows, counts, res = _run(sel, [c["mask"] for c in cs], [c["depth"] for c in cs], cs[0]["P"], _sampling(sel, mode))
+                out[form, mode] = (rows.tobytes(), counts.tobytes(), res)
+            assert sel.ml_planes(form) == form
+    finally:
+        sel.ml_planes(0)
+    assert out[1, "nth"] == out[2, "nth"] and out[1, "grid"] == out[2, "grid"]
+
+
+# ---------------------------------------------------------------------------------------------------- 7. one handle, several entries
+@pytest.mark.parametrize("kind", ["select_with_model", "candidates"])
+def test_handle_reuse_around_an_ml_call(L, kind):
+    cs = [_case(k, "nth") for k in SCENES]
+    masks, depths, P = _dev(np.stack([c["mask"] for c in cs])), _dev(np.stack([c["depth"] for c in cs])), cs[0]["P"]
+
+    def make():
+        s = L.GraspPointSelector(torch.device("cuda:0"), load_model=False)
+        s.set_camera_params(P)
+        s.set_cnn_state_dict(R.params())
+        return s
+
+    def classic(s):
+        if kind == "candidates":
+            _, cands = s.select_grasp_candidates_batch(masks, depths)
+            return bytes(s.last_results) + cands.tobytes()
+        s.select_grasp_points_batch(masks, depths)
+        return bytes(s.last_results)
+
+    one = make()
+    first = classic(one)
+    for mode in ("nth", "grid"):
+        tri = one.select_grasp_points_ml_batch(masks, depths, sampling=_sampling(one, mode))
+        assert [t[0] for t in tri] == [(int(c["xy"][c["pick"], 0]), int(c["xy"][c["pick"], 1])) for c in (_case(k, mode) for k in SCENES)]
+    third = classic(one)
+    assert first == third == classic(make())
+
+
+# ---------------------------------------------------------------------------------------------------- 8. full size
+def test_full_size_frame(sel):
+    labels, depth, P = R.scene(3, 1080, 1920)
+    ids, cnt = np.unique(labels[labels > 0], return_counts=True)
+    mask = labels == int(ids[np.argmax(cnt)])
+    tri, rows, counts, _ = _run(sel, [mask], [depth], P, sel.ml_sampling("nth"))
+    _assert_table(rows[0], counts[0], mask, MODES["nth"], host=False)
+    n = int(counts[0])
+    assert 100 <= n <= 199
+    pick = _first_max(rows[0], n)
+    assert pick >= 0 and tri[0][0] == (int(rows["x"][0, pick]), int(rows["y"][0, pick]))
+
+
+# ---------------------------------------------------------------------------------------------------- the Python surface
+def test_python_entries(sel, L):
+    c = _case("interior", "grid")
+    sel.set_camera_params(c["P"])
+    m, d = _dev(c["mask"]), _dev(c["depth"])
+    cn = _case("interior", "nth")
+    assert sel.select_grasp_point_ml(m, d)[0] == (int(cn["xy"][cn["pick"], 0]), int(cn["xy"][cn["pick"], 1]))
+    smap, rows = sel.ml_score_map(m, d, stride=8)
+    assert smap.shape == (H, W) and smap.dtype == torch.float32 and smap.is_cuda and len(rows) == c["n"]
+    host = smap.cpu().numpy()
+    sc = rows[rows["scored"] != 0]
+    assert np.array_equal(host[sc["y"], sc["x"]], sc["ml_score"]) and int((~np.isnan(host)).sum()) == len(sc)
+    bare = L.GraspPointSelector(torch.device("cuda:0"), load_model=False)    # no camera: logged, the None triple
+    assert bare.select_grasp_point_ml(m, d) == (None, None, None)
+    with pytest.raises(ValueError):
+        sel.ml_sampling("dense")
