@@ -1,5 +1,5 @@
 // ML-only grasp selection, the device-side link between the bit rows and the gather / CNN / finish kernels (lg_mlsel.h):
-// row counts -> sample table -> slot list -> (gather + CNN in chunks, lg_api.hip) -> pick -> (lg_finish_kernel) -> result rows.
+// row counts -> sample table -> slot list -> (gather + CNN in chunks, lg_select.hip) -> pick -> (lg_finish_kernel) -> result rows.
 // Every step is a launch of its own; nothing here waits on another workgroup.  Integer counts, 64-wide scans and no atomics:
 // the table and the list are the same on every run.
 #include "lg_internal.h"

@@ -319,10 +319,17 @@ def test_both_plane_forms_give_the_same_rows(sel):
 
 
 # ---------------------------------------------------------------------------------------------------- 7. one handle, several entries
-@pytest.mark.parametrize("kind", ["select_with_model", "candidates"])
+@pytest.mark.parametrize("kind", ["select_with_model", "candidates", "label_aware"])
 def test_handle_reuse_around_an_ml_call(L, kind):
-    cs = [_case(k, "nth") for k in SCENES]
-    masks, depths, P = _dev(np.stack([c["mask"] for c in cs])), _dev(np.stack([c["depth"] for c in cs])), cs[0]["P"]
+    """label_aware: both paths grow the mode's workspace and leave the isolation fields in the sweeps' scratch; a plain ML call
+    between them overwrites that scratch"""
+    if kind == "label_aware":
+        lc = _label_case()
+        assert lc["margin"] > MARGIN and lc["ref"].others.any()
+        labels, depths, P = _dev(lc["labels"][None]), _dev(lc["depth"][None]), lc["P"]
+    else:
+        cs = [_case(k, "nth") for k in SCENES]
+        masks, depths, P = _dev(np.stack([c["mask"] for c in cs])), _dev(np.stack([c["depth"] for c in cs])), cs[0]["P"]
 
     def make():
         s = L.GraspPointSelector(torch.device("cuda:0"), load_model=False)
@@ -331,6 +338,9 @@ def test_handle_reuse_around_an_ml_call(L, kind):
         return s
 
     def classic(s):
+        if kind == "label_aware":
+            _, cands = s.select_grasp_candidates_for_leaves(labels, [1], depths, label_aware=True)
+            return bytes(s.last_results) + cands.tobytes()
         if kind == "candidates":
             _, cands = s.select_grasp_candidates_batch(masks, depths)
             return bytes(s.last_results) + cands.tobytes()
@@ -339,9 +349,14 @@ def test_handle_reuse_around_an_ml_call(L, kind):
 
     one = make()
     first = classic(one)
-    for mode in ("nth", "grid"):
-        tri = one.select_grasp_points_ml_batch(masks, depths, sampling=_sampling(one, mode))
-        assert [t[0] for t in tri] == [(int(c["xy"][c["pick"], 0]), int(c["xy"][c["pick"], 1])) for c in (_case(k, mode) for k in SCENES)]
+    if kind == "label_aware":
+        tri = one.select_grasp_points_ml_for_leaves(labels, [1], depths, sampling=one.ml_sampling("nth"), label_aware=True)
+        assert tri[0][0] == (int(lc["xy"][lc["pick"], 0]), int(lc["xy"][lc["pick"], 1]))
+        one.select_grasp_points_ml_batch(_dev(lc["ref"].current[None]), depths)   # not label-aware: the fields are gone
+    else:
+        for mode in ("nth", "grid"):
+            tri = one.select_grasp_points_ml_batch(masks, depths, sampling=_sampling(one, mode))
+            assert [t[0] for t in tri] == [(int(c["xy"][c["pick"], 0]), int(c["xy"][c["pick"], 1])) for c in (_case(k, mode) for k in SCENES)]
     third = classic(one)
     assert first == third == classic(make())
 
