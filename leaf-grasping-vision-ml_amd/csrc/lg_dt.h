@@ -7,7 +7,9 @@ int lg_dt_geometry(int W, int* waves);
 // search_mode: 0 = d_in by the two sweeps for every frame, 1 = by the row search wherever it applies (a non-empty mask with
 // at least one zero pixel), 2 = the row search when the batch's estimated search work stays below the sweeps' latency
 // mf: what lg_launch_pack_bits / lg_launch_pack_labels accumulated on the same stream
-void lg_launch_window(const uint32_t* mf, LgWin* win, int B, int H, int W, int search_mode, hipStream_t s);
+// init0: lg_params.chamfer_init_dist0 of a call whose windows the distance transforms will use (lg_dt_far); the orientation-only
+// callers leave it out
+void lg_launch_window(const uint32_t* mf, LgWin* win, int B, int H, int W, int search_mode, hipStream_t s, uint32_t init0 = 0xFFFFFFFFu);
 int lg_launch_dt(bool bwd, const uint8_t* mask, uint32_t* tmp, float* dist_out, uint32_t* maxfix, const LgWin* win, int B,
                  int H, int W, uint32_t init0, hipStream_t s);   // init0: lg_params.chamfer_init_dist0 (frames without a zero pixel)
 // max d_out outside the sweep windows (closed-form chamfer norm on the frame border) -> atomicMax into maxfix[b][1]

@@ -58,12 +58,12 @@ __device__ __forceinline__ uint32_t lg_wave_min_u32(uint32_t v) {
 // The per-frame costs are integers: the workgroup sums them (and takes the tallest box) through LDS, and every thread takes
 // the same decision before it writes its frames; if the sweeps win, no frame is searched.
 __global__ __launch_bounds__(1024) void lg_window_kernel(const uint32_t* __restrict__ mf, LgWin* __restrict__ wins, int B, int H, int W,
-                                                         int wc, int nw_max, int search_mode, float search_budget) {
+                                                         int wc, int nw_max, int search_mode, float search_budget, int far) {
     __shared__ unsigned long long s_cost;
     __shared__ unsigned s_rows;
     const int t = threadIdx.x;
-    bool sweeps = false;
-    if (search_mode == 2) {
+    bool sweeps = far != 0;   // (lg_dt_far: the whole frame is swept)
+    if (search_mode == 2 && !far) {
         if (t == 0) { s_cost = 0; s_rows = 0; }
         __syncthreads();
         unsigned long long cost = 0;
@@ -85,16 +85,18 @@ __global__ __launch_bounds__(1024) void lg_window_kernel(const uint32_t* __restr
     for (int f = t; f < B; f += 1024) {
         LgWin w = lg_win_from_box(mf + (size_t)f * LG_MF + LG_BOX_X0, H, W, wc, nw_max, search_mode);
         if (sweeps) w.search_in = 0;
+        if (far) { w.wx0 = 0; w.nw = nw_max; w.wy0 = 0; w.wy1 = H; w.skip_out = 0; }
         wins[f] = w;
     }
 }
 
-void lg_launch_window(const uint32_t* mf, LgWin* win, int B, int H, int W, int search_mode, hipStream_t s) {
+void lg_launch_window(const uint32_t* mf, LgWin* win, int B, int H, int W, int search_mode, hipStream_t s, uint32_t init0) {
     int nw = 0;
     const int wc = lg_dt_geometry(W, &nw);
     // mode 2: search while sum over the frames of area^1.5 <= LG_SEARCH_BUDGET * rows of the tallest window: 0.69 ms for 256
     // benchmark leaves of 100 k pixels in either form (anchors + bands; sweeps: ~1.6 us per row).
-    hipLaunchKernelGGL(lg_window_kernel, dim3(1), dim3(1024), 0, s, mf, win, B, H, W, wc, nw, search_mode, LG_SEARCH_BUDGET);
+    hipLaunchKernelGGL(lg_window_kernel, dim3(1), dim3(1024), 0, s, mf, win, B, H, W, wc, nw, search_mode, LG_SEARCH_BUDGET,
+                       lg_dt_far(H, W, init0) ? 1 : 0);
 }
 
 // ============================================================================ max d_out outside the sweep window
@@ -216,6 +218,7 @@ __global__ __launch_bounds__(T) void lg_dt5_kernel(const uint8_t* __restrict__ m
     const int which = blockIdx.x;
     const int frame = blockIdx.y;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const bool far = BWD && lg_dt_far(H, W, init0);
     // ---- sweep window (see LgWin): waves beyond it leave; s_barrier only counts the surviving waves
     const LgWin win = wins[frame];
     const int nwa = win.nw;
@@ -383,9 +386,11 @@ __global__ __launch_bounds__(T) void lg_dt5_kernel(const uint8_t* __restrict__ m
                     for (int k = 0; k < E; k++) {
                         const int pc = pc0 + (E - 1 - k);
                         uint32_t val = v[k];
-                        if (val >= LG_NOSRC) {  // image without any source pixel: OpenCV's border-initialised result
+                        // OpenCV's border cells (lg_dt_far): all there is in an image without any source pixel (no path: >= LG_INF)
+                        if (far || val >= LG_INF) {
                             int dd = min(min(pc + 1, W - pc), min(prow + 1, H - prow));
-                            val = init0 + (uint32_t)dd * LG_A5;
+                            const uint32_t cap = init0 + (uint32_t)dd * LG_A5;
+                            val = val >= LG_INF ? cap : min(val, cap);
                         }
                         if (pc < W) mx = max(mx, val);
                         o[E - 1 - k] = (float)val * (1.0f / 65536.0f);

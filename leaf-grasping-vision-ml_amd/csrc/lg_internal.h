@@ -13,7 +13,7 @@
 #define LG_B3 89738u        // 1.3693
 #define LG_INIT0 0x1FFFFFFFu  // INT_MAX >> 2 : OpenCV's border initialiser, the default of lg_params.chamfer_init_dist0
 #define LG_INF 0x3FFFFFFFu    // "no path yet" inside the DT sweeps (never wins against a real distance)
-#define LG_NOSRC 0x20000000u  // values >= this after the backward sweep mean: image has no source pixel
+#define LG_NOSRC 0x20000000u  // 8192 px: with chamfer_init_dist0 up to here OpenCV's border cells hide every distance near LG_INF (make_plan)
 #define LG_HCAP 16383u        // run distance of a row without any zero pixel in the image (row search; W <= 8192)
 // lg_window_kernel, search_mode 2: a batch's d_in comes from the row search while sum over its frames of area^1.5 <= this *
 // (rows of its tallest bounding box)
@@ -67,6 +67,13 @@ __host__ __device__ inline uint32_t lg_norm5(int dx, int dy) {   // closed-form 
     const uint32_t a = (uint32_t)(dx > dy ? dx : dy), b = (uint32_t)(dx > dy ? dy : dx);
     return 2u * b <= a ? (a - 2u * b) * LG_A5 + b * LG_C5 : (a - b) * LG_C5 + (2u * b - a) * LG_B5;
 }
+// OpenCV's transform keeps chamfer_init_dist0 in the border cells around the image, so a pixel's value is
+//     min(distance to the nearest source, init0 + a * (steps to the nearest border cell)).
+// The second term can only win in a frame where a distance can reach init0 (INT_MAX >> 2 is 8192 px: frames taller than 8192 rows,
+// or 8192 columns wide and a few rows high).  Such a frame is swept whole -- no window, no closed-form border maximum, no row
+// search -- and lg_dt5_kernel applies the border term to every pixel; every other frame cannot tell the difference.
+__host__ __device__ inline bool lg_dt_far(int H, int W, uint32_t init0) { return lg_norm5(W - 1, H - 1) >= init0; }
+
 // ---- max d_out along one frame border line (lg_dout_border_kernel; host export lg_border_line_max)
 // prof[i], i in [0, n): distance from the border line of the nearest leaf pixel in line position lo + i (-1: none).  A candidate
 // p on the line has d_out(p) = min over the entries i with prof[i] >= 0 of lg_norm5(|p - (lo + i)|, prof[i]); the line's maximum

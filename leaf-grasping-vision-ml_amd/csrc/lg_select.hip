@@ -318,7 +318,8 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
     }
     {
         ProfScope ps(h, "bbox", s);
-        lg_launch_window(h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, h->opt.dt_search, s);
+        lg_launch_window(h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, h->opt.dt_search, s,
+                         (uint32_t)pl.P.chamfer_init_dist0);
     }
     LG_HIP(h, hipEventRecord(ev_prep, s));
     LG_HIP(h, hipStreamWaitEvent(h->copy_stream, ev_prep, 0));
@@ -587,6 +588,9 @@ int make_plan(lg_ctx* h, Plan& pl, const float* depth, const uint8_t* mask, int 
         return fail(h, LG_ERR_INVALID, "gaussian_size / 2 must be smaller than H and W (reflect padding)");
     if (pl.P.chamfer_init_dist0 < (int32_t)LG_INIT0)   // (a zeroed struct, or a value a real distance could reach)
         return fail(h, LG_ERR_INVALID, "chamfer_init_dist0 must be in [INT_MAX >> 2, INT_MAX] (lg_default_params: INT_MAX >> 2)");
+    // a real distance must stay below the sweeps' "no path" value wherever OpenCV's border cells do not hide it (lg_dt_far)
+    if (lg_norm5(W - 1, H - 1) + 2u * LG_C5 >= LG_INF && (uint32_t)pl.P.chamfer_init_dist0 > LG_NOSRC)
+        return fail(h, LG_ERR_UNSUPPORTED, "chamfer_init_dist0 above INT_MAX >> 2 needs a frame whose diagonal stays below 16384 px");
     if (lg_label_aware_check(&pl.P, 1)) return fail(h, LG_ERR_INVALID, "label_aware must be 0 or 1");
     pl.B = B; pl.H = H; pl.W = W; pl.WW = (W + 63) / 64;
     pl.tiles_x = (W + LG_TW - 1) / LG_TW; pl.tiles_y = (H + LG_TH - 1) / LG_TH;
