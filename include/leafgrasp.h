@@ -191,8 +191,11 @@ const char* lg_version(void);
 void lg_default_params(lg_params* p);
 
 /* Score planes for B frames.  depth [B][H][W] f32, mask [B][H][W] u8 (0/1), out_maps[i] [B][H][W] f32
-   (any entry may be NULL = not wanted, except DISTANCE/TRADITIONAL which later stages need),
-   out_valid [B][H][W] u8 (may be NULL).  theta_host (optional, HOST, B floats) receives the leaf
+   (any entry may be NULL = not wanted, DISTANCE and TRADITIONAL included: later stages need those two, so the call
+   computes them into planes of the handle's workspace instead and goes on; out_maps itself may be NULL = no plane wanted),
+   out_valid [B][H][W] u8 (may be NULL: a workspace plane takes its place).  Every subset gives the planes it asks for
+   within the library's tolerances; flatness and traditional of a call that leaves out a plane other than those two may
+   differ in the last bit from a call that takes all eight.  theta_host (optional, HOST, B floats) receives the leaf
    axis angle per frame (NaN when the mask has no contour).  Work is enqueued on `stream`
    (a hipStream_t, NULL = default stream); the call synchronises internally only with its own
    copy stream (orientation hand-off), not with `stream`. */
@@ -233,8 +236,9 @@ int lg_cnn_unload(lg_handle h);
 int lg_cnn_forward(lg_handle h, const float* patches, int N, float* logits, void* stream);
 
 /* Whole GraspPointSelector.select_grasp_point for B frames: maps -> valid -> top-k -> (CNN rescoring
-   if a model is loaded) -> 3-D point -> pre-grasp.  out_maps / out_valid may be NULL (library
-   workspace is used).  results: HOST array of B.  Synchronises `stream` before returning. */
+   if a model is loaded) -> 3-D point -> pre-grasp.  out_maps / out_valid may be NULL, and so may any entry of out_maps, as
+   for lg_score_maps (library workspace is used for what is left out; the result rows name the same grasp pixel whichever
+   subset is taken back).  results: HOST array of B.  Synchronises `stream` before returning. */
 int lg_select_grasp(lg_handle h, const float* depth, const uint8_t* mask, int B, int H, int W,
                     const lg_params* p, float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid,
                     lg_grasp_result* results, void* stream);
