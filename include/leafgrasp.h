@@ -615,6 +615,37 @@ int lg_train_get_state(lg_trainer* t, float* params, float* buffers, float* exp_
 int lg_train_step(lg_trainer* t, const float* x, const float* labels, int N, const float* masks, uint64_t seed,
                   const lg_train_hparams* hp, int apply_update, float* loss_host, float* grad_norm_host, float* logits_dev);
 int lg_train_sync(lg_trainer* t);
+/* lg_train_epoch: the steps of one epoch in one call, nothing between them on the host -- it leaves every float where the
+   same sequence of lg_train_step(masks = NULL, apply_update = 1) calls leaves it.
+     x [n][9][32][32], labels [n]   DEVICE, 16-byte aligned x: the whole training set; it stays where it is.
+     idx [m]                        HOST: sample numbers in drawing order (what WeightedRandomSampler / torch.multinomial
+                                    returns).  Every entry is checked against [0, n) before anything is enqueued.
+   Step k takes idx[k * batch .. min(m, (k + 1) * batch)) in that order; a last step of fewer than 2 samples is skipped
+   (BatchNorm in train mode), m < 2 runs no step: lg_train_epoch_plan states the rule on the host (number of steps, size of
+   the last one run, 0 when there is none), without a device or a trainer; LG_ERR_INVALID for batch < 2 or m outside
+   [0, INT32_MAX].  Per step, on the trainer's stream: a gather kernel writes the step's rows straight into the step's input
+   buffers (in place of lg_train_step's device-to-device copies), the step runs with dropout masks drawn on the device from
+   `seed` and the device's step counter, and a one-workgroup kernel files loss and gradient norm into device slot k, adds
+   the step's correct predictions to a device counter and copies its logits to logits_dev + k * batch.  idx, hp and seed
+   are uploaded once; one copy-back and one stream synchronisation end the call.
+     losses, grad_norms             HOST, capacity lg_train_epoch_plan's n_steps
+     correct                        HOST: predictions with (logit > 0) == (label == 1).  trainer.py's fit() writes
+                                    sigmoid(logit) > 0.5 in float32; the two differ only for 0 < logit <~ 1.2e-7, where
+                                    the float32 sigmoid rounds to exactly 0.5
+     logits_dev                     DEVICE [m]; the entries of a skipped tail are not written
+     n_steps                        HOST: steps run.  Any of these five may be NULL.
+   LG_ERR_INVALID, with the trainer untouched: an index outside [0, n), batch outside [2, max_batch], a NULL t / x / labels /
+   hp, a NULL idx with m > 0, n or m above INT32_MAX, x not 16-byte aligned.
+   LG_TRAIN_STREAMS=2 is honoured (the step's last act is to wait for its side stream, so consecutive steps cannot overlap
+   on the shared buffers).  LG_TRAIN_GRAPH=1 is not: the epoch always issues plain launches, because a captured step
+   replayed back to back without a host synchronisation in between has never been run, and the memset node that step once
+   replayed wrongly (see lg_train_step in lg_train.hip) is reason enough not to start here.
+   A HIP error in the middle returns its code; the weights are then whatever the completed steps left, and the step count
+   lg_train_get_state reports counts the steps enqueued up to there. */
+int lg_train_epoch(lg_trainer* t, const float* x, const float* labels, int64_t n, const int32_t* idx, int64_t m, int batch,
+                   uint64_t seed, const lg_train_hparams* hp, float* losses, float* grad_norms, int64_t* correct,
+                   float* logits_dev, int32_t* n_steps);
+int lg_train_epoch_plan(int64_t m, int batch, int32_t* n_steps, int32_t* last_n);
 /* Data-parallel training (one process per GPU): lg_train_step(apply_update = 0) on the rank's shard of the batch, average
    the flat gradient vector over the ranks (RCCL all-reduce on a tensor wrapping *dev_ptr; lg_train_sync first), then
    lg_train_apply = clip_grad_norm_ + Adam.step() on the averaged gradients (train_model.py:256-258).  BatchNorm statistics

@@ -177,6 +177,9 @@ SYMBOLS = {
     "lg_train_set_state": (C.c_int, [_VP, _FP, _FP, _FP, _FP, C.c_int64]),
     "lg_train_get_state": (C.c_int, [_VP, _FP, _FP, _FP, _FP, _FP, C.POINTER(C.c_int64)]),
     "lg_train_step": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, C.c_uint64, C.POINTER(LgTrainHparams), C.c_int, _FP, _FP, _VP]),
+    "lg_train_epoch": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int, C.c_uint64,
+                                 C.POINTER(LgTrainHparams), _FP, _FP, C.POINTER(C.c_int64), _VP, C.POINTER(C.c_int32)]),
+    "lg_train_epoch_plan": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lg_train_sync": (C.c_int, [_VP]),
     "lg_train_grad_buffer": (C.c_int, [_VP, C.POINTER(_FP), C.POINTER(C.c_int64)]),
     "lg_train_apply": (C.c_int, [_VP, C.POINTER(LgTrainHparams), _FP]),

@@ -888,6 +888,44 @@ __global__ void lgt_mask_kernel(float* __restrict__ mask, MaskTable T, const uin
     mask[i] = u >= p ? 1.0f / (1.0f - p) : 0.0f;
 }
 
+// ------------------------------------------------------------------------------------------------ device epoch
+constexpr int kRowVec = 9 * 1024 / 4;   // one sample [9][32][32] as 16-byte pieces
+// One step's batch straight into the step's input buffers: row r of xin / lab is sample idx[r] of the training set.
+// grid (N, kRowVec / 256), one 16-byte load and store per thread; the host has checked every index against the set.
+__global__ __launch_bounds__(256) void lgt_gather_kernel(const float4* __restrict__ x, const float* __restrict__ labels,
+                                                         const int32_t* __restrict__ idx, float4* __restrict__ xin,
+                                                         float* __restrict__ lab) {
+    const int r = blockIdx.x;
+    const size_t src = (size_t)idx[r];
+    const int v = blockIdx.y * 256 + threadIdx.x;
+    xin[(size_t)r * kRowVec + v] = x[src * kRowVec + v];
+    if (v == 0) lab[r] = labels[src];
+}
+
+// What the host reads after a step, filed on the device instead: loss and gradient norm into slot k, the step's correct
+// predictions ((logit > 0) == (label == 1)) added to the epoch's counter, the logits behind those of the steps before.
+// One workgroup; the steps of an epoch are in stream order, so the counter needs no atomic.
+__global__ __launch_bounds__(256) void lgt_file_step_kernel(const float* __restrict__ loss, const float* __restrict__ state,
+                                                            const float* __restrict__ logits, const float* __restrict__ lab,
+                                                            int N, int k, float* __restrict__ losses,
+                                                            float* __restrict__ grad_norms,
+                                                            unsigned long long* __restrict__ correct,
+                                                            float* __restrict__ logits_out) {
+    __shared__ float s_red[4];
+    float c = 0.0f;   // a count of at most N <= 8192: exact in float
+    for (int n = threadIdx.x; n < N; n += 256) {
+        const float z = logits[n];
+        c += ((z > 0.0f) == (lab[n] == 1.0f)) ? 1.0f : 0.0f;
+        if (logits_out) logits_out[n] = z;
+    }
+    c = block_sum(c, s_red);
+    if (threadIdx.x == 0) {
+        losses[k] = loss[0];
+        grad_norms[k] = state[1];
+        correct[0] += (unsigned long long)c;
+    }
+}
+
 }  // namespace
 
 // ================================================================================================= host side
@@ -929,6 +967,8 @@ struct lg_trainer {
     bool use_graph = false;                      // LG_TRAIN_GRAPH=1: replay the step as a captured graph (measured: no gain)
     std::map<uint64_t, hipGraphExec_t> graphs;   // key: N, masks drawn on the device, optimizer applied
     int64_t steps = 0;
+    void* epoch_dev = nullptr;                   // lg_train_epoch: counter, loss and norm slots, indices; grown on demand
+    size_t epoch_bytes = 0;
     std::string err;
     std::vector<void*> allocs;
 };
@@ -1178,6 +1218,7 @@ int lg_train_destroy(lg_trainer* tr) {
         if (tr->ev_wg[k]) hipEventDestroy(tr->ev_wg[k]);
     }
     for (void* q : tr->allocs) hipFree(q);
+    if (tr->epoch_dev) hipFree(tr->epoch_dev);
     delete tr;
     return LG_OK;
 }
@@ -1469,6 +1510,77 @@ int lg_train_step(lg_trainer* tr, const float* x, const float* labels, int N, co
         if (loss_host) *loss_host = l;
         if (grad_norm_host) *grad_norm_host = st[1];
     }
+    return LG_OK;
+}
+
+// fit()'s batching rule (trainer.py, train_model.py:247): batches of `batch` in drawing order, a last one of fewer than 2
+// samples skipped.  Host arithmetic only.
+int lg_train_epoch_plan(int64_t m, int batch, int32_t* n_steps, int32_t* last_n) {
+    if (m < 0 || m > INT32_MAX || batch < 2) return LG_ERR_INVALID;
+    const int64_t full = m / batch, tail = m % batch;
+    const int64_t steps = full + (tail >= 2 ? 1 : 0);
+    if (n_steps) *n_steps = (int32_t)steps;
+    if (last_n) *last_n = (int32_t)(tail >= 2 ? tail : (full > 0 ? batch : 0));
+    return LG_OK;
+}
+
+// One epoch of lg_train_step calls without the host between them (see include/leafgrasp.h).  Always plain launches.
+int lg_train_epoch(lg_trainer* tr, const float* x, const float* labels, int64_t n, const int32_t* idx, int64_t m, int batch,
+                   uint64_t seed, const lg_train_hparams* hp, float* losses, float* grad_norms, int64_t* correct,
+                   float* logits_dev, int32_t* n_steps) {
+    if (!tr || !x || !labels || !hp) return LG_ERR_INVALID;
+    if (n < 0 || n > INT32_MAX || m < 0 || m > INT32_MAX || (m > 0 && !idx)) { tr->err = "lg_train_epoch: n and m must be in [0, INT32_MAX], idx given"; return LG_ERR_INVALID; }
+    if (batch < 2 || batch > tr->capN) { tr->err = "lg_train_epoch: batch must be in [2, max_batch] (BatchNorm needs a batch)"; return LG_ERR_INVALID; }
+    if (((uintptr_t)x & 15) != 0) { tr->err = "lg_train_epoch: x must be 16-byte aligned"; return LG_ERR_INVALID; }
+    for (int64_t i = 0; i < m; i++)
+        if (idx[i] < 0 || (int64_t)idx[i] >= n) { tr->err = "lg_train_epoch: idx[" + std::to_string(i) + "] outside [0, n)"; return LG_ERR_INVALID; }
+    int32_t steps = 0, last = 0;
+    lg_train_epoch_plan(m, batch, &steps, &last);
+    if (n_steps) *n_steps = steps;
+    if (correct) *correct = 0;
+    if (steps == 0) return LG_OK;
+
+    hipSetDevice(tr->device);
+    hipStream_t s = tr->stream;
+    // device scratch: [correct u64][losses steps][grad norms steps][idx m]; the first three come back in one copy
+    const size_t res_bytes = 8 + (size_t)steps * 8, need = res_bytes + (size_t)m * 4;
+    if (need > tr->epoch_bytes) {
+        TR_HIP(hipStreamSynchronize(s));
+        if (tr->epoch_dev) TR_HIP(hipFree(tr->epoch_dev));
+        tr->epoch_dev = nullptr;
+        tr->epoch_bytes = 0;
+        if (hipMalloc(&tr->epoch_dev, need) != hipSuccess) { tr->epoch_dev = nullptr; tr->err = "hipMalloc failed"; return LG_ERR_NOMEM; }
+        tr->epoch_bytes = need;
+    }
+    unsigned long long* d_correct = (unsigned long long*)tr->epoch_dev;
+    float* d_losses = (float*)((char*)tr->epoch_dev + 8);
+    float* d_norms = d_losses + steps;
+    int32_t* d_idx = (int32_t*)((char*)tr->epoch_dev + res_bytes);
+    TR_HIP(hipMemcpyAsync(d_idx, idx, (size_t)m * 4, hipMemcpyHostToDevice, s));
+    TR_HIP(hipMemsetAsync(d_correct, 0, 8, s));
+    const AdamHp h = {hp->lr, hp->beta1, hp->beta2, hp->eps, hp->weight_decay, hp->max_grad_norm, hp->pos_weight, 0.0f};
+    TR_HIP(hipMemcpyAsync(tr->hp, &h, sizeof(h), hipMemcpyHostToDevice, s));
+    TR_HIP(hipMemcpyAsync(tr->seed_dev, &seed, sizeof(seed), hipMemcpyHostToDevice, s));
+    for (int32_t k = 0; k < steps; k++) {
+        const int N = k == steps - 1 ? last : batch;
+        const size_t first = (size_t)k * batch;
+        hipLaunchKernelGGL(lgt_gather_kernel, dim3(N, kRowVec / 256), dim3(256), 0, s, (const float4*)x, labels,
+                           (const int32_t*)(d_idx + first), (float4*)tr->xin, tr->labels);
+        TR_HIP(hipMemsetAsync(tr->G, 0, tr->n_params * 4, s));   // where lg_train_step has it: see the note there
+        const int rc = enqueue_step(tr, N, /*draw_masks*/ true, /*apply_update*/ 1);
+        if (rc != LG_OK) return rc;
+        tr->steps++;
+        hipLaunchKernelGGL(lgt_file_step_kernel, dim3(1), dim3(256), 0, s, (const float*)tr->loss, (const float*)tr->state,
+                           (const float*)tr->logits, (const float*)tr->labels, N, (int)k, d_losses, d_norms, d_correct,
+                           logits_dev ? logits_dev + first : (float*)nullptr);
+    }
+    TR_HIP(hipGetLastError());
+    std::vector<unsigned char> back(res_bytes);
+    TR_HIP(hipMemcpyAsync(back.data(), tr->epoch_dev, res_bytes, hipMemcpyDeviceToHost, s));
+    TR_HIP(hipStreamSynchronize(s));
+    if (correct) { unsigned long long c = 0; memcpy(&c, back.data(), 8); *correct = (int64_t)c; }
+    if (losses) memcpy(losses, back.data() + 8, (size_t)steps * 4);
+    if (grad_norms) memcpy(grad_norms, back.data() + 8 + (size_t)steps * 4, (size_t)steps * 4);
     return LG_OK;
 }
 

@@ -361,6 +361,41 @@ class GraspTrainer:
             return loss.value, logits, gnorm.value
         return loss.value
 
+    def train_epoch(self, features, labels, idx, batch_size, return_logits=False):
+        """The steps of one epoch in one call (lg_train_epoch): step k trains on features[idx[k*batch_size:(k+1)*batch_size]],
+        gathered on the device, with dropout masks drawn there as train_step draws them with masks=None; a last batch of
+        fewer than 2 samples is skipped, as fit() skips it.  Every float ends where the same train_step calls leave it.
+        features [n,9,32,32] and labels [n]: contiguous float32 tensors on this trainer's device (the whole training set);
+        idx: anything np.asarray(..., np.int32) takes, in drawing order.  Returns {"losses": np.float32[n_steps],
+        "grad_norms": np.float32[n_steps], "correct": int, "n_steps": int}, with return_logits also "logits": a device
+        tensor [len(idx)] whose skipped-tail entries are NaN.  correct counts (logit > 0) == (label == 1)."""
+        for t, what in ((features, "features"), (labels, "labels")):
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous() and t.device.type == "cuda"
+                    and (t.device.index == self.device.index or self.device.index is None)):
+                raise ValueError(f"{what} must be a contiguous float32 tensor on {self.device}")
+        n = labels.shape[0]
+        if tuple(features.shape) != (n, 9, 32, 32) or labels.dim() != 1:
+            raise ValueError("features must be [n,9,32,32] and labels [n]")
+        ix = np.ascontiguousarray(np.asarray(idx, np.int32).reshape(-1))
+        m = ix.shape[0]
+        plan = C.c_int32()
+        if lib.lg_train_epoch_plan(m, int(batch_size), C.byref(plan), None) != 0:
+            raise ValueError(f"batch size {batch_size} below 2 (BatchNorm in train mode needs N > 1)")
+        losses, gnorms = np.empty(plan.value, np.float32), np.empty(plan.value, np.float32)
+        logits = torch.full((m,), float("nan"), dtype=torch.float32, device=self.device) if return_logits else None
+        correct, n_steps = C.c_int64(), C.c_int32()
+        torch.cuda.current_stream(self.device).synchronize()   # the library works on its own stream
+        self._check(lib.lg_train_epoch(self._h, features.data_ptr(), labels.data_ptr(), n,
+                                       ix.ctypes.data_as(C.POINTER(C.c_int32)), m, int(batch_size), self.seed,
+                                       C.byref(self.hp), losses.ctypes.data_as(_FP), gnorms.ctypes.data_as(_FP),
+                                       C.byref(correct), logits.data_ptr() if logits is not None else None,
+                                       C.byref(n_steps)), "lg_train_epoch")
+        self.num_batches_tracked += n_steps.value
+        out = {"losses": losses, "grad_norms": gnorms, "correct": int(correct.value), "n_steps": int(n_steps.value)}
+        if return_logits:
+            out["logits"] = logits
+        return out
+
     # ------------------------------------------------------------------ data parallel (one process per GPU)
     def gradient_tensor(self):
         """The library's flat gradient vector as a torch tensor (no copy): what the ranks all-reduce."""
@@ -412,13 +447,15 @@ class GraspTrainer:
     # ------------------------------------------------------------------ epoch loop (train_model.py:155-356)
     def fit(self, features, labels, num_epochs=150, batch_size=16, val_fraction=0.2, save_dir=None, patience=15,
             min_delta=0.001, sched_factor=0.5, sched_patience=5, min_lr=1e-6, normalization_stats=None, log=print,
-            device_eval=False):
+            device_eval=False, device_epoch=False):
         """80/20 split, weighted sampling with replacement, ReduceLROnPlateau(min, 0.5, 5, min_lr 1e-6),
         EarlyStopping(15, 0.001, restore best weights), best_model.pth with the reference's checkpoint keys.
         The last incomplete batch of an epoch is used when it has at least 2 samples (a batch of 1 raises in the
         reference: BatchNorm1d in train mode).  device_eval=True: the epoch's validation is one evaluate() call (weights
         handed to the inference CNN on the device, loss and counts reduced there) instead of state_dict() + reload + a
-        loss per batch; the loss is then summed in double, so it agrees with the float32 loop to ~1e-6 relative."""
+        loss per batch; the loss is then summed in double, so it agrees with the float32 loop to ~1e-6 relative.
+        device_epoch=True: the epoch's training steps are one train_epoch() call (batches gathered on the device, no host
+        round trip between steps) instead of a train_step() per batch; the weights and the history come out the same."""
         gen = torch.Generator().manual_seed(self.seed)
         feats = torch.as_tensor(features, dtype=torch.float32).to(self.device)
         labs = torch.as_tensor(labels, dtype=torch.float32).to(self.device)
@@ -437,15 +474,22 @@ class GraspTrainer:
         scheduler = PlateauScheduler(self, factor=sched_factor, patience=sched_patience, min_lr=min_lr)
         train_losses, val_losses, metrics_history = [], [], []
         for epoch in range(num_epochs):
-            idx = torch.multinomial(w.cpu(), n_tr, replacement=True, generator=gen).to(self.device)
+            idx = torch.multinomial(w.cpu(), n_tr, replacement=True, generator=gen)
             tot, nb, correct = 0.0, 0, 0
-            for s in range(0, n_tr, batch_size):
-                bi = idx[s:s + batch_size]
-                if bi.numel() < 2:
-                    continue
-                loss, logits, _ = self.train_step(tr_x[bi], tr_y[bi], return_logits=True)
-                tot, nb = tot + loss, nb + 1
-                correct += ((torch.sigmoid(logits) > 0.5).float() == tr_y[bi]).sum().item()
+            if device_epoch:
+                ep = self.train_epoch(tr_x, tr_y, idx.numpy(), batch_size)
+                for loss in ep["losses"]:   # the same Python-float sum, in the same order, as the loop below
+                    tot += float(loss)
+                nb, correct = ep["n_steps"], ep["correct"]
+            else:
+                idx = idx.to(self.device)
+                for s in range(0, n_tr, batch_size):
+                    bi = idx[s:s + batch_size]
+                    if bi.numel() < 2:
+                        continue
+                    loss, logits, _ = self.train_step(tr_x[bi], tr_y[bi], return_logits=True)
+                    tot, nb = tot + loss, nb + 1
+                    correct += ((torch.sigmoid(logits) > 0.5).float() == tr_y[bi]).sum().item()
             train_losses.append(tot / max(nb, 1))
             if device_eval:
                 ev = self.evaluate(va_x, va_y, selector=sel, batch_size=batch_size)
@@ -482,7 +526,7 @@ class GraspTrainer:
 
 
 def train_grasp_model(data_path=None, save_dir=None, device="cuda:0", num_epochs=150, log=print, device_eval=False,
-                      **trainer_kwargs):
+                      device_epoch=False, **trainer_kwargs):
     """scripts/train_model.py::train_grasp_model (:155-395) on this path: torch.manual_seed(42), load
     ~/leaf_grasp_output/ml_training_data/training_data.pt (EnhancedGraspDataCollector's file; loaded with weights_only=True),
     normalise, 80/20 split, weighted sampling, Adam / ReduceLROnPlateau / EarlyStopping, best_model.pth + final_model.pth in
@@ -498,7 +542,7 @@ def train_grasp_model(data_path=None, save_dir=None, device="cuda:0", num_epochs
         log(f"Combined features shape: {tuple(features.shape)}")
     trainer = GraspTrainer(torch.device(device), **trainer_kwargs)
     hist = trainer.fit(features, labels, num_epochs=num_epochs, save_dir=save_dir, normalization_stats=stats, log=log,
-                       device_eval=device_eval)
+                       device_eval=device_eval, device_epoch=device_epoch)
     torch.save({"epoch": len(hist["val_losses"]) - 1, "model_state_dict": trainer.state_dict(),
                 "optimizer_state_dict": trainer.torch_optimizer_state_dict(),
                 "val_loss": hist["val_losses"][-1] if hist["val_losses"] else None,
