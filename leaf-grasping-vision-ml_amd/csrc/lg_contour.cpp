@@ -15,7 +15,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "lg_internal.h"
+#include "lg_contour.h"
 
 namespace {
 

@@ -48,7 +48,7 @@ __device__ __forceinline__ uint32_t lg_wave_min_u32(uint32_t v) {
 }
 
 // ============================================================================ sweep window (mask bounding box)
-// One workgroup, thread = frame (frames t, t + 1024, ...): LgWin of every frame (lg_win_from_box, lg_internal.h) from the bounding
+// One workgroup, thread = frame (frames t, t + 1024, ...): LgWin of every frame (lg_win_from_box, lg_dt.h) from the bounding
 // box and area the bit-row pass left in the frame's maxfix words.
 //
 // Search or sweeps is decided for the BATCH (search_mode 2): the search's time grows like the sum over the frames of area^1.5

@@ -3,7 +3,8 @@
 // each complement by two raster sweeps, and the plane on the pixels of the current leaf.  Reference semantics:
 // scripts/utils/grasp_point_selector.py:595-633 with `other_leaves` taken from the label image.  Nothing here runs while the
 // mode is off.
-#include "lg_internal.h"
+#include "lg_iso.h"
+#include "lg_bits.h"
 #include "lg_wave.h"
 
 #include <algorithm>

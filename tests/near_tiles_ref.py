@@ -4,7 +4,7 @@ ty0+15+HALO reflected at the frame border, and can only meet the mask when
 
     bx1 >= bx0 and bx0 <= tx0 + 71 and bx1 >= tx0 - 8 and by0 <= ty0 + 15 + HALO and by1 >= ty0 - 16 - HALO
 
-for the mask's bounding box [bx0, bx1] x [by0, by1].  The library states this once (lg_near_tiles in lg_internal.h, exported as
+for the mask's bounding box [bx0, bx1] x [by0, by1].  The library states this once (lg_near_tiles in lg_planes.h, exported as
 lg_near_tile_rect); nothing here calls it."""
 import numpy as np
 

@@ -114,7 +114,7 @@ def subset_id(planes, valid):
 
 def store_form(planes, valid, entry="score_maps", model=False):
     """Which store form of lg_final_kernel a call reaches -- a pure function of the pointers, the entry and the model
-    (lg_select.hip: take_planes, lg_kernels.hip: lg_launch_final).  take_planes fills in workspace planes for distance and
+    (lg_select.hip: take_planes, lg_planes.hip: lg_launch_final).  take_planes fills in workspace planes for distance and
     traditional always, for all eight when a model is loaded and the planes are not deferred, and the workspace validity plane
     when out_valid is NULL; lg_launch_final then takes ALL when no pointer is left NULL.
       "all"      every plane given (with or without validity), or a non-sparse lg_select_grasp* call with a model loaded

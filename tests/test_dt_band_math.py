@@ -1,5 +1,5 @@
 """The two identities the band form of the sweep-free distance transform rests on (lg_dtseed_kernel's seed pairs +
-lg_dtband_kernel, csrc/lg_kernels.hip), checked on the CPU against the integers of the oracle's two-pass chamfer transform:
+lg_dtband_kernel, csrc/lg_dt.hip), checked on the CPU against the integers of the oracle's two-pass chamfer transform:
   1. with h = the run distance of a pixel's own row, U(y) = min(A h, the 5 x 5 stencil over U(y - 1), U(y - 2)) is the distance to
      the nearest zero pixel at or above the row -- no in-row scan; the mirrored D, and d = min(U, D);
   2. the same recurrence started from the TRUE d on two adjacent rows, downwards from the pair above a band and upwards from the

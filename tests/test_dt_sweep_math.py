@@ -1,4 +1,4 @@
-"""What form 6 of the sweep-free distance transform (lg_dtsweep_kernel, csrc/lg_kernels.hip) does beyond identity (1) of
+"""What form 6 of the sweep-free distance transform (lg_dtsweep_kernel, csrc/lg_dt.hip) does beyond identity (1) of
 tests/test_dt_band_math.py, restated in NumPy and checked against the integers of the oracle's two-pass chamfer transform:
   * U and D run over the rows of the mask's bounding box only, and over a span of `lanes` x E columns that starts at the box's
     first column rounded down to a multiple of 4 (E = the smallest of 4, 8, 16, 32 that holds the box); cells above / below the

@@ -38,7 +38,7 @@ from tests.test_gpu_sparse_planes import _assert_sparse_equals_dense  # noqa: E4
 from tests.test_window_box_host import lib_window  # noqa: E402
 
 FORCED = {"auto": 0, "search1": 1, "bands": 5, "sweep": 6}    # LG_DT_SEARCH_ALGO of each entry of DT_FORMS that searches
-SEARCH_BUDGET = 2.0e7                                          # LG_SEARCH_BUDGET (lg_internal.h)
+SEARCH_BUDGET = 2.0e7                                          # LG_SEARCH_BUDGET (lg_dt.h)
 SMALL_ALL_FORMS = [(8, 8), (8, 9), (9, 8), (16, 16)]           # 16 x 16 and below: the forms differ (1 forced / 5 and 6 at sixteen)
 
 

@@ -4,7 +4,7 @@ The calls go through ctypes on a GraspPointSelector's handle; cases and subsets:
 pixels, no near-tie, the tile classes of the two frames): tests/test_plane_outputs_host.py.
 
 Which lg_final_kernel<VEC, ALL, R, SCORE> a call reaches is a pure function of (W % 4, gaussian_size, the NULL pointers, the
-entry, a loaded model) -- lg_select.hip take_planes, lg_kernels.hip lg_launch_final; plane_outputs.store_form restates it:
+entry, a loaded model) -- lg_select.hip take_planes, lg_planes.hip lg_launch_final; plane_outputs.store_form restates it:
   VEC    = W % 4 == 0                                     264 / 263
   R      = gaussian_size / 2                              0, 1, 2, 3
   SCORE  = lg_select_grasp* with no plane and no validity (sparse mode, deferred planes)
@@ -16,7 +16,7 @@ entry, a loaded model) -- lg_select.hip take_planes, lg_kernels.hip lg_launch_fi
     <true,  false, 2> / <false, false, 2>   test_score_maps_every_subset[264 / 263], test_select_grasp_named_subsets[*-no model]
     <true,  false, 0 / 1 / 3>               test_score_maps_named_subsets[264-*-g1 / g3 / g7], test_select_grasp_other_radii[264-*]
     <false, false, 0 / 1 / 3>               test_score_maps_named_subsets[263-*-g1 / g3 / g7], test_select_grasp_other_radii[263-*]
-The partial form squares the gradient with the other product fused (lg_flat4<VEC && (ALL || SCORE)>, lg_kernels.hip:419-422):
+The partial form squares the gradient with the other product fused (lg_flat4<VEC && (ALL || SCORE)>, lg_pixel.h):
 its flatness and traditional planes may differ from a full call's in the last bit, by design.  Nothing here compares floats
 between subsets; every call is held to the oracle at the project's tolerances, and the rows to the same grasp pixel.
 

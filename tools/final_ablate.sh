@@ -3,7 +3,7 @@
 # written), 16 = the memory traffic without the arithmetic (planes written from the loaded values right after staging).
 # LG_NO_SKIP=1 (every tile on the stencil path; same results) stays a runtime switch.  usage (GPU box): bash tools/final_ablate.sh
 set -e
-LG_VARIANT_SRC=lg_kernels.hip bash tools/build_variants.sh "fin_nostore:-DLG_FINAL_ABLATE=8" "fin_noarith:-DLG_FINAL_ABLATE=16"
+LG_VARIANT_SRC=lg_planes.hip bash tools/build_variants.sh "fin_nostore:-DLG_FINAL_ABLATE=8" "fin_noarith:-DLG_FINAL_ABLATE=16"
 V=leaf-grasping-vision-ml_amd/csrc/variants
 for round in 1 2; do
 for lib in "" $V/liblgrasp_fin_nostore.so $V/liblgrasp_fin_noarith.so; do
