@@ -639,7 +639,7 @@ int lg_train_sync(lg_trainer* t);
    LG_TRAIN_STREAMS=2 is honoured (the step's last act is to wait for its side stream, so consecutive steps cannot overlap
    on the shared buffers).  LG_TRAIN_GRAPH=1 is not: the epoch always issues plain launches, because a captured step
    replayed back to back without a host synchronisation in between has never been run, and the memset node that step once
-   replayed wrongly (see lg_train_step in lg_train.hip) is reason enough not to start here.
+   replayed wrongly (see zero_grads in lg_train.hip) is reason enough not to start here.
    A HIP error in the middle returns its code; the weights are then whatever the completed steps left, and the step count
    lg_train_get_state reports counts the steps enqueued up to there. */
 int lg_train_epoch(lg_trainer* t, const float* x, const float* labels, int64_t n, const int32_t* idx, int64_t m, int batch,

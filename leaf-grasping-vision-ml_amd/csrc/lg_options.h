@@ -44,7 +44,7 @@ struct LgCnnOptions {   // a model's (standard encoder): read once per load, so 
 struct LgTrainOptions {   // a trainer's: read once per lg_train_create
     bool graph = false;          // LG_TRAIN_GRAPH=1: replay the step as a captured graph (measured: no gain)
     int streams = 1;             // LG_TRAIN_STREAMS=2: backward-weights on a second stream; 1: in line
-    int conv_small_below = 256, conv_split_below = 256;   // LG_TRAIN_CONV_SMALL / LG_TRAIN_CONV_SPLIT: convolution shape thresholds (launch_conv)
+    int conv_small_below = 256, conv_split_below = 256;   // LG_TRAIN_CONV_SMALL / LG_TRAIN_CONV_SPLIT: convolution shape thresholds (lgt_conv)
 };
 LgOptions lg_options_from_env();
 LgCnnOptions lg_cnn_options_from_env();

@@ -194,7 +194,7 @@ def test_train_step_with_dropout_masks_vs_oracle(att, filt, n, seed):
         assert_close_robust(opt["exp_avg_sq"][k].numpy(), ref2["opt_state"]["exp_avg_sq"][k], 4e-2, 1e-9, 0.05, 0.1, what="v " + k)
 
 
-# lgt_conv_kernel's three shapes (launch_conv in lg_train.hip; forward and dgrad): large (256 px x 64 channels, several samples
+# lgt_conv_kernel's three shapes (lgt_conv in lg_train_conv.hip; forward and dgrad): large (256 px x 64 channels, several samples
 # per tile on the 8 x 8 and 4 x 4 layers), small, K-split.  The thresholds are read at lg_train_create: the environment forces
 # one form on every layer it can take (the K-split needs 32 input channels; layer 0 keeps its own choice there).
 CONV_FORMS = {"large": {"LG_TRAIN_CONV_SMALL": "0", "LG_TRAIN_CONV_SPLIT": "0"},

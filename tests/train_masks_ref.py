@@ -1,5 +1,5 @@
 """NumPy restatement of the device-drawn dropout keep masks of the trainer (include/leafgrasp.h: masks = NULL, "drawn on the
-device from `seed` and the step counter"; lgt_mask_kernel in lg_train.hip).
+device from `seed` and the step counter"; lgt_mask_kernel in lg_train_optim.hip).
 
 One counter-based hash per mask entry.  The entries of all dropout layers form one flat vector laid out [layer][N][width]
 in dropout_layout(filters) order; entry i (0-based) gets
