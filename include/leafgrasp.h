@@ -26,6 +26,9 @@
  *   lg_select_grasp    GraspPointSelector.select_grasp_point :184-253 (whole path, batched)
  *   lg_select_grasp_candidates   the per-candidate log lines of its selection loop :210-236, every candidate ranked
  *   lg_select_grasp_ml   the commented-out "grasp point based on only ML model" select_grasp_point :290-390 (batched)
+ *   lg_select_grasp_collect   the select_grasp_point that calls collect_sample (scripts/utils/grasp_point_selector_bkp.py:73-169):
+ *                      eroded safe zone, tip penalty, plain arg-max, centroid fallback (batched); lg_erode_ellipse, lg_tip_penalty
+ *                      and lg_argmax_first are its stages on their own
  *   lg_harvest_patches / lg_negative_masks / lg_leaf_contour   EnhancedGraspDataCollector's patch extraction and
  *                      negative-region helpers (scripts/utils/ml_grasp_optimizer/data_collector.py:91-173,426-490)
  *   lg_leaf_stats      the per-leaf passes of OptimalLeafSelector.select_optimal_leaf
@@ -350,6 +353,63 @@ int lg_ml_sample_points_host(const uint64_t* bits, int H, int W, int WW, const l
    measurement; LG_DEFER_PLANES=0 at lg_create: form 2).  Holds for the handle's later calls.
    *last (may be NULL) = the form the last lg_select_grasp_ml* call on this handle took, 0: none yet.  Same results either way. */
 int lg_debug_ml_planes(lg_handle h, int form, int32_t* last);
+
+/* ---- the collecting selector: the select_grasp_point that feeds the data collector (scripts/utils/grasp_point_selector_bkp.py
+   :73-169, "bkp" below; the only caller of collect_sample in the reference).  DESIGN 2 quirk 16 has the details.  Per frame:
+     safe      cv2.erode(mask, ellipse(erosion_kernel_size), iterations = erosion_iterations) (bkp:79-82); the frame border does
+               not erode.
+     planes    sdf, approach, isolation, distance, accessibility, stem and the leaf angle on `safe`; flatness on depth * the
+               ORIGINAL mask (bkp:88-89), a whole-frame plane.
+     tip       the tip penalty as written (bkp:395-408): `(~tip_area).astype(np.uint8)` has no zero pixel, so its 5 x 5 transform is
+               chamfer_init_dist0 + 65536 min(x + 1, y + 1, W - x, H - y) in 16.16 integers; penalty = (1 - d / (max d + 1e-6)) on
+               `safe`, 0 elsewhere (float32, as the isolation plane).  A ramp of a few per cent from the frame border.
+     fusion    trad = float32(w_approach approach + w_sdf sdf + w_flat flatness + w_tip (1 - tip)) (1 - stem) valid, valid =
+               (distance > min_edge_distance) & safe (bkp:98-108): no accessibility term, no stem threshold.  The sum is taken in
+               double from the float32 planes.  Outside the bounding box of `safe` both are exactly 0.
+     point     any trad > 0: np.argmax(trad), the first maximum in row-major order, a NaN counting as the maximum; else the
+               centroid of the ORIGINAL mask, sum x / n and sum y / n in double from integer sums, rounded to float32, truncated
+               (torch's float32 mean may differ from that in the last bit: DESIGN).  Empty original mask: found = 0.
+     result    x, y = the point; X, Y, Z, has_pre, pX, pY, pZ by the code lg_select_grasp runs for its pick, the pre-grasp probes
+               on dilate(safe, ellipse 2 pregrasp_clearance + 1) (bkp:82 reassigns the mask); n_candidates 1 for an arg-max
+               point, 0 for the centroid; best_score = np.max(trad); theta = the angle of `safe`; ml_used 0.
+   lg_params here: w_approach, w_sdf, w_flat the three weights, min_edge_distance the 20; w_access, stem_valid_thresh, top_k are not
+   read; label_aware = 1 is LG_ERR_INVALID.  lg_collect_params: NULL = the defaults.  tip_aware = 1 (the method's stated intent: the
+   transform of the tip area itself) is not built: LG_ERR_UNSUPPORTED.
+   lg_collect_params_check (no device, no handle): the rule every entry below applies to the two structs (either may be NULL =
+   defaults) -- LG_ERR_UNSUPPORTED for an even or out-of-range erosion_kernel_size (1..63), erosion_iterations outside 0..8,
+   tip_aware = 1, and with it a tip_se that is even or outside 3..63; LG_ERR_INVALID for any other tip_aware and for label_aware != 0.
+   lg_erode_ellipse        safe alone: mask, out u8 [B][H][W] DEVICE (0 / 1; nonzero mask bytes count as 1).  Enqueued on `stream`.
+   lg_erode_words_host     the same on the host (no device, no handle) for one frame of bit rows [H][WW] (bit j of word w = pixel
+                           64 w + j; bits past W are ignored and come out 0) -- the per-word code of the device.
+   lg_tip_penalty          the tip plane alone on a given `safe` (u8, DEVICE): out f32 [B][H][W]; out_tip_area u8 [B][H][W] or NULL,
+                           zeros unless tip_aware.  p: NULL = defaults (chamfer_init_dist0 is read).  Enqueued on `stream`.
+   lg_tip_fix_host         the 16.16 field of the tip penalty as written over a whole H x W frame (no device, no handle), and its
+                           maximum in *max_fix (may be NULL): what the device evaluates on the pixels of `safe`.
+   lg_argmax_first         per frame of a handed plane f32 [B][H][W] DEVICE: xy_host [B][2] = np.argmax as (x, y), max_host [B] =
+                           np.max (NaN when the plane holds one), any_positive_host [B] = (plane > 0).any(); each may be NULL.
+                           Synchronises `stream`.
+   lg_select_grasp_collect the whole of it.  out_maps[i] (any may be NULL, and out_maps itself), out_tip f32, out_safe u8, out_valid
+                           u8: [B][H][W] DEVICE or NULL; out_maps[LG_MAP_TRADITIONAL] is the fused plane above.  The result rows do
+                           not depend on which outputs are taken.  results: HOST array of B.  Synchronises `stream`. */
+typedef struct lg_collect_params {
+    int32_t erosion_kernel_size;  /* 21 (bkp:30); odd, 1..63 */
+    int32_t erosion_iterations;   /* 2  (bkp:31); 0..8 */
+    int32_t tip_se;               /* 15 (bkp:397); odd, 3..63; read only when tip_aware */
+    int32_t tip_aware;            /* 0 as written, 1 intent; else LG_ERR_INVALID */
+    float   w_tip;                /* 0.1 (bkp:102) */
+} lg_collect_params;
+void lg_default_collect_params(lg_collect_params* p);
+int lg_collect_params_check(const lg_params* p, const lg_collect_params* cp);
+int lg_erode_ellipse(lg_handle h, const uint8_t* mask, int B, int H, int W, int k, int iterations, uint8_t* out, void* stream);
+int lg_erode_words_host(const uint64_t* bits, int H, int W, int WW, int k, int iterations, uint64_t* out);
+int lg_tip_penalty(lg_handle h, const uint8_t* safe, int B, int H, int W, const lg_params* p, const lg_collect_params* cp, float* out,
+                   uint8_t* out_tip_area, void* stream);
+int lg_tip_fix_host(int H, int W, int32_t chamfer_init_dist0, uint32_t* out, uint32_t* max_fix);
+int lg_argmax_first(lg_handle h, const float* plane, int B, int H, int W, int32_t* xy_host, float* max_host,
+                    int32_t* any_positive_host, void* stream);
+int lg_select_grasp_collect(lg_handle h, const float* depth, const uint8_t* mask, int B, int H, int W, const lg_params* p,
+                            const lg_collect_params* cp, float* const out_maps[LG_NUM_MAPS], float* out_tip, uint8_t* out_safe,
+                            uint8_t* out_valid, lg_grasp_result* results, void* stream);
 
 /* The node's result message of every frame (leaf_grasp_node_v3.py:170-176: "x,y,X,Y,Z[,pX,pY,pZ]", each number as Python's
    str() prints it -- the shortest decimal string of the float32 value as a double), '\n'-terminated, one line per frame in

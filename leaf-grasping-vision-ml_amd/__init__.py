@@ -8,6 +8,7 @@ and constructing a selector without a HIP device raises RuntimeError.
 from ._lib import LIB_PATH, MAP_NAMES, LgError, lib  # noqa: F401  (loads the library, fails loudly)
 from ._lib import LgParams as ScoreParams  # every constant of the path; defaults = the reference values
 from ._lib import default_params  # noqa: F401
+from .collecting_selector import CollectingGraspPointSelector
 from .confidence_manager import ConfidenceManager
 from .data_collector import EnhancedGraspDataCollector
 from .grasp_point_selector import GRASP_CANDIDATE_DTYPE, ML_SAMPLE_DTYPE, GraspPointSelector, clahe
@@ -19,4 +20,4 @@ from .node_harness import LeafGraspHarness
 
 __all__ = ["GraspPointSelector", "ImageProcessor", "HybridSelector", "ConfidenceManager", "ScoreParams",
            "default_params", "MAP_NAMES", "LIB_PATH", "LgError", "OptimalLeafSelector", "HybridGraspSelector",
-           "LeafGraspHarness", "EnhancedGraspDataCollector", "clahe", "GRASP_CANDIDATE_DTYPE", "ML_SAMPLE_DTYPE"]
+           "LeafGraspHarness", "EnhancedGraspDataCollector", "CollectingGraspPointSelector", "clahe", "GRASP_CANDIDATE_DTYPE", "ML_SAMPLE_DTYPE"]

@@ -64,6 +64,12 @@ class LgMlSample(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("scored", C.c_int32), ("logit", C.c_float), ("ml_score", C.c_float)]
 
 
+class LgCollectParams(C.Structure):
+    """lg_collect_params: the constants of the collecting selector (lg_select_grasp_collect)."""
+    _fields_ = [("erosion_kernel_size", C.c_int32), ("erosion_iterations", C.c_int32), ("tip_se", C.c_int32),
+                ("tip_aware", C.c_int32), ("w_tip", C.c_float)]
+
+
 class LgTrainHparams(C.Structure):
     """lg_train_hparams; defaults = scripts/train_model.py:221-222,256."""
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
@@ -122,6 +128,16 @@ SYMBOLS = {
     "lg_ml_sample_points_host": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(LgMlSampling), _VP, _VP, C.c_int,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "lg_debug_ml_planes": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int32)]),
+    "lg_default_collect_params": (None, [C.POINTER(LgCollectParams)]),
+    "lg_collect_params_check": (C.c_int, [C.POINTER(LgParams), C.POINTER(LgCollectParams)]),
+    "lg_erode_ellipse": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP]),
+    "lg_erode_words_host": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
+    "lg_tip_penalty": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(LgParams), C.POINTER(LgCollectParams), _VP, _VP,
+                                 _VP]),
+    "lg_tip_fix_host": (C.c_int, [C.c_int, C.c_int, C.c_int32, _VP, C.POINTER(C.c_uint32)]),
+    "lg_argmax_first": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _FP, C.POINTER(C.c_int32), _VP]),
+    "lg_select_grasp_collect": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(LgParams), C.POINTER(LgCollectParams),
+                                          C.POINTER(_VP * LG_NUM_MAPS), _VP, _VP, _VP, C.POINTER(LgGraspResult), _VP]),
     "lg_rank_grasp_candidates": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
     "lg_ml_combined_score": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double)]),

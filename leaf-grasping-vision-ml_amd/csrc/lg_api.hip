@@ -104,6 +104,7 @@ int lg_destroy(lg_handle h) {
     lg_cnn_free(&h->cnn);
     if (h->eval_ws) hipFree(h->eval_ws);
     ml_free(h);
+    col_free(h);
     if (h->ev_ml) hipEventDestroy(h->ev_ml);
     lg_leaf_free(h->leaf);
     lg_leaf_prof_free(h->leaf_prof);
@@ -483,6 +484,54 @@ int lg_dilate_words_host(const uint64_t* bits, int H, int W, int WW, int k, uint
         }
     for (int y = 0; y < H; y++)
         for (int w = 0; w < WW; w++) out[(size_t)y * WW + w] = lg_frame_dilate_word(src.data(), H, W, WW, y, w, se, sp);
+    return LG_OK;
+}
+
+void lg_default_collect_params(lg_collect_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->erosion_kernel_size = 21; p->erosion_iterations = 2;   // grasp_point_selector_bkp.py:30-31
+    p->tip_se = 15;                                           // :397
+    p->tip_aware = 0;
+    p->w_tip = 0.1f;                                          // :102
+}
+
+// cv2.erode(bits, ellipse k, iterations) on the host, the device's per-word code (lg_collect.h): complemented rows, one dilation
+// per iteration on the words of the mask's bounding box, complemented back
+int lg_erode_words_host(const uint64_t* bits, int H, int W, int WW, int k, int iterations, uint64_t* out) {
+    if (!bits || !out || H < 1 || W < 1 || WW != (W + 63) / 64) return LG_ERR_INVALID;
+    if (k < 1 || k > 63 || !(k & 1) || iterations < 0 || iterations > 8) return LG_ERR_UNSUPPORTED;
+    LgSeSpans se;
+    lg_make_se_spans(k, &se);
+    LgStemPlan sp;
+    lg_make_stem_plan(se, &sp);
+    std::vector<unsigned long long> a((size_t)H * WW), b((size_t)H * WW);
+    int bx0 = W, bx1 = -1, by0 = H, by1 = -1;
+    for (int y = 0; y < H; y++)
+        for (int w = 0; w < WW; w++) {
+            const unsigned long long fm = lg_frame_word_mask(W, WW, w), v = (unsigned long long)bits[(size_t)y * WW + w] & fm;
+            a[(size_t)y * WW + w] = ~v & fm;
+            if (!v) continue;
+            bx0 = std::min(bx0, 64 * w + __builtin_ctzll(v));
+            bx1 = std::max(bx1, 64 * w + 63 - __builtin_clzll(v));
+            by0 = std::min(by0, y);
+            by1 = y;
+        }
+    for (int i = 0; i < iterations; i++) {
+        for (int y = 0; y < H; y++)
+            for (int w = 0; w < WW; w++) b[(size_t)y * WW + w] = lg_erode_step_word(a.data(), H, W, WW, y, w, bx0, bx1, by0, by1, se, sp);
+        a.swap(b);
+    }
+    for (int y = 0; y < H; y++)
+        for (int w = 0; w < WW; w++) out[(size_t)y * WW + w] = ~a[(size_t)y * WW + w] & lg_frame_word_mask(W, WW, w);
+    return LG_OK;
+}
+
+int lg_tip_fix_host(int H, int W, int32_t chamfer_init_dist0, uint32_t* out, uint32_t* max_fix) {
+    if (!out || H < 1 || W < 1 || W > 8192 || H > 16384 || chamfer_init_dist0 < (int32_t)LG_INIT0) return LG_ERR_INVALID;
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) out[(size_t)y * W + x] = lg_tip_fix(x, y, H, W, (uint32_t)chamfer_init_dist0);
+    if (max_fix) *max_fix = lg_tip_fix_max(H, W, (uint32_t)chamfer_init_dist0);
     return LG_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "lg_cnn.h"
+#include "lg_collect.h"
 #include "lg_internal.h"
 #include "lg_leaf.h"
 #include "lg_midrib.h"
@@ -128,6 +129,7 @@ struct lg_ctx {
     hipEvent_t ev_ml = nullptr;           // behind the table kernels and the copy of the counts
     int ml_planes = 0;                    // lg_debug_ml_planes: 0 by rule, 1 deferred, 2 stored
     int ml_last_form = 0;
+    LgColWs col;                          // lg_select_grasp_collect, lg_erode_ellipse, lg_argmax_first (lg_collect.h), grown on demand
 };
 
 namespace {   // (every translation unit takes its own copy, as when all of this lived in one file: nothing here is exported)
@@ -237,3 +239,4 @@ inline void gaussian1d(int size, float* k1) {
 LG_LOCAL int ensure_ws(lg_ctx* h, int B, int H, int W, int K);
 LG_LOCAL void free_ws(lg_ctx* h);
 LG_LOCAL void ml_free(lg_ctx* h);
+LG_LOCAL void col_free(lg_ctx* h);

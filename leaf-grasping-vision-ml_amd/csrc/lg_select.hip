@@ -145,7 +145,50 @@ void ml_free(lg_ctx* h) {
     h->ml_patches_cap = 0; h->ml_rows_cap = 0; h->ml_chunk_cap = 0;
 }
 
+void col_free(lg_ctx* h) {   // the collecting entries' workspace (lg_collect.h)
+    LgColWs& c = h->col;
+    free_dev(c.comp[0]); free_dev(c.comp[1]); free_dev(c.safe);
+    for (float*& p : c.planes) free_dev(p);
+    free_dev(c.sums); free_dev(c.red.key); free_dev(c.red.any);
+    free_dev(c.pick.n); free_dev(c.pick.xy); free_dev(c.pick.info); free_dev(c.pick.meta);
+    free_pinned(c.key_host); free_pinned(c.any_host);
+    c.cap_words = 0; c.cap_px = 0; c.cap_B = 0;
+}
+
 namespace {
+
+// Room for B frames of H x W: the buffers are indexed by the call's own shape, so one capacity per kind is enough.  The float
+// planes come on first use (col_plane): a caller who takes every plane back needs none.
+int col_ensure(lg_ctx* h, int B, int H, int W) {
+    LgColWs& c = h->col;
+    const size_t words = (size_t)B * H * ((W + 63) / 64), px = (size_t)B * H * W;
+    if (words <= c.cap_words && px <= c.cap_px && B <= c.cap_B) return LG_OK;
+    const size_t nw = std::max(words, c.cap_words), np = std::max(px, c.cap_px);
+    const int nB = std::max(B, c.cap_B);
+    hipDeviceSynchronize();
+    col_free(h);
+    LG_HIP(h, dev_alloc(&c.comp[0], nw));
+    LG_HIP(h, dev_alloc(&c.comp[1], nw));
+    LG_HIP(h, dev_alloc(&c.safe, np));
+    LG_HIP(h, dev_alloc(&c.sums, (size_t)nB * LG_COL_SUMS));
+    LG_HIP(h, dev_alloc(&c.red.key, (size_t)nB));
+    LG_HIP(h, dev_alloc(&c.red.any, (size_t)nB));
+    LG_HIP(h, dev_alloc(&c.pick.n, (size_t)nB));
+    LG_HIP(h, dev_alloc(&c.pick.xy, (size_t)nB * 2));
+    LG_HIP(h, dev_alloc(&c.pick.info, (size_t)nB * 2));
+    LG_HIP(h, dev_alloc(&c.pick.meta, (size_t)nB * 2));
+    LG_HIP(h, hipHostMalloc((void**)&c.key_host, sizeof(unsigned long long) * nB));
+    LG_HIP(h, hipHostMalloc((void**)&c.any_host, sizeof(int32_t) * nB));
+    c.cap_words = nw; c.cap_px = np; c.cap_B = nB;
+    return LG_OK;
+}
+
+int col_plane(lg_ctx* h, int i, float** out) {
+    LgColWs& c = h->col;
+    if (!c.planes[i]) LG_HIP(h, dev_alloc(&c.planes[i], c.cap_px));
+    *out = c.planes[i];
+    return LG_OK;
+}
 
 int ml_ensure(lg_ctx* h, int B, int H, int M, int chunk, bool want_rows) {
     const size_t BM = (size_t)B * M, BH = (size_t)B * H;
@@ -954,6 +997,106 @@ int lg_select_grasp_ml_impl(lg_handle h, const float* depth, const uint8_t* mask
     return LG_OK;
 }
 
+// ============================================================================ the collecting selector (lg_collect.h)
+// why the two parameter structs are refused (null: they are not), and with which status
+const char* collect_params_error(const lg_params* p, const lg_collect_params* cp, int* code) {
+    lg_collect_params d;
+    if (!cp) { lg_default_collect_params(&d); cp = &d; }
+    *code = LG_ERR_INVALID;
+    if (p && p->label_aware != 0) return "label_aware must be 0 (the collecting selector takes one mask, no label image)";
+    if (cp->tip_aware != 0 && cp->tip_aware != 1) return "tip_aware must be 0 or 1";
+    *code = LG_ERR_UNSUPPORTED;
+    if (cp->erosion_kernel_size < 1 || cp->erosion_kernel_size > 63 || !(cp->erosion_kernel_size & 1))
+        return "erosion_kernel_size must be odd and in [1,63]";
+    if (cp->erosion_iterations < 0 || cp->erosion_iterations > 8) return "erosion_iterations must be in [0,8]";
+    if (cp->tip_aware == 1) {
+        if (cp->tip_se < 3 || cp->tip_se > 63 || !(cp->tip_se & 1)) return "tip_se must be odd and in [3,63]";
+        return "tip_aware = 1 is not built (the tip penalty as written, tip_aware = 0, is)";
+    }
+    *code = LG_OK;
+    return nullptr;
+}
+
+// safe = erode(mask, ellipse k, iterations) as 0 / 1 bytes, from the mask's bit rows (h->bits) and bounding boxes (h->win); sums:
+// the original mask's centroid numerators into the workspace as well
+void enq_erode(lg_ctx* h, int B, int H, int W, int WW, int k, int iterations, uint8_t* safe, bool sums, hipStream_t s) {
+    LgColWs& c = h->col;
+    ProfScope ps(h, "col_erode", s);
+    if (sums) hipMemsetAsync(c.sums, 0, sizeof(unsigned long long) * LG_COL_SUMS * B, s);
+    lg_launch_col_complement(h->bits, c.comp[0], sums ? c.sums : nullptr, B, H, W, WW, s);
+    for (int i = 0; i < iterations; i++) lg_launch_col_erode_step(c.comp[i & 1], c.comp[(i + 1) & 1], h->win, B, H, W, WW, k, s);
+    lg_launch_col_unpack(c.comp[iterations & 1], safe, B, H, W, WW, s);
+}
+
+// Two passes of the front: flatness alone on the original mask (a whole-frame plane, bkp:88-89), everything else on `safe`, whose
+// bit rows, bounding boxes and angles the handle then holds for the tail.  The erosion runs behind the first pass's bit rows.
+int lg_select_grasp_collect_impl(lg_handle h, const float* depth, const uint8_t* mask, int B, int H, int W, const lg_params* pin,
+                                 const lg_collect_params* cpin, float* const out_maps[LG_NUM_MAPS], float* out_tip, uint8_t* out_safe,
+                                 uint8_t* out_valid, lg_grasp_result* results, void* stream_) {
+    if (!results) return fail(h, LG_ERR_INVALID, "lg_select_grasp_collect: results is null");
+    lg_collect_params CP;
+    if (cpin) CP = *cpin; else lg_default_collect_params(&CP);
+    Plan po;   // the original mask: flatness
+    int rc = make_plan(h, po, depth, mask, B, H, W, pin, nullptr, nullptr);
+    if (rc) return rc;
+    if (const char* why = collect_params_error(&po.P, &CP, &rc)) return fail(h, rc, (std::string("lg_select_grasp_collect: ") + why).c_str());
+    hipStream_t s = (hipStream_t)stream_;
+    LG_HIP(h, hipSetDevice(h->device));
+    if ((rc = ensure_ws(h, B, H, W, 20))) return rc;
+    if ((rc = col_ensure(h, B, H, W))) return rc;
+    reset_last(h);
+    LgColWs& c = h->col;
+    float* planes[LG_NUM_MAPS + 1];   // the caller's, or the workspace's for those the fusion reads; [8]: tip
+    for (int i = 0; i <= LG_NUM_MAPS; i++) {
+        planes[i] = i < LG_NUM_MAPS ? (out_maps ? out_maps[i] : nullptr) : out_tip;
+        if (!planes[i] && i != LG_MAP_ISOLATION && i != LG_MAP_ACCESS && (rc = col_plane(h, i, &planes[i]))) return rc;
+    }
+    uint8_t* safe = out_safe ? out_safe : c.safe;
+    po.maps[LG_MAP_FLATNESS] = planes[LG_MAP_FLATNESS];
+    if ((rc = take_planes(h, po, false))) return rc;
+    LgFinalArgs fargs;
+    rc = enq_front(h, po, s, &fargs, nullptr, [&]() -> int {
+        enq_erode(h, B, H, W, po.WW, CP.erosion_kernel_size, CP.erosion_iterations, safe, true, s);
+        return LG_OK;
+    });
+    if (rc) return rc;
+    Plan ps;   // the eroded mask: every other plane, the angle, the bit rows of the pre-grasp probes
+    if ((rc = make_plan(h, ps, depth, safe, B, H, W, pin, nullptr, out_valid))) return rc;
+    for (int i = 0; i < LG_NUM_MAPS; i++) ps.maps[i] = i == LG_MAP_FLATNESS ? nullptr : planes[i];
+    if (!ps.valid) ps.valid = h->ws_valid;
+    if ((rc = enq_front(h, ps, s, &fargs, nullptr, nothing_after_prep))) return rc;
+    {
+        ProfScope pf(h, "col_tip", s);
+        lg_launch_col_tip(safe, planes[LG_NUM_MAPS], B, H, W, (uint32_t)ps.P.chamfer_init_dist0, s);
+    }
+    LG_HIP(h, hipMemsetAsync(c.red.key, 0, sizeof(unsigned long long) * B, s));
+    LG_HIP(h, hipMemsetAsync(c.red.any, 0, sizeof(int32_t) * B, s));
+    {
+        LgFuseArgs a;
+        memset(&a, 0, sizeof(a));
+        a.approach = planes[LG_MAP_APPROACH]; a.sdf = planes[LG_MAP_SDF]; a.flat = planes[LG_MAP_FLATNESS];
+        a.stem = planes[LG_MAP_STEM]; a.dist = planes[LG_MAP_DISTANCE]; a.tip = planes[LG_NUM_MAPS];
+        a.safe = safe; a.win = h->win; a.trad = planes[LG_MAP_TRADITIONAL]; a.valid = ps.valid; a.red = c.red;
+        a.B = B; a.H = H; a.W = W;
+        a.w_approach = ps.P.w_approach; a.w_sdf = ps.P.w_sdf; a.w_flat = ps.P.w_flat; a.w_tip = CP.w_tip;
+        a.min_edge_distance = ps.P.min_edge_distance;
+        ProfScope pf(h, "col_fuse", s);
+        lg_launch_col_fuse(a, s);
+    }
+    {
+        ProfScope pf(h, "col_pick", s);
+        lg_launch_col_pick(c.red, c.sums, depth, c.pick, B, H, W, s);
+    }
+    LgFinishArgs fa = finish_args(h, ps, 1, false);   // the one-point list: nothing to rescore
+    fa.cand_n = c.pick.n; fa.cand_xy = c.pick.xy; fa.cand_info = c.pick.info; fa.slot_frames = B;
+    {
+        ProfScope pf(h, "finish", s);
+        lg_launch_finish(fa, s);
+    }
+    lg_launch_col_rows(c.pick, fa.out, B, s);
+    return return_results(h, ps, results, false, "lg_select_grasp_collect", s);
+}
+
 }  // namespace
 
 // ============================================================================ the entries
@@ -1034,6 +1177,100 @@ int lg_select_grasp_ml_labels(lg_handle h, const float* depth, const int16_t* la
     const int rc = labels_stage(h, labels, leaf_ids, B, H, W, stream_);
     if (rc) return rc;
     return lg_select_grasp_ml_impl(h, depth, h->mask_ws, labels, B, H, W, pin, sampling, results, samples, n_samples, stream_);
+}
+
+// ---- the collecting selector and its stages on their own
+int lg_collect_params_check(const lg_params* p, const lg_collect_params* cp) {
+    int code = LG_OK;
+    collect_params_error(p, cp, &code);
+    return code;
+}
+
+int lg_select_grasp_collect(lg_handle h, const float* depth, const uint8_t* mask, int B, int H, int W, const lg_params* pin,
+                            const lg_collect_params* cp, float* const out_maps[LG_NUM_MAPS], float* out_tip, uint8_t* out_safe,
+                            uint8_t* out_valid, lg_grasp_result* results, void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    return lg_select_grasp_collect_impl(h, depth, mask, B, H, W, pin, cp, out_maps, out_tip, out_safe, out_valid, results, stream_);
+}
+
+int lg_erode_ellipse(lg_handle h, const uint8_t* mask, int B, int H, int W, int k, int iterations, uint8_t* out, void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (!mask || !out || B < 1 || H < 1 || W < 1 || W > 8192 || H > 16384)
+        return fail(h, LG_ERR_INVALID, "lg_erode_ellipse: bad pointer or shape (W <= 8192, H <= 16384)");
+    lg_collect_params cp;
+    lg_default_collect_params(&cp);
+    cp.erosion_kernel_size = k; cp.erosion_iterations = iterations;
+    int rc = LG_OK;
+    if (const char* why = collect_params_error(nullptr, &cp, &rc)) return fail(h, rc, (std::string("lg_erode_ellipse: ") + why).c_str());
+    hipStream_t s = (hipStream_t)stream_;
+    LG_HIP(h, hipSetDevice(h->device));
+    if ((rc = ensure_ws(h, B, H, W, 20))) return rc;
+    if ((rc = col_ensure(h, B, H, W))) return rc;
+    reset_last(h);
+    const int WW = (W + 63) / 64;
+    LG_HIP(h, hipMemsetAsync(h->maxfix, 0, sizeof(uint32_t) * LG_MF * B, s));   // (the bounding boxes accumulate from zero)
+    lg_launch_pack_bits(mask, h->bits, B, H, W, WW, s, h->maxfix);
+    lg_launch_window(h->maxfix, h->win, B, H, W, 0, s);
+    enq_erode(h, B, H, W, WW, k, iterations, out, false, s);
+    LG_HIP(h, hipGetLastError());
+    return LG_OK;
+}
+
+int lg_tip_penalty(lg_handle h, const uint8_t* safe, int B, int H, int W, const lg_params* pin, const lg_collect_params* cp,
+                   float* out, uint8_t* out_tip_area, void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (!safe || !out || B < 1 || H < 1 || W < 1 || W > 8192 || H > 16384)
+        return fail(h, LG_ERR_INVALID, "lg_tip_penalty: bad pointer or shape (W <= 8192, H <= 16384)");
+    lg_params P;
+    if (pin) P = *pin; else lg_default_params(&P);
+    if (P.chamfer_init_dist0 < (int32_t)LG_INIT0)
+        return fail(h, LG_ERR_INVALID, "lg_tip_penalty: chamfer_init_dist0 must be in [INT_MAX >> 2, INT_MAX]");
+    int rc = LG_OK;
+    if (const char* why = collect_params_error(&P, cp, &rc)) return fail(h, rc, (std::string("lg_tip_penalty: ") + why).c_str());
+    hipStream_t s = (hipStream_t)stream_;
+    LG_HIP(h, hipSetDevice(h->device));
+    {
+        ProfScope ps(h, "col_tip", s);
+        lg_launch_col_tip(safe, out, B, H, W, (uint32_t)P.chamfer_init_dist0, s);
+    }
+    if (out_tip_area) LG_HIP(h, hipMemsetAsync(out_tip_area, 0, (size_t)B * H * W, s));   // (no tip area as written)
+    LG_HIP(h, hipGetLastError());
+    return LG_OK;
+}
+
+int lg_argmax_first(lg_handle h, const float* plane, int B, int H, int W, int32_t* xy_host, float* max_host,
+                    int32_t* any_positive_host, void* stream_) {
+    if (!h) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (!plane || B < 1 || H < 1 || W < 1 || (unsigned long long)H * W > 0xFFFFFFFFull)
+        return fail(h, LG_ERR_INVALID, "lg_argmax_first: bad pointer or shape (H * W below 2^32)");
+    hipStream_t s = (hipStream_t)stream_;
+    LG_HIP(h, hipSetDevice(h->device));
+    int rc = col_ensure(h, B, 1, 1);
+    if (rc) return rc;
+    LgColWs& c = h->col;
+    LG_HIP(h, hipMemsetAsync(c.red.key, 0, sizeof(unsigned long long) * B, s));
+    LG_HIP(h, hipMemsetAsync(c.red.any, 0, sizeof(int32_t) * B, s));
+    {
+        ProfScope ps(h, "col_argmax", s);
+        lg_launch_col_argmax(plane, c.red, B, H, W, s);
+    }
+    LG_HIP(h, hipMemcpyAsync(c.key_host, c.red.key, sizeof(unsigned long long) * B, hipMemcpyDeviceToHost, s));
+    LG_HIP(h, hipMemcpyAsync(c.any_host, c.red.any, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+    LG_HIP(h, hipStreamSynchronize(s));
+    LG_HIP(h, hipGetLastError());
+    for (int b = 0; b < B; b++) {
+        float v;
+        uint32_t idx;
+        lg_argmax_unkey(c.key_host[b], &v, &idx);
+        if (xy_host) { xy_host[2 * b] = (int32_t)(idx % (uint32_t)W); xy_host[2 * b + 1] = (int32_t)(idx / (uint32_t)W); }
+        if (max_host) max_host[b] = v;
+        if (any_positive_host) any_positive_host[b] = c.any_host[b] ? 1 : 0;
+    }
+    return LG_OK;
 }
 
 }  // extern "C"
