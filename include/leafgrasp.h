@@ -578,6 +578,23 @@ int lg_border_line_max(const int32_t* prof, int n, int lo, int len, uint32_t* ou
    LG_ERR_INVALID when that call did not take the near launch (planes or validity taken back, LG_FINAL_NEAR=0, LG_SUBBATCH,
    LG_NO_SKIP, LG_FINAL_PERSIST / LG_FINAL_TPW, each as the handle found it at lg_create) or cap is too small.  Launches nothing. */
 int lg_debug_near_tiles(lg_handle h, int32_t* off, int cap);
+/* Tail lanes of lg_select_grasp* ("Tail in lanes"): behind the front, which runs once, the batch is cut into
+   lanes of consecutive frames, and every lane runs planes -> top-k -> survivors -> gather -> CNN as a chain on a stream of its
+   own, beside the other lanes'.  Results do not depend on the lanes: every row equals the one-lane call's bit for bit.
+   lg_tail_lane_plan (host only: no device, no handle) is the rule: B frames, requested = 0 (automatic: LG_TAIL_LANES_AUTO lanes
+   from LG_TAIL_LANES_MIN_B frames on, else one) or 1 .. 4 (that many), eligible = the call may run in lanes at all (sparse call
+   with the near launch, model loaded, pruned CNN pass, not label-aware, not the candidates entry; 0: one lane).  *sb = frames per
+   lane, ceil(B / min(requested lanes, B)); *lanes = ceil(B / *sb), so no lane is empty and only the last may be shorter.
+   LG_ERR_INVALID for B < 1, requested outside [0, 4] or a null pointer.
+   A call under the automatic rule runs in one lane as well while another handle of the process is inside an lg_select_grasp*
+   call (the other batch fills the chip already: two batches in flight measured 5-10 % slower with lanes), and where its
+   B * top_k patch slots exceed one slice of the CNN pass (8192): lanes would then hold a slice's worth of activation workspace
+   each.  A forced setting ignores both.
+   lg_debug_tail_lanes: set = 0 .. 4 stores the request for the handle's later calls, set < 0 only reports; *last (may be null) =
+   lanes of the last lg_select_grasp* call on this handle (1 for a call that did not run in lanes; 0 before any, and behind an entry of another family).  Lanes show as
+   sub-batches in lg_debug_cnn_survivors.  LG_ERR_INVALID for set > 4. */
+int lg_tail_lane_plan(int B, int requested, int eligible, int32_t* lanes, int32_t* sb);
+int lg_debug_tail_lanes(lg_handle h, int set, int32_t* last);
 /* The experiment switches as text, one "NAME=value\n" line per switch ("Experiment switches", has the rows).
    lg_options_text (host only: no device, no handle): the environment as it is now, through the parser of `which` -- 0 a
    handle's switches (lg_create), 1 a model's (lg_cnn_load*), 2 a trainer's (lg_train_create).  lg_debug_options: the values the

@@ -172,6 +172,8 @@ SYMBOLS = {
     "lg_window_from_box": (C.c_int, [C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "lg_border_line_max": (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "lg_debug_near_tiles":(C.c_int, [_VP, C.POINTER(C.c_int32), C.c_int]),
+    "lg_tail_lane_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "lg_debug_tail_lanes": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int32)]),
     "lg_debug_cnn_scored": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "lg_debug_leaf_fallback": (C.c_int, [_VP, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lg_debug_cnn_survivors": (C.c_int, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,

@@ -72,8 +72,15 @@ void lg_cnn_free(LgCnn* c);   // weights and workspace
 // allow_split = false: no item of lg_wino4_kernel is split along the input channels, so a patch's logit does not depend on the
 // number of patches of the call.  n_dev (device; needs haloed_in and lg_cnn_counts_on_device): the call runs on the first *n_dev
 // of the N patch slots only -- N bounds the workspace, the grids and the slices; the logits of the other slots are not written.
+// act_off: the first patch slot of the activation buffers this run takes (it uses [act_off, act_off + min(N, slice)) of every
+// layer's).  Runs in flight at the same time on different streams must take ranges that do not meet, and lg_cnn_reserve must have
+// made room for all of them before the first is queued: a run that had to grow the buffers would free what the others read.
 int lg_cnn_run(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err,
-               bool allow_split = true, const int* n_dev = nullptr);
+               bool allow_split = true, const int* n_dev = nullptr, int act_off = 0);
+// Patch slots one run of N patches takes in the activation buffers (a slice's), and room for `slots` of them: grows the buffers
+// behind a synchronise of s when they hold fewer, as the first run on a larger batch does by itself.
+int lg_cnn_act_slots(int N);
+int lg_cnn_reserve(LgCnn* c, int slots, hipStream_t s, std::string* err);
 bool lg_cnn_counts_on_device(const LgCnn* c);
 size_t lg_cnn_halo_patch_floats(void);
 // after a synchronisation of the stream a forward ran on: true (once) if a split item of it gave up waiting for its parts

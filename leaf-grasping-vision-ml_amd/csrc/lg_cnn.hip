@@ -1418,7 +1418,7 @@ static int ensure_act(LgCnn* c, int N, hipStream_t s, std::string* err) {
 }
 
 static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err,
-                            bool allow_split, const int* n_dev, int n_off);
+                            bool allow_split, const int* n_dev, int n_off, int act_off);
 
 // every layer on lg_wino4_kernel: the kernels that can take their patch count from device memory
 bool lg_cnn_counts_on_device(const LgCnn* c) {
@@ -1426,24 +1426,35 @@ bool lg_cnn_counts_on_device(const LgCnn* c) {
 }
 
 // Slices bound the activation workspace (0.8 MB per patch for the standard model): at most 8192 patches at a time.
+constexpr int LG_CNN_MAX_SLICE = 8192;
+int lg_cnn_act_slots(int N) { return N < LG_CNN_MAX_SLICE ? N : LG_CNN_MAX_SLICE; }
+int lg_cnn_reserve(LgCnn* c, int slots, hipStream_t s, std::string* err) {
+    if (!c->loaded) { *err = "no model"; return LG_ERR_NO_MODEL; }
+    return ensure_act(c, slots, s, err);
+}
+
 int lg_cnn_run(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err,
-               bool allow_split, const int* n_dev) {
+               bool allow_split, const int* n_dev, int act_off) {
     if (!c->loaded) { *err = "no model"; return LG_ERR_NO_MODEL; }
     if (n_dev && !(haloed_in && lg_cnn_counts_on_device(c))) { *err = "lg_cnn_run: no device-side patch count on this path"; return LG_ERR_UNSUPPORTED; }
-    const int max_slice = 8192;
+    if (act_off && !haloed_in) { *err = "lg_cnn_run: an activation offset needs haloed patches"; return LG_ERR_UNSUPPORTED; }   // (in_halo has no ranges)
+    const int max_slice = LG_CNN_MAX_SLICE;
     const size_t pstride = haloed_in ? lg_cnn_halo_patch_floats() : (size_t)9 * 1024;
     for (int off = 0; off < N; off += max_slice) {
         const int n = N - off < max_slice ? N - off : max_slice;
-        int rc = lg_cnn_run_slice(c, patches + (size_t)off * pstride, haloed_in, n, logits + off, s, err, allow_split, n_dev, off);
+        int rc = lg_cnn_run_slice(c, patches + (size_t)off * pstride, haloed_in, n, logits + off, s, err, allow_split, n_dev, off, act_off);
         if (rc) return rc;
     }
     return LG_OK;
 }
 
 static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int N, float* logits, hipStream_t s, std::string* err,
-                            bool allow_split, const int* n_dev, int n_off) {
-    int rc = ensure_act(c, N, s, err);
+                            bool allow_split, const int* n_dev, int n_off, int act_off) {
+    // (behind lg_cnn_reserve this finds the room it needs: it must not grow the buffers while another stream's run reads them)
+    int rc = ensure_act(c, act_off + N, s, err);
     if (rc) return rc;
+    float* act[8];   // this run's range of every layer's buffer
+    for (int L = 0; L < c->n_layers; L++) act[L] = c->act[L] + (size_t)act_off * c->act_per[L];
     const float* x = patches;
     if (!haloed_in) {   // the C-ABI's dense [N][9][32][32] patches -> haloed planes
         hipLaunchKernelGGL(lg_repack_kernel, dim3((unsigned)(N * 9)), dim3(256), 0, s, patches, c->in_halo, (long long)N * 9);
@@ -1451,20 +1462,20 @@ static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int 
     }
     // layer 0: the F(4x4,3x3) kernel on 12 input planes (3 chunks); the direct 9-channel kernel with LG_CNN_DIRECT / _F23 / mask bit 0 clear
     if (!c->use_f23 && (c->wino_mask & 1) &&
-        launch_wino4_rt(12, c->layers[0].coutp, 32, false, true, x, c->uwino4[0], c->bconv[0], c->act[0], N, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off)) {
+        launch_wino4_rt(12, c->layers[0].coutp, 32, false, true, x, c->uwino4[0], c->bconv[0], act[0], N, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off)) {
         // (a shape the F(4x4) table lacks falls through to the direct kernel instead of leaving act[0] unwritten)
-    } else if (c->layers[0].coutp == 64) launch_conv0<64>(x, c, c->act[0], N, s);
-    else launch_conv0<128>(x, c, c->act[0], N, s);
-    const float* cur = c->act[0];
+    } else if (c->layers[0].coutp == 64) launch_conv0<64>(x, c, act[0], N, s);
+    else launch_conv0<128>(x, c, act[0], N, s);
+    const float* cur = act[0];
     if (c->standard) {
         const int wmask = c->wino_mask;
 #define LG_LAYER(L, KC, PP, CP)                                                                                     \
     do {                                                                                                            \
         const RtLayer& l = c->layers[L];                                                                            \
-        if (!(wmask & (1 << L))) launch_conv<L, KC, PP, CP>(cur, c, c->act[L], N, s);                               \
-        else if (c->use_f23) launch_wino_rt(l.cinp, l.coutp, l.wi, l.pool, L != 5, cur, c->uwino[L], c->bconv[L], c->act[L], N, s); \
-        else launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L != 5, cur, c->uwino4[L], c->bconv[L], c->act[L], N, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off); \
-        cur = c->act[L];                                                                                            \
+        if (!(wmask & (1 << L))) launch_conv<L, KC, PP, CP>(cur, c, act[L], N, s);                               \
+        else if (c->use_f23) launch_wino_rt(l.cinp, l.coutp, l.wi, l.pool, L != 5, cur, c->uwino[L], c->bconv[L], act[L], N, s); \
+        else launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L != 5, cur, c->uwino4[L], c->bconv[L], act[L], N, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off); \
+        cur = act[L];                                                                                            \
     } while (0)
         LG_LAYER(1, 8, 4, 1);   // 64 -> 64, pool -> 16x16
         LG_LAYER(2, 8, 4, 1);   // 64 -> 128, 16x16
@@ -1475,13 +1486,13 @@ static int lg_cnn_run_slice(LgCnn* c, const float* patches, bool haloed_in, int 
     } else {
         for (int L = 1; L < c->n_layers; L++) {
             const RtLayer& l = c->layers[L];
-            const bool okl = c->use_f23 ? launch_wino_rt(l.cinp, l.coutp, l.wi, l.pool, L + 1 < c->n_layers, cur, c->uwino[L], c->bconv[L], c->act[L], N, s)
-                                        : launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L + 1 < c->n_layers, cur, c->uwino4[L], c->bconv[L], c->act[L], N, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off);
+            const bool okl = c->use_f23 ? launch_wino_rt(l.cinp, l.coutp, l.wi, l.pool, L + 1 < c->n_layers, cur, c->uwino[L], c->bconv[L], act[L], N, s)
+                                        : launch_wino4_rt(l.cinp, l.coutp, l.wi, l.pool, L + 1 < c->n_layers, cur, c->uwino4[L], c->bconv[L], act[L], N, c->kpart, c->kflag, c->kerr_dev, s, allow_split, n_dev, n_off);
             if (!okl) {
                 *err = "lg_cnn_forward: unsupported layer shape";
                 return LG_ERR_UNSUPPORTED;
             }
-            cur = c->act[L];
+            cur = act[L];
         }
     }
 #define LG_HEAD(F_, NP_)                                                                                              \

@@ -22,6 +22,7 @@
 struct LgProfSlot {
     std::string name;
     std::vector<hipEvent_t> ev;  // pairs
+    std::vector<uint8_t> cont;   // per pair: it continues a launch of this call that another pair counts (ProfScope, lg_ctx::prof_cont)
     size_t used = 0;
     int launches = 0;
     double total_ms = 0.0;
@@ -103,6 +104,13 @@ struct lg_ctx {
     hipEvent_t ev_orient = nullptr, ev_side = nullptr, ev_search = nullptr;
     int last_dt_algo = 0;           // lg_debug_dt_search_form: the form the row search of the last call took (0: no search was queued)
     int prof_on = 0;  // 0 off, 1 every kernel (event pairs on the stream), 2 only launches that stamp their own events
+    // true while the call queues lanes 1 .. of its tail (lg_select_grasp_impl): a scope opened now continues the launch that lane
+    // 0 counted -- prof_flush adds its milliseconds to the slot without counting a launch, so a slot reads one launch per call
+    // and the sum of its lanes' times (which overlap: the slots of a call in lanes add up to more than its wall time)
+    bool prof_cont = false;
+    // tail lanes of lg_select_grasp* (lg_debug_tail_lanes): the request -- 0: the automatic rule, 1 .. 4: that many lanes wherever
+    // lanes are allowed -- and the lanes of the last call
+    int tail_lanes_req = 0, last_tail_lanes = 0;
     std::vector<LgProfSlot> prof;
     LgPool* pool = nullptr;
     LgOptions opt;               // the experiment switches, read ONCE at lg_create (never on the per-call path): lg_options.h
@@ -187,7 +195,9 @@ struct ProfScope {  // records an event pair around a launch when profiling is o
             if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { slot = nullptr; return; }
             slot->ev.push_back(a);
             slot->ev.push_back(b);
+            slot->cont.push_back(0);
         }
+        slot->cont[slot->used / 2] = h->prof_cont ? 1 : 0;
         e0 = slot->ev[slot->used];
         if (!ext) hipEventRecord(e0, s);
         e1 = slot->ev[slot->used + 1];
@@ -204,7 +214,7 @@ inline void prof_flush(lg_ctx* h) {  // resolve recorded pairs into totals (call
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, p.ev[i], p.ev[i + 1]) == hipSuccess) {
                 p.total_ms += ms;
-                p.launches++;
+                if (!p.cont[i / 2]) p.launches++;
             }
         }
         p.used = 0;

@@ -71,7 +71,9 @@ struct LgFinalArgs {
     // near launch (sparse mode): the workgroups take the entries of the batch's list of near tiles (lg_near_tiles) instead of
     // every tile; the far tiles' keys and state bytes were written by lg_launch_near_tiles.  null: every tile
     const int32_t* near_off;   // [B + 1] DEVICE: first list entry of every frame, near_off[B] = near_total
-    int near_total;            // entries of the list (the host's copy of near_off[B])
+    int near_total;            // entries of the list this launch takes (the whole batch: the host's copy of near_off[B])
+    int near_base;             // list entry of near_off[0] (a launch over the frames [f0, f1) of a batch passes near_off + f0, B = f1 - f0,
+                               //   near_base = near_off[f0] and near_total = near_off[f1] - near_off[f0]; the whole batch: 0)
     int near_tpw;              // consecutive list entries per workgroup (>= 1)
 };
 

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) LG_FINAL_WPE_ATTR void lg_final_kernel(LgFinal
     int li = 0;
     if (near) {   // the frame of list entry li: the last one that starts at or before it (scalar binary search; frames without near tiles own no entry)
         lg_off_ptr noff = (lg_off_ptr)ap->near_off;
-        li = xcd_first + it;
+        li = ap->near_base + xcd_first + it;   // (the batch's entry: a launch over a range of frames starts at its first frame's)
         int lo = 0, hi = ap->B;   // near_off[lo] <= li < near_off[hi]
         while (hi - lo > 1) {
             const int mid = (lo + hi) >> 1;

@@ -10,13 +10,33 @@
 #include "lg_ctx.h"
 #include "lg_dt.h"
 
+// Tail lanes of lg_select_grasp* (lg_tail_lane_plan): the automatic rule -- LG_TAIL_LANES_AUTO lanes from LG_TAIL_LANES_MIN_B
+// frames on, one lane below -- and the library streams of lanes 1, 2, 3 (members of the handle `h`).
+// profiles/NOTES_tail_lanes.md has the readings behind all three (tools/tail_lanes_ab.py, 1080p, ms per step, three rounds):
+//   256 frames: 1 lane 1.886 .. 1.897, 2 lanes 1.816 .. 1.820, 3 lanes 2.225 .. 2.238, 4 lanes 2.249 .. 2.267
+//   128 frames: 1.162 .. 1.165 / 1.254 .. 1.256 / 1.572 .. 1.573 / 1.616 .. 1.623;  64: 0.937 .. 0.947 / 0.993 .. 1.004;  32: 0.742 .. 0.743 / 0.749 .. 0.753
+// Two lanes win every round at 256 frames and lose at 128 and below; three and four lose everywhere.  Lane 1 on s_dt[0]
+// instead of s_main: 1.808 .. 1.813 against 1.881 .. 1.884 ms, the same gain -- neither lands on the caller's hardware queue.
+#ifndef LG_TAIL_LANES_AUTO
+#define LG_TAIL_LANES_AUTO 2
+#endif
+#ifndef LG_TAIL_LANES_MIN_B
+#define LG_TAIL_LANES_MIN_B 256
+#endif
+#ifndef LG_TAIL_LANE_STREAMS
+#define LG_TAIL_LANE_STREAMS h->s_main, h->s_topk, h->s_dt[0]
+#endif
+
 // ============================================================================ workspaces
 namespace {
+
+std::atomic<int> g_select_in_flight{0};   // lg_select_grasp* calls of this process that are running now, on any handle (tail lanes)
 
 // the inspection fields a selection call owns (lg_debug_near_tiles, _isolation_fields, _cnn_scored, _cnn_survivors, _patch):
 // cleared when the call starts and when the workspace goes, set again by what the call does
 void reset_last(lg_ctx* h) {
     h->last_near_B = 0; h->last_iso_B = 0;
+    h->last_tail_lanes = 0;
     h->last_scored = 0; h->last_scored_subs = 0; h->last_cnn_B = 0; h->last_patch_floats = 0;
 }
 
@@ -600,10 +620,11 @@ int enq_final(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, bool upl
     a.persist = h->opt.final_persist;   // (lg_launch_final: the tile walk and the tiles per workgroup stay experiment switches)
     a.tpw = h->opt.final_tpw;
     a.nt_stores = 0;
-    if (pl.near) {   // (one sub-batch: off = 0, n = B)
+    if (pl.near) {   // (the whole batch, or one lane of its tail: the entries of the batch's list that the frames [off, off + n) own)
         LG_HIP(h, hipEventSynchronize(h->ev_near));   // near_off_host is written (the kernel ended long ago: it follows the bit-row pass)
-        a.near_off = h->near_off;
-        a.near_total = h->near_off_host[n];
+        a.near_off = h->near_off + off;
+        a.near_base = h->near_off_host[off];
+        a.near_total = h->near_off_host[off + n] - h->near_off_host[off];
         a.near_tpw = h->opt.final_near;
     }
     {
@@ -677,18 +698,32 @@ struct Timeline {
 // A whole call as one sub-batch on the caller's stream, up to its planes: bit rows -> `after_prep` (what else reads only the bit
 // rows and the bounding boxes) -> distance transform -> label-aware fields -> orientation -> plane kernel -> stored isolation
 // plane.  *fargs: the plane launch's arguments, for the deferred gather.
+// does a call with this plan take the near launch of the plane kernel?
+bool takes_near_launch(const lg_ctx* h, const Plan& pl) {
+    return pl.sparse && h->opt.final_near > 0 && h->opt.subbatch == 0 && h->opt.no_skip == 0;
+}
+
+// enq_front up to, and without, the plane kernel.  *upload_fp: as finish_orient's.
 template <typename AfterPrep>
-int enq_front(lg_ctx* h, Plan& pl, hipStream_t s, LgFinalArgs* fargs, Timeline* tl, AfterPrep&& after_prep) {
-    pl.near = pl.sparse && h->opt.final_near > 0 && h->opt.subbatch == 0 && h->opt.no_skip == 0;
+int enq_front_sweeps(lg_ctx* h, Plan& pl, hipStream_t s, Timeline* tl, AfterPrep&& after_prep, bool* upload_fp) {
+    pl.near = takes_near_launch(h, pl);
     int rc = enq_prep(h, pl, 0, pl.B, s, h->ev_prep);
     if (rc) return rc;
     if ((rc = after_prep())) return rc;
     if ((rc = enq_dt(h, pl, 0, pl.B, s))) return rc;
     if ((rc = enq_iso(h, pl, s))) return rc;
     if (tl) { tl->mark(Timeline::SWEEPS); tl->host(Timeline::ENQ1); }
-    bool upload_fp = true;
-    if ((rc = finish_orient(h, pl, 0, pl.B, &upload_fp))) return rc;   // theta per frame: device results (or host analysis) while the sweeps run
+    *upload_fp = true;
+    if ((rc = finish_orient(h, pl, 0, pl.B, upload_fp))) return rc;   // theta per frame: device results (or host analysis) while the sweeps run
     if (tl) tl->host(Timeline::ORIENT);
+    return LG_OK;
+}
+
+template <typename AfterPrep>
+int enq_front(lg_ctx* h, Plan& pl, hipStream_t s, LgFinalArgs* fargs, Timeline* tl, AfterPrep&& after_prep) {
+    bool upload_fp = true;
+    int rc = enq_front_sweeps(h, pl, s, tl, after_prep, &upload_fp);
+    if (rc) return rc;
     if ((rc = enq_final(h, pl, 0, pl.B, s, upload_fp, fargs))) return rc;
     enq_iso_plane(h, pl, *fargs, s);
     return LG_OK;
@@ -769,8 +804,46 @@ int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* mask, c
     // D(0)->F(0)->T(0) must drain before the first CNN launch, and D's latency does not shrink with SB.
     // Kept for experiments (LG_SUBBATCH=n in the environment when the handle is created); the default is one sub-batch.
     if (h->opt.subbatch > 0 && !pl.label_aware) SB = h->opt.subbatch;   // (the label-aware transforms reuse the sweeps' scratch: one sub-batch)
+    const bool piped = SB < B;
+    // ---- tail in lanes.  The other way to cut a batch, and the one that pays at 256 frames (1.82 against 1.89 ms per step; the
+    // sub-batch pipeline above is the LG_SUBBATCH experiment, this one is on by rule): the front runs ONCE for the whole batch, exactly as
+    // in a call of one sub-batch, and only what follows it -- planes, top-k, survivors, gather, CNN -- runs per lane of SB
+    // consecutive frames, each lane an in-order chain on a stream of its own (lane 0: the caller's), lane k's plane launch
+    // behind lane k - 1's.  The pipeline above splits the front too, whose latency does not shrink with the frames, and loses;
+    // here the front costs what it did and the lanes fill each other's holes: the left-over rounds of a lane's persistent CNN
+    // launches, its seven launch boundaries and its one-workgroup-per-frame top-k run beside the other lane's matrix work.
+    // Whole CNN items, a survivor list, count and slot map per lane and a range of the activation buffers per lane
+    // (lg_cnn_run's act_off) keep every logit, candidate and result row equal to the one-lane call's bit for bit.
+    // Only where the pruned CNN pass follows the near launch: a model, LG_CNN_PRUNE, not the candidates entry, not label-aware
+    // (lg_tail_lane_plan has the rule, lg_debug_tail_lanes overrides it; DESIGN.md section 4, "Tail in lanes").
+    // The automatic rule also asks that no other handle of the process is inside a selection call: lanes fill the holes of a
+    // chip this call would otherwise have to itself.  With two batches in flight on two handles (bench.py's `pipelined`) the
+    // other batch fills them already, and lanes cost 5-10 % there (1.74, 1.82 against 1.65, 1.67 ms per step before this
+    // rule).  Results never depend on the lanes, so a rule that depends on timing is safe; a forced setting ignores it.
+    struct InFlight {
+        const int others;
+        InFlight() : others(g_select_in_flight.fetch_add(1, std::memory_order_relaxed)) {}
+        ~InFlight() { g_select_in_flight.fetch_sub(1, std::memory_order_relaxed); }
+    } in_flight;
+    // And it asks that the call's B * K patch slots fit one slice of lg_cnn_run: a larger call runs its CNN in slices one behind
+    // the other in the activation workspace of ONE slice (6.5 GB for the standard model); in lanes each lane would hold a
+    // slice's worth of it.  The automatic rule never grows that workspace beyond what the one-lane call takes.
+    const bool one_slice = lg_cnn_act_slots(B * K) == B * K;
+    const int lanes_req = h->tail_lanes_req ? h->tail_lanes_req : (in_flight.others || !one_slice ? 1 : 0);
+    int32_t lanes = 1, lane_sb = B;
+    lg_tail_lane_plan(B, lanes_req, !piped && prune && !pl.label_aware && takes_near_launch(h, pl), &lanes, &lane_sb);
+    const bool laned = lanes > 1;
+    if (laned) SB = lane_sb;
     const int nsub = (B + SB - 1) / SB;
-    const bool piped = nsub > 1;
+    h->last_tail_lanes = laned ? nsub : 1;
+    // the lanes' ranges of the CNN's activation buffers: made before anything is queued (growing them synchronises and frees)
+    const int lane_slots = lg_cnn_act_slots(SB * K);
+    if (laned) {
+        std::string err;
+        const int r2 = lg_cnn_reserve(&h->cnn, (nsub - 1) * lane_slots + lg_cnn_act_slots((B - (nsub - 1) * SB) * K), s, &err);
+        if (r2) return fail(h, r2, err.c_str());
+    }
+    struct ContGuard { lg_ctx* h; ~ContGuard() { h->prof_cont = false; } } cont_guard{h};
     std::vector<LgFinalArgs> fargs((size_t)nsub);   // the plane launches' arguments, for the deferred gather
     hipStream_t sD[2] = {piped ? h->s_dt[0] : s, piped ? h->s_dt[1] : s};
     hipStream_t sM = piped ? h->s_main : s, sT = piped ? h->s_topk : s;
@@ -790,7 +863,7 @@ int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* mask, c
                        h->cand_xy + (size_t)off * K * 2, h->cand_n + off, h->cand_info + (size_t)off * K * 2, sT,
                        prune ? h->surv_keep + off : nullptr, P.mask_is_bool);
     };
-    auto enq_G = [&](int k) -> int {
+    auto enq_G = [&](int k, int act_off = 0) -> int {
         const int off = k * SB, n = std::min(SB, B - off);
         if (piped) LG_HIP(h, hipStreamWaitEvent(sM, EV(k, 4), 0));
         if (use_cnn) {
@@ -814,14 +887,35 @@ int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* mask, c
             {
                 ProfScope ps(h, "cnn", sM);
                 int r2 = lg_cnn_run(&h->cnn, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, n * K, h->logits + (size_t)off * K, sM, &err,
-                                    false, count);
+                                    false, count, act_off);
                 if (r2) return fail(h, r2, err.c_str());
             }
         }
         return LG_OK;
     };
     Timeline tl(h->opt.trace, !piped, s);
-    if (!piped) {
+    if (laned) {
+        bool upload_fp = true;
+        if ((rc = enq_front_sweeps(h, pl, s, &tl, nothing_after_prep, &upload_fp))) return rc;
+        // Lanes 1 .. on library streams that are idle by now and, through the event of the lane before, behind the front on the
+        // caller's stream.  s_main first: LG_TAIL_LANE_STREAMS has the reading.
+        const hipStream_t lane_s[4] = {s, LG_TAIL_LANE_STREAMS};
+        for (int k = 0; k < nsub; k++) {   // (EV(k, 3): lane k's planes are written; EV(k, 5): lane k has ended)
+            const int off = k * SB, n = std::min(SB, B - off);
+            sM = sT = lane_s[k];
+            h->prof_cont = k > 0;
+            if (k) LG_HIP(h, hipStreamWaitEvent(sM, EV(k - 1, 3), 0));
+            if ((rc = enq_final(h, pl, off, n, sM, upload_fp, &fargs[k]))) return rc;
+            if (k + 1 < nsub) LG_HIP(h, hipEventRecord(EV(k, 3), sM));
+            if (!k) tl.mark(Timeline::PLANES);
+            enq_T(k);
+            if (!k) tl.mark(Timeline::TOPK);
+            if ((rc = enq_G(k, k * lane_slots))) return rc;
+            if (k) LG_HIP(h, hipEventRecord(EV(k, 5), sM));
+        }
+        h->prof_cont = false;
+        for (int k = 1; k < nsub; k++) LG_HIP(h, hipStreamWaitEvent(s, EV(k, 5), 0));
+    } else if (!piped) {
         if ((rc = enq_front(h, pl, s, &fargs[0], &tl, nothing_after_prep))) return rc;
         tl.mark(Timeline::PLANES);
         enq_T(0);
@@ -853,7 +947,7 @@ int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* mask, c
             if (k >= 1) { rc = enq_G(k - 1); if (rc) return rc; }
         }
     }
-    if ((rc = enq_G(nsub - 1))) return rc;
+    if (!laned && (rc = enq_G(nsub - 1))) return rc;
     if (prune) h->last_scored_subs = nsub;
     tl.mark(Timeline::CNN);
     if (piped) {  // join: the caller's stream continues after every internal stream
@@ -1101,6 +1195,24 @@ int lg_select_grasp_collect_impl(lg_handle h, const float* depth, const uint8_t*
 
 // ============================================================================ the entries
 extern "C" {
+
+int lg_tail_lane_plan(int B, int requested, int eligible, int32_t* lanes, int32_t* sb) {
+    if (B < 1 || requested < 0 || requested > 4 || !lanes || !sb) return LG_ERR_INVALID;
+    int want = requested ? requested : (B >= LG_TAIL_LANES_MIN_B ? LG_TAIL_LANES_AUTO : 1);
+    if (!eligible) want = 1;
+    want = std::min(want, B);            // a lane never holds fewer than one frame
+    *sb = (B + want - 1) / want;
+    *lanes = (B + *sb - 1) / *sb;        // (7 frames in 4 lanes: 2 + 2 + 2 + 1; 5 in 4: 2 + 2 + 1, three lanes)
+    return LG_OK;
+}
+
+int lg_debug_tail_lanes(lg_handle h, int set, int32_t* last) {
+    if (!h || set > 4) return LG_ERR_INVALID;
+    LG_ENTER(h);
+    if (set >= 0) h->tail_lanes_req = set;
+    if (last) *last = h->last_tail_lanes;
+    return LG_OK;
+}
 
 int lg_score_maps(lg_handle h, const float* depth, const uint8_t* mask, int B, int H, int W, const lg_params* pin,
                   float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid, float* theta_host, void* stream_) {

@@ -308,6 +308,16 @@ class GraspPointSelector:
             raise RuntimeError(lib.lg_last_error(self._h).decode())
         return dict(sub_frames=int(sub_frames.value), n_sub=int(n_sub.value), counts=counts, list=lst, slot=slot, logits=logits)
 
+    def tail_lanes(self, lanes=None):
+        """Inspection and control of the tail lanes (lg_debug_tail_lanes): lanes = 0 the automatic rule, 1 .. 4 that many lanes
+        wherever a call may run in lanes, None only reports.  Returns the lanes of the last select_grasp_point(s) call on this
+        selector (1: it did not run in lanes; 0: none yet).  Results never depend on the lanes."""
+        last = C.c_int32()
+        rc = lib.lg_debug_tail_lanes(self._h, -1 if lanes is None else int(lanes), C.byref(last))
+        if rc != 0:
+            raise RuntimeError(f"lg_debug_tail_lanes({lanes}) -> {rc}")
+        return int(last.value)
+
     def patch(self, slot):
         """Inspection: [9, 32, 32] float32, the patch in slot `slot` of the last select call with a model loaded, as the CNN read
         it (lg_debug_patch; slots as in cnn_survivors()['list'])."""
