@@ -33,9 +33,10 @@ struct lg_ctx {
     std::string err;
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_prep = nullptr, ev_copy = nullptr;
-    // sub-batch pipeline of lg_select_grasp: latency-bound stages run beside the bandwidth / MFMA bound ones
+    // library streams of lg_select_grasp*: the stages of the LG_SUBBATCH pipeline (schedule_subbatches) and lanes 1 .. of the
+    // tail in lanes (schedule_lanes, LG_TAIL_LANE_STREAMS); s_dt also takes the row search and the small batches' side tail
     hipStream_t s_dt[2] = {nullptr, nullptr}, s_main = nullptr, s_topk = nullptr;
-    std::vector<hipEvent_t> ev_pool;  // untimed events, 6 per sub-batch
+    std::vector<hipEvent_t> ev_pool;  // untimed events of both, four per frame range (lg_select.hip: EV_DT .. EV_DONE)
     hipEvent_t ev_begin = nullptr;
     // workspace, sized for (capB, capH, capW)
     int capB = 0, capH = 0, capW = 0, capK = 0;
@@ -104,7 +105,7 @@ struct lg_ctx {
     hipEvent_t ev_orient = nullptr, ev_side = nullptr, ev_search = nullptr;
     int last_dt_algo = 0;           // lg_debug_dt_search_form: the form the row search of the last call took (0: no search was queued)
     int prof_on = 0;  // 0 off, 1 every kernel (event pairs on the stream), 2 only launches that stamp their own events
-    // true while the call queues lanes 1 .. of its tail (lg_select_grasp_impl): a scope opened now continues the launch that lane
+    // true while the call queues lanes 1 .. of its tail (schedule_lanes): a scope opened now continues the launch that lane
     // 0 counted -- prof_flush adds its milliseconds to the slot without counting a launch, so a slot reads one launch per call
     // and the sum of its lanes' times (which overlap: the slots of a call in lanes add up to more than its wall time)
     bool prof_cont = false;

@@ -302,7 +302,7 @@ struct Plan {  // one call's geometry, parameters and plane pointers (absolute, 
     // stay unwritten, lg_final_kernel records per tile which were written (tile_state), top-k and the gather read that
     bool sparse = false;
     // near launch: lg_final_kernel takes only the tiles around the leaves (lg_near_tiles), the others get their constant key and
-    // state byte from lg_near_tiles_kernel beside the distance transform.  Sparse mode, one sub-batch, constant-tile path on.
+    // state byte from lg_near_tiles_kernel beside the distance transform.  Set with `sparse`, by takes_near_launch.
     bool near = false;
     // deferred planes (sparse mode, unless LG_DEFER_PLANES=0): lg_final_kernel stores what top-k reads and flatness (score-only);
     // sdf, approach, isolation, accessibility and stem are neither allocated nor written: the gather computes them at the
@@ -362,31 +362,27 @@ int enq_tail(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
     return LG_OK;
 }
 
-// pack bits + D2H of the bit rows on the copy stream
-int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_t ev_prep) {
+// pack bits of the whole batch (h->ev_prep behind them) + what reads only the bit rows, on the side streams
+int enq_prep(lg_ctx* h, const Plan& pl, hipStream_t s) {
     h->export_pending = true;
-    const size_t px = (size_t)pl.H * pl.W, words = (size_t)pl.H * pl.WW;
-    LG_HIP(h, hipMemsetAsync(h->maxfix + LG_MF * (size_t)off, 0, sizeof(uint32_t) * LG_MF * n, s));
-    if (pl.label_aware) LG_HIP(h, hipMemsetAsync(h->iso_mf + LG_ISO_MF * (size_t)off, 0, sizeof(uint32_t) * LG_ISO_MF * n, s));
+    const int n = pl.B;
+    LG_HIP(h, hipMemsetAsync(h->maxfix, 0, sizeof(uint32_t) * LG_MF * n, s));
+    if (pl.label_aware) LG_HIP(h, hipMemsetAsync(h->iso_mf, 0, sizeof(uint32_t) * LG_ISO_MF * n, s));
     {
         ProfScope ps(h, "prep", s);
-        if (pl.labels && pl.label_aware)   // (one sub-batch: off = 0)
-            lg_launch_pack_labels(pl.labels + off * px, h->ids_dev + off, h->mask_ws + off * px, h->bits + off * words, n, pl.H, pl.W,
-                                  pl.WW, s, h->maxfix + LG_MF * (size_t)off, h->iso_others + off * words, h->iso_mf + LG_ISO_MF * (size_t)off);
-        else if (pl.labels)
-            lg_launch_pack_labels(pl.labels + off * px, h->ids_dev + off, h->mask_ws + off * px, h->bits + off * words, n, pl.H, pl.W,
-                                  pl.WW, s, h->maxfix + LG_MF * (size_t)off);
+        if (pl.labels)   // (label-aware: the other leaves' rows as well)
+            lg_launch_pack_labels(pl.labels, h->ids_dev, h->mask_ws, h->bits, n, pl.H, pl.W, pl.WW, s, h->maxfix,
+                                  pl.label_aware ? h->iso_others : nullptr, pl.label_aware ? h->iso_mf : nullptr);
         else
-            lg_launch_pack_bits(pl.mask + off * px, h->bits + off * words, n, pl.H, pl.W, pl.WW, s, h->maxfix + LG_MF * (size_t)off);
+            lg_launch_pack_bits(pl.mask, h->bits, n, pl.H, pl.W, pl.WW, s, h->maxfix);
     }
     {
         ProfScope ps(h, "bbox", s);
-        lg_launch_window(h->maxfix + LG_MF * (size_t)off, h->win + off, n, pl.H, pl.W, h->opt.dt_search, s,
-                         (uint32_t)pl.P.chamfer_init_dist0);
+        lg_launch_window(h->maxfix, h->win, n, pl.H, pl.W, h->opt.dt_search, s, (uint32_t)pl.P.chamfer_init_dist0);
     }
-    LG_HIP(h, hipEventRecord(ev_prep, s));
-    LG_HIP(h, hipStreamWaitEvent(h->copy_stream, ev_prep, 0));
-    if (pl.near) {   // (one sub-batch: off = 0, n = B)  list offsets of the near tiles + the far tiles' keys and state bytes
+    LG_HIP(h, hipEventRecord(h->ev_prep, s));
+    LG_HIP(h, hipStreamWaitEvent(h->copy_stream, h->ev_prep, 0));
+    if (pl.near) {   // list offsets of the near tiles + the far tiles' keys and state bytes
         // On the caller's stream, which (the row search runs on a stream of its own) has little to do until the plane kernel and
         // orders the plane kernel and top-k behind it for free -- not in front of the orientation kernel on the side stream,
         // whose chain nothing of this feeds.  The host reads near_off_host[n] behind ev_near (enq_final), after ev_orient.
@@ -402,13 +398,12 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
         const bool direct = h->fp_host_dev && h->orient->h_status_dev;
         {
             ProfScope ps(h, "orient", h->copy_stream);
-            lg_launch_orient(h->orient, h->bits + off * words, h->win + off, h->fp_dev + off, off, n, pl.H, pl.W, pl.WW, h->copy_stream,
-                             direct ? h->fp_host_dev + off : nullptr);
+            lg_launch_orient(h->orient, h->bits, h->win, h->fp_dev, 0, n, pl.H, pl.W, pl.WW, h->copy_stream,
+                             direct ? h->fp_host_dev : nullptr);
         }
         if (!direct) {
-            LG_HIP(h, hipMemcpyAsync(h->fp_host + off, h->fp_dev + off, sizeof(LgFrameParams) * n, hipMemcpyDeviceToHost, h->copy_stream));
-            LG_HIP(h, hipMemcpyAsync(h->orient->h_status + off, h->orient->status + off, sizeof(int) * n, hipMemcpyDeviceToHost,
-                                     h->copy_stream));
+            LG_HIP(h, hipMemcpyAsync(h->fp_host, h->fp_dev, sizeof(LgFrameParams) * n, hipMemcpyDeviceToHost, h->copy_stream));
+            LG_HIP(h, hipMemcpyAsync(h->orient->h_status, h->orient->status, sizeof(int) * n, hipMemcpyDeviceToHost, h->copy_stream));
         }
         LG_HIP(h, hipEventRecord(h->ev_orient, h->copy_stream));
     }
@@ -428,8 +423,8 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
         // search uses s_dt[1]).
         const bool own_tail = h->opt.subbatch == 0 && (h->opt.side_tail == 2 || n <= 32);
         hipStream_t ts = own_tail ? h->s_dt[0] : h->copy_stream;
-        if (ts != h->copy_stream) LG_HIP(h, hipStreamWaitEvent(ts, ev_prep, 0));
-        const int rc = enq_tail(h, pl, off, n, ts);
+        if (ts != h->copy_stream) LG_HIP(h, hipStreamWaitEvent(ts, h->ev_prep, 0));
+        const int rc = enq_tail(h, pl, 0, n, ts);
         if (rc) return rc;
         LG_HIP(h, hipEventRecord(h->ev_side, ts));
     }
@@ -439,16 +434,14 @@ int enq_prep(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s, hipEvent_
 // Bit rows of the bounding boxes + the windows to the host: only for the host contour analysis (LG_HOST_ORIENT, or frames the
 // device orientation kernel hands back) -- since round 3 the pre-grasp probes run on the device (lg_finish_kernel) and a normal
 // call exports nothing.  The export writes pinned host memory over PCIe and slows every memory-bound kernel beside it about 4x,
-// which is why it is only queued when somebody is about to wait for it.  `after`: an event to wait for first, or nullptr.
-int enq_export(lg_ctx* h, const Plan& pl, int off, int n, hipEvent_t after) {
-    const size_t words = (size_t)pl.H * pl.WW;
-    if (after) LG_HIP(h, hipStreamWaitEvent(h->copy_stream, after, 0));
+// which is why it is only queued when somebody is about to wait for it.  The whole batch.
+int enq_export(lg_ctx* h, const Plan& pl) {
+    const size_t words = (size_t)pl.B * pl.H * pl.WW;
     if (h->bits_host_dev)   // rows of the bounding boxes only, posted writes by a small grid on the priority stream
-        lg_launch_export_rows(h->bits + off * words, h->win + off, h->bits_host_dev + off * words, n, pl.H, pl.WW, h->copy_stream);
+        lg_launch_export_rows(h->bits, h->win, h->bits_host_dev, pl.B, pl.H, pl.WW, h->copy_stream);
     else
-        LG_HIP(h, hipMemcpyAsync(h->bits_host + off * words, h->bits + off * words, sizeof(unsigned long long) * n * words,
-                                 hipMemcpyDeviceToHost, h->copy_stream));
-    LG_HIP(h, hipMemcpyAsync(h->win_host + off, h->win + off, sizeof(LgWin) * n, hipMemcpyDeviceToHost, h->copy_stream));
+        LG_HIP(h, hipMemcpyAsync(h->bits_host, h->bits, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, h->copy_stream));
+    LG_HIP(h, hipMemcpyAsync(h->win_host, h->win, sizeof(LgWin) * pl.B, hipMemcpyDeviceToHost, h->copy_stream));
     LG_HIP(h, hipEventRecord(h->ev_copy, h->copy_stream));
     h->export_pending = false;
     return LG_OK;
@@ -505,7 +498,7 @@ int enq_dt(lg_ctx* h, const Plan& pl, int off, int n, hipStream_t s) {
     return LG_OK;
 }
 
-// Label-aware mode (one sub-batch: frame 0 of the call): others -> two dilations -> two chamfer-3 transforms, behind the distance
+// Label-aware mode (the whole batch; such a call is never piped): others -> two dilations -> two chamfer-3 transforms, behind the distance
 // transform on the caller's stream: the fields take the sweeps' scratch (h->tmp, [B][2][H][W] words), free from here on.  A frame
 // without another leaf is skipped by every kernel.
 LgIsoFields iso_fields(const lg_ctx* h) { return {h->tmp, h->iso_mf}; }
@@ -549,26 +542,26 @@ void host_orient_frame(lg_ctx* h, const Plan& pl, int b) {
     h->fp_host[b] = f;
 }
 
-// Orientation of frames [off, off+n) into fp_host (and fp_dev).  Device path: wait for lg_orient_kernel's results (it runs
+// Orientation of every frame into fp_host (and fp_dev).  Device path: wait for lg_orient_kernel's results (it runs
 // beside the sweeps on the side stream); frames it handed back (status 1: more runs than its scratch holds) are analysed on
 // the host threads.  LG_HOST_ORIENT: every frame on the host.  *upload = fp_host has entries the device does not have yet.
-int finish_orient(lg_ctx* h, const Plan& pl, int off, int n, bool* upload) {
+int finish_orient(lg_ctx* h, const Plan& pl, bool* upload) {
     *upload = true;
     h->last_redo = 0;
     if (!h->orient) {
-        if (h->export_pending) { const int rc = enq_export(h, pl, 0, pl.B, nullptr); if (rc) return rc; }
+        if (h->export_pending) { const int rc = enq_export(h, pl); if (rc) return rc; }
         LG_HIP(h, hipEventSynchronize(h->ev_copy));   // bit rows are on the host; the sweeps are running
-        parallel_for(h, n, [=, &pl](int i) { host_orient_frame(h, pl, off + i); });
+        parallel_for(h, pl.B, [=, &pl](int b) { host_orient_frame(h, pl, b); });
         return LG_OK;
     }
     LG_HIP(h, hipEventSynchronize(h->ev_orient));
     std::vector<int> redo;
-    for (int i = 0; i < n; i++)
-        if (h->orient->h_status[off + i]) redo.push_back(off + i);
+    for (int b = 0; b < pl.B; b++)
+        if (h->orient->h_status[b]) redo.push_back(b);
     h->last_redo = (int)redo.size();
     *upload = !redo.empty();
     if (redo.empty()) return LG_OK;
-    if (h->export_pending) { const int rc = enq_export(h, pl, 0, pl.B, nullptr); if (rc) return rc; }
+    if (h->export_pending) { const int rc = enq_export(h, pl); if (rc) return rc; }
     LG_HIP(h, hipEventSynchronize(h->ev_copy));
     const int* rp = redo.data();
     parallel_for(h, (int)redo.size(), [=, &pl](int i) { host_orient_frame(h, pl, rp[i]); });
@@ -695,34 +688,33 @@ struct Timeline {
     }
 };
 
-// A whole call as one sub-batch on the caller's stream, up to its planes: bit rows -> `after_prep` (what else reads only the bit
-// rows and the bounding boxes) -> distance transform -> label-aware fields -> orientation -> plane kernel -> stored isolation
-// plane.  *fargs: the plane launch's arguments, for the deferred gather.
-// does a call with this plan take the near launch of the plane kernel?
+// Plan::near: does a call with this plan take the near launch of the plane kernel?  Asked once per call, where `sparse` is set
+// (an LG_SUBBATCH handle never does: its plane launches are per sub-batch, the list is the batch's).
 bool takes_near_launch(const lg_ctx* h, const Plan& pl) {
     return pl.sparse && h->opt.final_near > 0 && h->opt.subbatch == 0 && h->opt.no_skip == 0;
 }
 
 // enq_front up to, and without, the plane kernel.  *upload_fp: as finish_orient's.
 template <typename AfterPrep>
-int enq_front_sweeps(lg_ctx* h, Plan& pl, hipStream_t s, Timeline* tl, AfterPrep&& after_prep, bool* upload_fp) {
-    pl.near = takes_near_launch(h, pl);
-    int rc = enq_prep(h, pl, 0, pl.B, s, h->ev_prep);
+int enq_front_sweeps(lg_ctx* h, const Plan& pl, hipStream_t s, Timeline* tl, AfterPrep&& after_prep, bool* upload_fp) {
+    int rc = enq_prep(h, pl, s);
     if (rc) return rc;
     if ((rc = after_prep())) return rc;
     if ((rc = enq_dt(h, pl, 0, pl.B, s))) return rc;
     if ((rc = enq_iso(h, pl, s))) return rc;
     if (tl) { tl->mark(Timeline::SWEEPS); tl->host(Timeline::ENQ1); }
-    *upload_fp = true;
-    if ((rc = finish_orient(h, pl, 0, pl.B, upload_fp))) return rc;   // theta per frame: device results (or host analysis) while the sweeps run
+    if ((rc = finish_orient(h, pl, upload_fp))) return rc;   // theta per frame: device results (or host analysis) while the sweeps run
     if (tl) tl->host(Timeline::ORIENT);
     return LG_OK;
 }
 
+// A whole call on the caller's stream, up to its planes: bit rows -> `after_prep` (what else reads only the bit rows and the
+// bounding boxes) -> distance transform -> label-aware fields -> orientation -> plane kernel -> stored isolation plane.
+// *fargs: the plane launch's arguments, for the deferred gather.
 template <typename AfterPrep>
-int enq_front(lg_ctx* h, Plan& pl, hipStream_t s, LgFinalArgs* fargs, Timeline* tl, AfterPrep&& after_prep) {
+int enq_front(lg_ctx* h, const Plan& pl, hipStream_t s, LgFinalArgs* fargs, AfterPrep&& after_prep) {
     bool upload_fp = true;
-    int rc = enq_front_sweeps(h, pl, s, tl, after_prep, &upload_fp);
+    int rc = enq_front_sweeps(h, pl, s, nullptr, after_prep, &upload_fp);
     if (rc) return rc;
     if ((rc = enq_final(h, pl, 0, pl.B, s, upload_fp, fargs))) return rc;
     enq_iso_plane(h, pl, *fargs, s);
@@ -759,6 +751,191 @@ int return_results(lg_ctx* h, const Plan& pl, lg_grasp_result* results, bool use
     return LG_OK;
 }
 
+// ============================================================================ the tail of lg_select_grasp*, per frame range
+// What the ranges of one call's tail share, and range k of it -- a lane, or a sub-batch: frames [off, off + n), with the first
+// pixel of its planes, the first tile of its tile tables and the first of its K-per-frame candidate slots.
+struct Tail {
+    lg_ctx* h; const Plan& pl; int K; bool use_cnn, prune;
+    std::vector<LgFinalArgs> fargs;   // per range: the plane launch's arguments, for the deferred gather
+    LgIsoFields iso;
+};
+struct Range { int k, off, n; size_t px, tile, cand; };
+Range frame_range(const Tail& t, int SB, int k) {
+    const Plan& pl = t.pl;
+    const int off = k * SB;
+    return {k, off, std::min(SB, pl.B - off), (size_t)off * pl.H * pl.W, (size_t)off * pl.tiles_x * pl.tiles_y, (size_t)off * t.K};
+}
+
+// The untimed events of range k (h->ev_pool): its sweeps, its planes, its top-k are queued; it has ended.
+enum { EV_DT, EV_PLANES, EV_TOPK, EV_DONE, EV_PER_RANGE };
+hipEvent_t range_ev(const lg_ctx* h, int k, int which) { return h->ev_pool[EV_PER_RANGE * k + which]; }
+int ensure_range_events(lg_ctx* h, int ranges) {
+    while ((int)h->ev_pool.size() < EV_PER_RANGE * ranges) {
+        hipEvent_t e;
+        LG_HIP(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        h->ev_pool.push_back(e);
+    }
+    return LG_OK;
+}
+
+// greedy spaced top-k of the range's frames and, pruned, the candidates of each that can still win (surv_keep)
+void enq_topk(const Tail& t, const Range& r, hipStream_t s) {
+    lg_ctx* h = t.h; const Plan& pl = t.pl;
+    const lg_params& P = pl.P;
+    ProfScope ps(h, "topk", s);
+    lg_launch_topk(pl.maps[LG_MAP_TRADITIONAL] + r.px, pl.valid + r.px, pl.depth + r.px, h->tilekeys + r.tile,
+                   pl.sparse ? h->tile_state + r.tile : nullptr, P.flat_scale, P.w_flat, true, r.n, pl.H, pl.W, t.K, P.nms_min_distance,
+                   h->cand_xy + r.cand * 2, h->cand_n + r.off, h->cand_info + r.cand * 2, s, t.prune ? h->surv_keep + r.off : nullptr,
+                   P.mask_is_bool);
+}
+
+// CNN rescoring of the range's candidates, behind its top-k on `s`: survivors (pruned: the range's own list, slot map and count)
+// -> patch gather -> lg_cnn_run on the activation buffers from slot act_off on.  Without a model: nothing.
+int enq_rescore(const Tail& t, const Range& r, hipStream_t s, int act_off) {
+    if (!t.use_cnn) return LG_OK;
+    lg_ctx* h = t.h; const Plan& pl = t.pl;
+    const int32_t* list = t.prune ? h->surv_list + r.cand : nullptr;
+    const int32_t* count = t.prune ? h->surv_count + r.k : nullptr;
+    float* patches = h->patches + r.cand * lg_cnn_halo_patch_floats();
+    if (t.prune) {
+        ProfScope ps(h, "survivors", s);
+        lg_launch_survivors(h->surv_keep + r.off, r.n, t.K, h->surv_list + r.cand, h->surv_slot + r.cand, h->surv_count + r.k, s);
+    }
+    {
+        ProfScope ps(h, "gather", s);
+        const float* mp[LG_NUM_MAPS];
+        for (int i = 0; i < LG_NUM_MAPS; i++) mp[i] = pl.maps[i] ? pl.maps[i] + r.px : nullptr;
+        lg_launch_gather(pl.depth + r.px, pl.mask + r.px, mp, pl.sparse ? h->tile_state + r.tile : nullptr, pl.P.flat_scale, r.n, pl.H,
+                         pl.W, t.K, h->cand_xy + r.cand * 2, h->cand_n + r.off, patches, true, s, list, count,
+                         pl.defer ? &t.fargs[r.k] : nullptr, pl.label_aware ? &t.iso : nullptr);
+    }
+    std::string err;
+    ProfScope ps(h, "cnn", s);
+    const int rc = lg_cnn_run(&h->cnn, patches, true, r.n * t.K, h->logits + r.cand, s, &err, false, count, act_off);
+    return rc ? fail(h, rc, err.c_str()) : LG_OK;
+}
+
+// ============================================================================ how a call's frames are cut, and its two schedules
+// One range -- the ordinary call --, tail lanes, or the sub-batches of an LG_SUBBATCH handle (label-aware calls excepted: their
+// transforms reuse the sweeps' scratch).  `ranges` ranges of SB frames, the last one shorter; lane_slots: a lane's range of the
+// CNN's activation buffers.
+// Lanes run only where the pruned CNN pass follows the near launch: a model, LG_CNN_PRUNE, not the candidates entry, not
+// label-aware, not piped (lg_tail_lane_plan has the rule, lg_debug_tail_lanes overrides it; DESIGN.md section 4, "Tail in lanes").
+// The automatic rule also asks that no other handle of the process is inside a selection call (InFlight, which lives as long as
+// the call): lanes fill the holes of a chip this call would otherwise have to itself.  With two batches in flight on two
+// handles (bench.py's `pipelined`) the other batch fills them already, and lanes cost 5-10 % there (1.74, 1.82 against 1.65,
+// 1.67 ms per step before this rule).  Results never depend on the lanes, so a rule that depends on timing is safe.
+// And it asks that the call's B * K patch slots fit one slice of lg_cnn_run: a larger call runs its CNN in slices one behind
+// the other in the activation workspace of ONE slice (6.5 GB for the standard model); in lanes each lane would hold a slice's
+// worth of it.  The automatic rule never grows that workspace beyond what the one-lane call takes.  A forced setting ignores both.
+struct InFlight {
+    const int others;
+    InFlight() : others(g_select_in_flight.fetch_add(1, std::memory_order_relaxed)) {}
+    ~InFlight() { g_select_in_flight.fetch_sub(1, std::memory_order_relaxed); }
+};
+struct Cut { bool piped; int lanes, SB, ranges, lane_slots; };
+Cut cut_frames(const lg_ctx* h, const Plan& pl, int K, bool prune, const InFlight& in_flight) {
+    const int B = pl.B;
+    Cut c = {false, 1, B, 1, 0};
+    if (h->opt.subbatch > 0 && !pl.label_aware) c.SB = h->opt.subbatch;
+    c.piped = c.SB < B;
+    const bool one_slice = lg_cnn_act_slots(B * K) == B * K;
+    const int lanes_req = h->tail_lanes_req ? h->tail_lanes_req : (in_flight.others || !one_slice ? 1 : 0);
+    int32_t lanes = 1, lane_sb = B;
+    lg_tail_lane_plan(B, lanes_req, !c.piped && prune && !pl.label_aware && pl.near, &lanes, &lane_sb);
+    if (lanes > 1) { c.lanes = lanes; c.SB = lane_sb; }
+    c.ranges = (B + c.SB - 1) / c.SB;
+    c.lane_slots = lg_cnn_act_slots(c.SB * K);
+    return c;
+}
+
+// The call in lanes; one lane is the ordinary call.  The front runs ONCE for the whole batch and only what follows it -- planes,
+// top-k, survivors, gather, CNN -- runs per lane of SB consecutive frames, each lane an in-order chain on a stream of its own:
+// lane 0 on the caller's, lanes 1 .. on library streams that are idle by now (s_main first: LG_TAIL_LANE_STREAMS has the
+// reading), lane k's plane launch behind lane k - 1's, which puts it behind the front and staggers the lanes; the caller's
+// stream goes on behind every lane.  The front costs what it did and the lanes fill each other's holes: the left-over rounds
+// of a lane's persistent CNN launches, its seven launch boundaries and its one-workgroup-per-frame top-k run beside the other
+// lane's matrix work (1.82 against 1.89 ms per step at 256 frames).  Whole CNN items, a survivor list, count and slot map per
+// lane and a range of the activation buffers per lane (lg_cnn_run's act_off; room reserved by the caller before anything is
+// queued) keep every logit, candidate and result row equal to the one-lane call's bit for bit.
+// One lane: everything on the caller's stream, no event, prof_cont never set.  The timeline's marks follow lane 0.
+int schedule_lanes(Tail& t, const Cut& c, hipStream_t s, Timeline& tl) {
+    lg_ctx* h = t.h; const Plan& pl = t.pl;
+    bool upload_fp = true;
+    int rc = enq_front_sweeps(h, pl, s, &tl, nothing_after_prep, &upload_fp);
+    if (rc) return rc;
+    const hipStream_t lane_s[4] = {s, LG_TAIL_LANE_STREAMS};
+    for (int k = 0; k < c.lanes; k++) {
+        const Range r = frame_range(t, c.SB, k);
+        const hipStream_t ls = lane_s[k];
+        h->prof_cont = k > 0;
+        if (k) LG_HIP(h, hipStreamWaitEvent(ls, range_ev(h, k - 1, EV_PLANES), 0));
+        if ((rc = enq_final(h, pl, r.off, r.n, ls, upload_fp, &t.fargs[k]))) return rc;
+        if (k + 1 < c.lanes) LG_HIP(h, hipEventRecord(range_ev(h, k, EV_PLANES), ls));
+        enq_iso_plane(h, pl, t.fargs[k], ls);   // (the whole batch's: label-aware calls are one lane)
+        if (!k) tl.mark(Timeline::PLANES);
+        enq_topk(t, r, ls);
+        if (!k) tl.mark(Timeline::TOPK);
+        if ((rc = enq_rescore(t, r, ls, k * c.lane_slots))) return rc;
+        if (k) LG_HIP(h, hipEventRecord(range_ev(h, k, EV_DONE), ls));
+    }
+    h->prof_cont = false;
+    for (int k = 1; k < c.lanes; k++) LG_HIP(h, hipStreamWaitEvent(s, range_ev(h, k, EV_DONE), 0));
+    tl.mark(Timeline::CNN);
+    return LG_OK;
+}
+
+// The LG_SUBBATCH experiment (LG_SUBBATCH=n in the environment when the handle is created): the front is cut as well.  Stages
+// per sub-batch k of SB frames:
+//   D(k): distance sweeps (the bit rows: once, in front)   -- latency bound, 2*SB workgroups  -> s_dt[k&1]
+//   F(k): fused score planes                               -- HBM bound                       -> s_main
+//   T(k): greedy spaced top-k                              -- latency bound, SB workgroups    -> s_topk
+//   G(k): survivors, patch gather, CNN                     -- MFMA bound                      -> s_main
+// s_main runs F(0) F(1) G(0) F(2) G(1) ... so T(k) hides behind F(k+1) and the D chain behind everything.
+// Measured on MI355X (B=128, 1080p): SB=32 is 14.8 ms/step vs 11.5 ms in one range -- the chain D(0)->F(0)->T(0) must drain
+// before the first CNN launch, and D's latency does not shrink with SB.  The lanes above cut only the tail, and win.
+int schedule_subbatches(Tail& t, const Cut& c, hipStream_t s, Timeline& tl) {
+    lg_ctx* h = t.h; const Plan& pl = t.pl;
+    const hipStream_t sD[2] = {h->s_dt[0], h->s_dt[1]}, sM = h->s_main, sT = h->s_topk;
+    // internal streams start after whatever the caller queued on `s`
+    LG_HIP(h, hipEventRecord(h->ev_begin, s));
+    for (hipStream_t q : {sD[0], sD[1], sM, sT}) LG_HIP(h, hipStreamWaitEvent(q, h->ev_begin, 0));
+    // bit rows of the whole batch first (one short kernel) so the host never waits behind a distance sweep
+    int rc = enq_prep(h, pl, sD[0]);
+    if (rc) return rc;
+    LG_HIP(h, hipStreamWaitEvent(sD[1], h->ev_prep, 0));
+    for (int k = 0; k < c.ranges; k++) {
+        const Range r = frame_range(t, c.SB, k);
+        if ((rc = enq_dt(h, pl, r.off, r.n, sD[k & 1]))) return rc;
+        LG_HIP(h, hipEventRecord(range_ev(h, k, EV_DT), sD[k & 1]));
+    }
+    tl.host(Timeline::ENQ1);
+    bool upload_fp = true;
+    if ((rc = finish_orient(h, pl, &upload_fp))) return rc;
+    tl.host(Timeline::ORIENT);
+    for (int k = 0; k < c.ranges; k++) {   // F(k) T(k) G(k - 1)
+        const Range r = frame_range(t, c.SB, k);
+        LG_HIP(h, hipStreamWaitEvent(sM, range_ev(h, k, EV_DT), 0));
+        if ((rc = enq_final(h, pl, r.off, r.n, sM, upload_fp, &t.fargs[k]))) return rc;
+        LG_HIP(h, hipEventRecord(range_ev(h, k, EV_PLANES), sM));
+        LG_HIP(h, hipStreamWaitEvent(sT, range_ev(h, k, EV_PLANES), 0));
+        enq_topk(t, r, sT);
+        LG_HIP(h, hipEventRecord(range_ev(h, k, EV_TOPK), sT));
+        if (k >= 1) {
+            LG_HIP(h, hipStreamWaitEvent(sM, range_ev(h, k - 1, EV_TOPK), 0));
+            if ((rc = enq_rescore(t, frame_range(t, c.SB, k - 1), sM, 0))) return rc;
+        }
+    }
+    LG_HIP(h, hipStreamWaitEvent(sM, range_ev(h, c.ranges - 1, EV_TOPK), 0));
+    if ((rc = enq_rescore(t, frame_range(t, c.SB, c.ranges - 1), sM, 0))) return rc;
+    for (hipStream_t q : {sD[0], sD[1], sM, sT}) {   // join: the caller's stream continues after every internal stream
+        LG_HIP(h, hipEventRecord(range_ev(h, 0, EV_DONE), q));
+        LG_HIP(h, hipStreamWaitEvent(s, range_ev(h, 0, EV_DONE), 0));
+        LG_HIP(h, hipStreamSynchronize(q));
+    }
+    return LG_OK;
+}
+
 int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* mask, const int16_t* labels, int B, int H, int W,
                          const lg_params* pin, float* const out_maps[LG_NUM_MAPS], uint8_t* out_valid, lg_grasp_result* results,
                          lg_grasp_candidate* cands, void* stream_) {
@@ -772,197 +949,44 @@ int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* mask, c
     pl.label_aware = pl.P.label_aware != 0;
     pl.sparse = !out_valid;
     for (int i = 0; i < LG_NUM_MAPS; i++) pl.sparse = pl.sparse && !pl.maps[i];
-    const lg_params& P = pl.P;
-    if (P.top_k < 1 || P.top_k > 64) return fail(h, LG_ERR_INVALID, "lg_select_grasp: top_k must be in [1,64]");
+    pl.near = takes_near_launch(h, pl);
+    pl.defer = pl.sparse && h->opt.defer_planes;
+    const int K = pl.P.top_k;
+    if (K < 1 || K > 64) return fail(h, LG_ERR_INVALID, "lg_select_grasp: top_k must be in [1,64]");
     hipStream_t s = (hipStream_t)stream_;
     LG_HIP(h, hipSetDevice(h->device));
-    if ((rc = ensure_ws(h, B, H, W, P.top_k))) return rc;
+    if ((rc = ensure_ws(h, B, H, W, K))) return rc;
     reset_last(h);
     if (pl.label_aware) rc = ensure_iso_ws(h, pl, "lg_select_grasp_labels: label-aware workspace");
-    if (!rc && cands) rc = ensure_cand_rows(h, (size_t)B * P.top_k);
+    if (!rc && cands) rc = ensure_cand_rows(h, (size_t)B * K);
     if (rc) return rc;
     const bool use_cnn = h->cnn.loaded;
     // The CNN on the candidates that can still win only (the result row needs no other; the candidates entry reports an ML
     // score for every candidate and scores them all).  Either way no item of the CNN is split: a patch's logit then does not
     // depend on how many patches run beside it, and the rows of both entries, pruned or not, are equal bit for bit.
     const bool prune = use_cnn && !cands && h->opt.cnn_prune && lg_cnn_counts_on_device(&h->cnn);
-    if (use_cnn) h->last_scored = (long long)B * P.top_k;
-    pl.defer = pl.sparse && h->opt.defer_planes;
+    if (use_cnn) h->last_scored = (long long)B * K;
     if ((rc = take_planes(h, pl, use_cnn))) return rc;
-    const int K = P.top_k;
-    const size_t px = (size_t)H * W;
-    const int tiles = pl.tiles_x * pl.tiles_y;
-
-    // ---- sub-batch pipeline.  Stages per sub-batch k of SB frames:
-    //   D(k): bit rows, stem bits, distance sweeps          -- latency bound, 2*SB workgroups  -> s_dt[k&1]
-    //   F(k): fused score planes                             -- HBM bound                       -> s_main
-    //   T(k): greedy spaced top-k                            -- latency bound, SB workgroups    -> s_topk
-    //   G(k): patch gather + CNN                             -- MFMA bound                      -> s_main
-    // s_main runs F(0) F(1) G(0) F(2) G(1) ... so T(k) hides behind F(k+1) and the D chain behind everything.
-    int SB = B;
-    // Measured on MI355X (B=128, 1080p): SB=32 is 14.8 ms/step vs 11.5 ms unpiped -- the chain
-    // D(0)->F(0)->T(0) must drain before the first CNN launch, and D's latency does not shrink with SB.
-    // Kept for experiments (LG_SUBBATCH=n in the environment when the handle is created); the default is one sub-batch.
-    if (h->opt.subbatch > 0 && !pl.label_aware) SB = h->opt.subbatch;   // (the label-aware transforms reuse the sweeps' scratch: one sub-batch)
-    const bool piped = SB < B;
-    // ---- tail in lanes.  The other way to cut a batch, and the one that pays at 256 frames (1.82 against 1.89 ms per step; the
-    // sub-batch pipeline above is the LG_SUBBATCH experiment, this one is on by rule): the front runs ONCE for the whole batch, exactly as
-    // in a call of one sub-batch, and only what follows it -- planes, top-k, survivors, gather, CNN -- runs per lane of SB
-    // consecutive frames, each lane an in-order chain on a stream of its own (lane 0: the caller's), lane k's plane launch
-    // behind lane k - 1's.  The pipeline above splits the front too, whose latency does not shrink with the frames, and loses;
-    // here the front costs what it did and the lanes fill each other's holes: the left-over rounds of a lane's persistent CNN
-    // launches, its seven launch boundaries and its one-workgroup-per-frame top-k run beside the other lane's matrix work.
-    // Whole CNN items, a survivor list, count and slot map per lane and a range of the activation buffers per lane
-    // (lg_cnn_run's act_off) keep every logit, candidate and result row equal to the one-lane call's bit for bit.
-    // Only where the pruned CNN pass follows the near launch: a model, LG_CNN_PRUNE, not the candidates entry, not label-aware
-    // (lg_tail_lane_plan has the rule, lg_debug_tail_lanes overrides it; DESIGN.md section 4, "Tail in lanes").
-    // The automatic rule also asks that no other handle of the process is inside a selection call: lanes fill the holes of a
-    // chip this call would otherwise have to itself.  With two batches in flight on two handles (bench.py's `pipelined`) the
-    // other batch fills them already, and lanes cost 5-10 % there (1.74, 1.82 against 1.65, 1.67 ms per step before this
-    // rule).  Results never depend on the lanes, so a rule that depends on timing is safe; a forced setting ignores it.
-    struct InFlight {
-        const int others;
-        InFlight() : others(g_select_in_flight.fetch_add(1, std::memory_order_relaxed)) {}
-        ~InFlight() { g_select_in_flight.fetch_sub(1, std::memory_order_relaxed); }
-    } in_flight;
-    // And it asks that the call's B * K patch slots fit one slice of lg_cnn_run: a larger call runs its CNN in slices one behind
-    // the other in the activation workspace of ONE slice (6.5 GB for the standard model); in lanes each lane would hold a
-    // slice's worth of it.  The automatic rule never grows that workspace beyond what the one-lane call takes.
-    const bool one_slice = lg_cnn_act_slots(B * K) == B * K;
-    const int lanes_req = h->tail_lanes_req ? h->tail_lanes_req : (in_flight.others || !one_slice ? 1 : 0);
-    int32_t lanes = 1, lane_sb = B;
-    lg_tail_lane_plan(B, lanes_req, !piped && prune && !pl.label_aware && takes_near_launch(h, pl), &lanes, &lane_sb);
-    const bool laned = lanes > 1;
-    if (laned) SB = lane_sb;
-    const int nsub = (B + SB - 1) / SB;
-    h->last_tail_lanes = laned ? nsub : 1;
-    // the lanes' ranges of the CNN's activation buffers: made before anything is queued (growing them synchronises and frees)
-    const int lane_slots = lg_cnn_act_slots(SB * K);
-    if (laned) {
+    InFlight in_flight;
+    const Cut c = cut_frames(h, pl, K, prune, in_flight);
+    h->last_tail_lanes = c.lanes;
+    if (c.lanes > 1) {   // the lanes' ranges of the CNN's activation buffers: made before anything is queued (growing them synchronises and frees)
         std::string err;
-        const int r2 = lg_cnn_reserve(&h->cnn, (nsub - 1) * lane_slots + lg_cnn_act_slots((B - (nsub - 1) * SB) * K), s, &err);
+        const int r2 = lg_cnn_reserve(&h->cnn, (c.lanes - 1) * c.lane_slots + lg_cnn_act_slots((B - (c.lanes - 1) * c.SB) * K), s, &err);
         if (r2) return fail(h, r2, err.c_str());
     }
+    if ((rc = ensure_range_events(h, c.ranges))) return rc;
     struct ContGuard { lg_ctx* h; ~ContGuard() { h->prof_cont = false; } } cont_guard{h};
-    std::vector<LgFinalArgs> fargs((size_t)nsub);   // the plane launches' arguments, for the deferred gather
-    hipStream_t sD[2] = {piped ? h->s_dt[0] : s, piped ? h->s_dt[1] : s};
-    hipStream_t sM = piped ? h->s_main : s, sT = piped ? h->s_topk : s;
-    while ((int)h->ev_pool.size() < 6 * nsub) {
-        hipEvent_t e;
-        LG_HIP(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->ev_pool.push_back(e);
-    }
-    auto EV = [&](int k, int which) { return h->ev_pool[6 * k + which]; };  // 0 prep 1 copy 2 dt 3 final 4 topk 5 done
-    const LgIsoFields iso = iso_fields(h);
-    auto enq_T = [&](int k) {
-        const int off = k * SB, n = std::min(SB, B - off);
-        ProfScope ps(h, "topk", sT);
-        lg_launch_topk(pl.maps[LG_MAP_TRADITIONAL] + off * px, pl.valid + off * px, depth + off * px,
-                       h->tilekeys + (size_t)off * tiles, pl.sparse ? h->tile_state + (size_t)off * tiles : nullptr,
-                       P.flat_scale, P.w_flat, true, n, H, W, K, P.nms_min_distance,
-                       h->cand_xy + (size_t)off * K * 2, h->cand_n + off, h->cand_info + (size_t)off * K * 2, sT,
-                       prune ? h->surv_keep + off : nullptr, P.mask_is_bool);
-    };
-    auto enq_G = [&](int k, int act_off = 0) -> int {
-        const int off = k * SB, n = std::min(SB, B - off);
-        if (piped) LG_HIP(h, hipStreamWaitEvent(sM, EV(k, 4), 0));
-        if (use_cnn) {
-            const int32_t* list = prune ? h->surv_list + (size_t)off * K : nullptr;
-            const int32_t* count = prune ? h->surv_count + k : nullptr;
-            if (prune) {
-                ProfScope ps(h, "survivors", sM);
-                lg_launch_survivors(h->surv_keep + off, n, K, h->surv_list + (size_t)off * K, h->surv_slot + (size_t)off * K,
-                                    h->surv_count + k, sM);
-            }
-            {
-                ProfScope ps(h, "gather", sM);
-                const float* mp[LG_NUM_MAPS];
-                for (int i = 0; i < LG_NUM_MAPS; i++) mp[i] = pl.maps[i] ? pl.maps[i] + off * px : nullptr;
-                lg_launch_gather(depth + off * px, mask + off * px, mp, pl.sparse ? h->tile_state + (size_t)off * tiles : nullptr,
-                                 P.flat_scale, n, H, W, K, h->cand_xy + (size_t)off * K * 2,
-                                 h->cand_n + off, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, sM, list, count,
-                                 pl.defer ? &fargs[k] : nullptr, pl.label_aware ? &iso : nullptr);
-            }
-            std::string err;
-            {
-                ProfScope ps(h, "cnn", sM);
-                int r2 = lg_cnn_run(&h->cnn, h->patches + (size_t)off * K * lg_cnn_halo_patch_floats(), true, n * K, h->logits + (size_t)off * K, sM, &err,
-                                    false, count, act_off);
-                if (r2) return fail(h, r2, err.c_str());
-            }
-        }
-        return LG_OK;
-    };
-    Timeline tl(h->opt.trace, !piped, s);
-    if (laned) {
-        bool upload_fp = true;
-        if ((rc = enq_front_sweeps(h, pl, s, &tl, nothing_after_prep, &upload_fp))) return rc;
-        // Lanes 1 .. on library streams that are idle by now and, through the event of the lane before, behind the front on the
-        // caller's stream.  s_main first: LG_TAIL_LANE_STREAMS has the reading.
-        const hipStream_t lane_s[4] = {s, LG_TAIL_LANE_STREAMS};
-        for (int k = 0; k < nsub; k++) {   // (EV(k, 3): lane k's planes are written; EV(k, 5): lane k has ended)
-            const int off = k * SB, n = std::min(SB, B - off);
-            sM = sT = lane_s[k];
-            h->prof_cont = k > 0;
-            if (k) LG_HIP(h, hipStreamWaitEvent(sM, EV(k - 1, 3), 0));
-            if ((rc = enq_final(h, pl, off, n, sM, upload_fp, &fargs[k]))) return rc;
-            if (k + 1 < nsub) LG_HIP(h, hipEventRecord(EV(k, 3), sM));
-            if (!k) tl.mark(Timeline::PLANES);
-            enq_T(k);
-            if (!k) tl.mark(Timeline::TOPK);
-            if ((rc = enq_G(k, k * lane_slots))) return rc;
-            if (k) LG_HIP(h, hipEventRecord(EV(k, 5), sM));
-        }
-        h->prof_cont = false;
-        for (int k = 1; k < nsub; k++) LG_HIP(h, hipStreamWaitEvent(s, EV(k, 5), 0));
-    } else if (!piped) {
-        if ((rc = enq_front(h, pl, s, &fargs[0], &tl, nothing_after_prep))) return rc;
-        tl.mark(Timeline::PLANES);
-        enq_T(0);
-        tl.mark(Timeline::TOPK);
-    } else {
-        // internal streams start after whatever the caller queued on `s`
-        LG_HIP(h, hipEventRecord(h->ev_begin, s));
-        for (hipStream_t q : {sD[0], sD[1], sM, sT}) LG_HIP(h, hipStreamWaitEvent(q, h->ev_begin, 0));
-        // bit rows of the whole batch first (one short kernel) so the host never waits behind a distance sweep
-        if ((rc = enq_prep(h, pl, 0, B, sD[0], h->ev_prep))) return rc;
-        LG_HIP(h, hipStreamWaitEvent(sD[1], h->ev_prep, 0));
-        for (int k = 0; k < nsub; k++) {
-            const int off = k * SB, n = std::min(SB, B - off);
-            if ((rc = enq_dt(h, pl, off, n, sD[k & 1]))) return rc;
-            LG_HIP(h, hipEventRecord(EV(k, 2), sD[k & 1]));
-        }
-        tl.host(Timeline::ENQ1);
-        bool upload_fp = true;
-        if ((rc = finish_orient(h, pl, 0, B, &upload_fp))) return rc;
-        tl.host(Timeline::ORIENT);
-        for (int k = 0; k < nsub; k++) {
-            const int off = k * SB, n = std::min(SB, B - off);
-            LG_HIP(h, hipStreamWaitEvent(sM, EV(k, 2), 0));
-            if ((rc = enq_final(h, pl, off, n, sM, upload_fp, &fargs[k]))) return rc;
-            LG_HIP(h, hipEventRecord(EV(k, 3), sM));
-            LG_HIP(h, hipStreamWaitEvent(sT, EV(k, 3), 0));
-            enq_T(k);
-            LG_HIP(h, hipEventRecord(EV(k, 4), sT));
-            if (k >= 1) { rc = enq_G(k - 1); if (rc) return rc; }
-        }
-    }
-    if (!laned && (rc = enq_G(nsub - 1))) return rc;
-    if (prune) h->last_scored_subs = nsub;
-    tl.mark(Timeline::CNN);
-    if (piped) {  // join: the caller's stream continues after every internal stream
-        for (hipStream_t q : {sD[0], sD[1], sM, sT}) {
-            LG_HIP(h, hipEventRecord(EV(0, 5), q));
-            LG_HIP(h, hipStreamWaitEvent(s, EV(0, 5), 0));
-            LG_HIP(h, hipStreamSynchronize(q));
-        }
-    }
+    Tail t{h, pl, K, use_cnn, prune, std::vector<LgFinalArgs>((size_t)c.ranges), iso_fields(h)};
+    Timeline tl(h->opt.trace, !c.piped, s);
+    if ((rc = c.piped ? schedule_subbatches(t, c, s, tl) : schedule_lanes(t, c, s, tl))) return rc;
+    if (prune) h->last_scored_subs = c.ranges;
     // ---- the rest of select_grasp_point per frame -- rescoring, 3-D point, pre-grasp probes -- on the device (lg_finish_kernel);
     //      one copy of B result rows comes back
     {
         LgFinishArgs fa = finish_args(h, pl, K, use_cnn);
         fa.cand_n = h->cand_n; fa.cand_xy = h->cand_xy; fa.cand_info = h->cand_info; fa.logits = h->logits;
-        fa.slot = prune ? h->surv_slot : nullptr; fa.slot_frames = SB;
+        fa.slot = prune ? h->surv_slot : nullptr; fa.slot_frames = c.SB;
         {
             ProfScope ps(h, "finish", s);
             lg_launch_finish(fa, s);
@@ -976,7 +1000,7 @@ int lg_select_grasp_impl(lg_handle h, const float* depth, const uint8_t* mask, c
         LG_HIP(h, hipMemcpyAsync(h->cand_rows_host, h->cand_rows_dev, sizeof(lg_grasp_candidate) * B * K, hipMemcpyDeviceToHost, s));
     if ((rc = return_results(h, pl, results, use_cnn, "lg_select_grasp", s, &tl))) return rc;
     if (cands) memcpy(cands, h->cand_rows_host, sizeof(lg_grasp_candidate) * B * K);
-    if (use_cnn) { h->last_cnn_B = B; h->last_cnn_K = K; h->last_cnn_SB = SB; h->last_cnn_pruned = prune; }
+    if (use_cnn) { h->last_cnn_B = B; h->last_cnn_K = K; h->last_cnn_SB = c.SB; h->last_cnn_pruned = prune; }
     h->last_patch_floats = use_cnn ? (long long)B * K * lg_cnn_halo_patch_floats() : 0;
     tl.print(B);
     return LG_OK;
@@ -1000,6 +1024,7 @@ int lg_select_grasp_ml_impl(lg_handle h, const float* depth, const uint8_t* mask
     if ((size_t)B * S.max_samples > 0x7fffffffull) return fail(h, LG_ERR_INVALID, "lg_select_grasp_ml: B * max_samples must stay below 2^31");
     pl.label_aware = pl.P.label_aware != 0;
     pl.sparse = true;
+    pl.near = takes_near_launch(h, pl);
     const lg_params& P = pl.P;
     const int M = S.max_samples, chunk = S.chunk > 0 ? S.chunk : LG_ML_DEFAULT_CHUNK;
     hipStream_t s = (hipStream_t)stream_;
@@ -1023,7 +1048,7 @@ int lg_select_grasp_ml_impl(lg_handle h, const float* depth, const uint8_t* mask
     LgFinalArgs fargs;
     // the table needs the bit rows and the bounding boxes only: it runs in front of the distance transform and the host reads
     // its counts behind ev_ml, after everything up to the plane kernel has been queued
-    rc = enq_front(h, pl, s, &fargs, nullptr, [&]() -> int {
+    rc = enq_front(h, pl, s, &fargs, [&]() -> int {
         {
             ProfScope ps(h, "ml_rows", s);
             lg_launch_ml_rows(h->bits, h->win, S, m, B, H, W, pl.WW, s);
@@ -1149,7 +1174,7 @@ int lg_select_grasp_collect_impl(lg_handle h, const float* depth, const uint8_t*
     po.maps[LG_MAP_FLATNESS] = planes[LG_MAP_FLATNESS];
     if ((rc = take_planes(h, po, false))) return rc;
     LgFinalArgs fargs;
-    rc = enq_front(h, po, s, &fargs, nullptr, [&]() -> int {
+    rc = enq_front(h, po, s, &fargs, [&]() -> int {
         enq_erode(h, B, H, W, po.WW, CP.erosion_kernel_size, CP.erosion_iterations, safe, true, s);
         return LG_OK;
     });
@@ -1158,7 +1183,7 @@ int lg_select_grasp_collect_impl(lg_handle h, const float* depth, const uint8_t*
     if ((rc = make_plan(h, ps, depth, safe, B, H, W, pin, nullptr, out_valid))) return rc;
     for (int i = 0; i < LG_NUM_MAPS; i++) ps.maps[i] = i == LG_MAP_FLATNESS ? nullptr : planes[i];
     if (!ps.valid) ps.valid = h->ws_valid;
-    if ((rc = enq_front(h, ps, s, &fargs, nullptr, nothing_after_prep))) return rc;
+    if ((rc = enq_front(h, ps, s, &fargs, nothing_after_prep))) return rc;
     {
         ProfScope pf(h, "col_tip", s);
         lg_launch_col_tip(safe, planes[LG_NUM_MAPS], B, H, W, (uint32_t)ps.P.chamfer_init_dist0, s);
@@ -1228,7 +1253,7 @@ int lg_score_maps(lg_handle h, const float* depth, const uint8_t* mask, int B, i
     if ((rc = take_planes(h, pl, false))) return rc;
     // (orientation: lg_orient_kernel beside the distance-transform sweeps, host threads for frames it hands back)
     LgFinalArgs fargs;
-    if ((rc = enq_front(h, pl, s, &fargs, nullptr, nothing_after_prep))) return rc;
+    if ((rc = enq_front(h, pl, s, &fargs, nothing_after_prep))) return rc;
     if (theta_host)
         for (int b = 0; b < B; b++) theta_host[b] = h->fp_host[b].theta;
     LG_HIP(h, hipGetLastError());

@@ -336,6 +336,60 @@ def test_profiling_slots_count_one_launch_per_call(lane_handles):
         sel.clear_cnn()
 
 
+# ------------------------------------------------------------------------------------------------------------------- LG_TRACE
+def _trace_lines(err, B):
+    """stderr of ONE traced call -> the four numbers of its `gpu timeline` line (None: the call printed none); the host line
+    must be there once."""
+    lines = err.splitlines()
+    assert sum(ln.startswith(f"[lg] B={B} enq1 ") for ln in lines) == 1, err
+    gpu = [ln for ln in lines if ln.startswith("[lg] gpu timeline")]
+    assert len(gpu) <= 1, err
+    if not gpu:
+        return None
+    _, _, fields = gpu[0].partition("):")
+    names, nums = zip(*(f.strip().rsplit(" ", 1) for f in fields.split("|")))
+    assert names == ("sweeps done", "planes", "topk", "cnn"), gpu[0]
+    return [float(x) for x in nums]
+
+
+def test_trace_lines_per_schedule(capfd):
+    """Handles created under LG_TRACE=1, stderr captured at the file descriptor.  B = 4 forced to one lane, then to two: the rows
+    are an untraced handle's byte for byte, and each call prints one host line and one device timeline whose four marks --
+    sweeps, planes, top-k, CNN, all on lane 0's stream -- are finite, not negative and in order.  LG_SUBBATCH=2 at B = 5: the
+    host line only (the stages run on the library's streams), rows equal to the one-sub-batch handle's."""
+    pool, k = R._pool(SIZE), 20
+    plain, traced, piped = R._handles([{}, {"LG_TRACE": "1"}, {"LG_TRACE": "1", "LG_SUBBATCH": "2"}])   # (a setting stays for the next)
+    try:
+        assert traced.options()["LG_TRACE"] == 1 and plain.options()["LG_TRACE"] == 0
+        assert piped.options()["LG_TRACE"] == 1 and piped.options()["LG_SUBBATCH"] == 2
+        m, d = pool.frames(pool.scene_ids(_mixed(4)))
+        for lanes in (1, 2):
+            plain.tail_lanes(lanes)
+            traced.tail_lanes(lanes)
+            want = _run(plain, pool, m, d, k)
+            capfd.readouterr()
+            got = _run(traced, pool, m, d, k)
+            err = capfd.readouterr().err
+            assert want[4] == got[4] == lanes
+            assert got[0] == want[0], f"{lanes} lanes: a traced handle's rows against an untraced handle's"
+            marks = _trace_lines(err, 4)
+            print(f"{lanes} lanes: gpu timeline {marks}")
+            assert marks is not None and len(marks) == 4 and all(np.isfinite(marks)), err
+            assert marks[0] >= 0 and all(a <= b for a, b in zip(marks, marks[1:])), err
+        m, d = pool.frames(pool.scene_ids(_mixed(5)))
+        plain.tail_lanes(0)
+        want = _run(plain, pool, m, d, k)
+        capfd.readouterr()
+        got = _run(piped, pool, m, d, k)
+        err = capfd.readouterr().err
+        assert (got[3]["n_sub"], got[3]["sub_frames"]) == (3, 2) and (want[3]["n_sub"], want[3]["sub_frames"]) == (1, 5)
+        assert got[0] == want[0], "LG_SUBBATCH=2: rows against the one-sub-batch handle's"
+        assert _trace_lines(err, 5) is None, err
+    finally:
+        for s in (traced, plain, piped):
+            s.clear_cnn()
+
+
 # --------------------------------------------------------------------------------------------------- the 8192-patch slice boundary
 def test_second_slice_in_one_lane():
     """129 frames at top_k = 64 with 8193 survivors (tests/cnn_plan.py): once the automatic rule cuts a batch of this size into
